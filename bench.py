@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X dynamic-video-depth step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
-    python bench.py --config 4 [--pairs 64]        BASELINE configs[4] on one GPU (768x1344, fp16 activations) with its parity leg
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full                         the headline line plus the cpu_baseline / parity legs and the configs4 /
+                                                   rccl_one_rank sub-records (minutes of CPU and two more runs)
+    python bench.py --config 4 [--pairs 64]        BASELINE configs[4] on one GPU (768x1344, fp16 activations); --full adds its
+                                                   parity leg
     DVD_RESERVE_GB=24 python bench.py ...           the same with 24 GB of the device taken first (stand-in for RCCL's buffers)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -19,14 +22,20 @@ backward, depth-net backward, gradient all-reduce (N>1) and both Adam updates.  
 resident in HBM before the timed region.
 
 Prints ONE JSON line: whole-job `value` in 48-pair iterations per second (weak scaling:
-every rank owns 48 pairs), plus
+every rank owns 48 pairs), `ms_per_step` (one timed step), plus
   roofline     -- the fused warp+loss op (HBM bound), timed live with events on its stream;
   roofline_mfma -- the matrix kernels (85 % of the step): algorithmic work the timed steps executed, counted by the library per
                   kernel class, over the step time, as a fraction of the 2.5 PFLOP/s dense fp16 MFMA peak; per-class kernel
                   times of the three largest classes from the committed trace (provenance stated);
+and with --full only:
   cpu_baseline -- the CPU oracle (a port of the reference step) on a bounded sample;
   parity       -- the HIP Model against that oracle on the SAME frame pair and weights at the benchmark's image size
-                  (losses and gradients of one step).
+                  (losses and gradients of one step);
+  configs4, rccl_one_rank -- two more lines of this script from child processes (see --no_extras).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 / float64 .npy files (dump_outputs below): two runs
+with the same arguments start from the same seeded weights and synthetic batch, so two builds can be compared file by file
+(with a tolerance: float atomics make two runs of one build differ by about 1e-6 of the largest value).
 """
 import argparse
 import json
@@ -391,6 +400,49 @@ def _sub_bench(args, timeout_s, keep):
         return {'error': repr(e)}
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of each large output by --dump-outputs (a fixed, seeded sample)
+
+
+def _sample(flat, n, seed):
+    """A fixed sample of a 1-D device tensor: `n` seeded positions (sorted) -- all of it when it is not larger."""
+    import numpy as np
+    if flat.numel() <= n:
+        return flat.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), size=n))
+    return flat.detach()[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+
+
+def dump_outputs(out_dir, model, log):
+    """What the timed path (`Model._train_on_batch`) gave its caller in the last timed step, as DIR/<name>.npy: the logged
+    losses (float64), the updated parameters of both networks (scene-flow MLP in full, a seeded sample of the depth net's) and
+    the step's depth maps and integrated scene flow (seeded samples).  About 22 MB at the headline size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for k, v in log.items():
+        if isinstance(v, (int, float)) and not isinstance(v, bool):
+            files['log_' + k] = np.array([v], dtype=np.float64)
+    files['sceneflow_net_params'] = torch.cat([p.detach().reshape(-1) for p in model.net_sceneflow.parameters()]).float().cpu().numpy()
+    # the depth net's parameters as one virtual vector (parameter order), sampled without concatenating them on the device
+    params = [p.detach().reshape(-1) for p in model.net_depth.parameters()]
+    sizes = np.array([p.numel() for p in params], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    idx = np.sort(np.random.default_rng(1).integers(0, int(offs[-1]), size=min(2 * DUMP_SAMPLE, int(offs[-1]))))
+    which = np.searchsorted(offs, idx, side='right') - 1
+    parts = []
+    for i in np.unique(which):
+        sel = torch.from_numpy(idx[which == i] - offs[i]).to(params[i].device)
+        parts.append(params[i][sel].float().cpu().numpy())
+    files['depth_net_params_sample'] = np.concatenate(parts)
+    last = getattr(model, '_last', None) or {}
+    for seed, k in enumerate(('depth_1', 'depth_2', 'sf_all'), start=2):
+        if torch.is_tensor(last.get(k)):
+            files[k + '_sample'] = _sample(last[k].reshape(-1), DUMP_SAMPLE, seed)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+    return sorted(files)
+
+
 def relaunch_under_torchrun(n):
     """`python bench.py --gpus N` without a torch.distributed environment: start N ranks of this script."""
     import socket
@@ -416,8 +468,8 @@ def main():
     ap.add_argument('--depth', choices=('midas', 'hourglass'), default='midas',
                     help="depth network: midas (BASELINE configs[1]/[2]) or the reference's default hourglass (extra bench line)")
     ap.add_argument('--cpu_steps', type=int, default=2,
-                    help='timed oracle steps of the cpu_baseline leg (after 1 warm-up; ~50 s each on a 128-thread host: two keep the '
-                         'default run, which since round 6 also carries the configs4 and rccl_one_rank child lines, inside ~6 minutes)')
+                    help='timed oracle steps of the cpu_baseline leg of --full (after 1 warm-up; ~50 s each on a 128-thread host: two '
+                         'keep the --full run, which also carries the configs4 and rccl_one_rank child lines, inside ~6 minutes)')
     ap.add_argument('--depth_graphs', type=int, default=int(os.environ.get('DVD_DEPTH_GRAPHS', '1')),
                     help='1 (default): replay the depth net from HIP graphs; 0: eager launches')
     ap.add_argument('--depth_chunk', type=int, default=0,
@@ -435,7 +487,7 @@ def main():
                          '(--pairs, default %d)' % PAIRS_CFG4)
     ap.add_argument('--cfg4_parity', choices=('auto', 'oracle', 'hip', 'none'), default='auto',
                     help='--config 4: the parity leg at 768x1344 (one pair): against the fp32 CPU oracle if the host has the memory '
-                         '(auto / oracle), else against the fp32-storage HIP step (hip)')
+                         '(auto / oracle), else against the fp32-storage HIP step (hip).  auto runs it with --full only')
     ap.add_argument('--feed', choices=('hbm', 'host'), default='hbm',
                     help="hbm (default, the contract's `value`): inputs resident in HBM before the timed region; host: every "
                          "step's batch starts in host memory and goes through the pinned double-buffered feeder "
@@ -447,8 +499,14 @@ def main():
                     help='HBM budget of the kept depth-net activation slots (Model.add_arguments: 150); every slot is still '
                          'subject to the free-memory test of keep_slot_fits')
     ap.add_argument('--no_extras', action='store_true',
-                    help='only the headline measurement: without the configs4 and rccl_one_rank sub-records the default N = 1 run '
-                         'adds from child processes of this script')
+                    help='with --full: without the configs4 and rccl_one_rank sub-records the N = 1 run adds from child processes '
+                         'of this script')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline measurement: the cpu_baseline and parity legs, the configs4 and '
+                         'rccl_one_rank sub-records (N = 1) and the parity leg of --config 4.  Off by default: a plain run sets up, '
+                         'warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, ~22 MB)')
     ap.add_argument('--rccl_one_rank', action='store_true',
                     help='N = 1 with a ONE-rank nccl (= RCCL) process group and the collectives of the N-rank step forced '
                          '(dvd_hip.parallel.init_one_rank): plan agreement, loss-sum all-reduces, MLP-gradient all-reduce under the '
@@ -539,6 +597,7 @@ def main():
             torch.distributed.barrier()
         dt = time.time() - t0
         warp = wt.summary()
+    dumped = dump_outputs(a.dump_outputs, model, log) if a.dump_outputs and rank == 0 else None
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
     if parallel.is_distributed():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -595,7 +654,10 @@ def main():
         # the collective library behind torch.distributed's 'nccl' backend on ROCm (RCCL) and the planner's head room
         'rccl_version': rccl_version, 'hbm_head_room_GB': head_room_gb,
         'hbm_reserved_by_others_GB': float(os.environ.get('DVD_RESERVE_GB') or 0.0),      # the DVD_RESERVE_GB ballast
+        'full': bool(a.full),
     }
+    if dumped is not None:
+        out['dumped_outputs'] = dumped
     if warp is not None:
         # HBM bytes per launch from the PMC counters cannot be collected inside this process (rocprofv3 --pmc passes of
         # the same launch at 48 x 384 x 672: tools/gpu_visit.sh, stage pmc -> tools/pmc_to_json.py); the committed summary of the
@@ -633,7 +695,8 @@ def main():
         st = model._gscale.tolist()
         out['loss_scale'] = {'log2_S': __import__('math').log2(st[0]) if st[0] > 0 else None, 'target_exponent': st[2],
                              'steps_skipped': st[5]}
-    if world == 1 and a.config == 4 and a.cfg4_parity != 'none' and a.depth == 'midas' and a.gap == GAP:
+    if world == 1 and a.config == 4 and (a.full or a.cfg4_parity in ('oracle', 'hip')) and a.cfg4_parity != 'none' \
+            and a.depth == 'midas' and a.gap == GAP:
         # BASELINE configs[4]'s own image size: one frame pair, the fp16-activation step against the fp32 CPU oracle where
         # the host holds it (~4 x the 60 GB of 384 x 672; --cfg4_parity oracle forces it), else against the fp32-storage HIP
         # step -- which one is stated in parity.reference
@@ -647,7 +710,7 @@ def main():
         out['parity']['reference'] = ('CPU oracle (fp32, ATen-CPU), %.0f s for its step' % first['seconds']) if use_oracle else \
             first['reference']
         out['parity']['host_mem_available_GB'] = host_mem_available_gb()
-    if world == 1 and not a.no_cpu_baseline and a.depth == 'midas' and a.gap == GAP and a.config == 2:
+    if a.full and world == 1 and not a.no_cpu_baseline and a.depth == 'midas' and a.gap == GAP and a.config == 2:
         # the 48-pair model's graph slots hold most of the HBM: release them before the 1-pair parity model is built
         import gc
         del model, batch
@@ -656,7 +719,7 @@ def main():
         first = oracle_first_step()
         out['parity'] = hip_parity(first, device, act_fp16=a.act_fp16)      # (fp16 activations: against the SAME fp32 oracle)
         out['cpu_baseline'] = cpu_baseline(first, timed_steps=max(1, a.cpu_steps))
-    if world == 1 and not a.no_extras and a.config == 2 and not a.act_fp16 and a.depth == 'midas' and a.gap == GAP \
+    if a.full and world == 1 and not a.no_extras and a.config == 2 and not a.act_fp16 and a.depth == 'midas' and a.gap == GAP \
             and a.feed == 'hbm' and not a.rccl_one_rank and a.pairs == PAIRS:
         # Two more lines of the SAME script, from child processes, inside the headline line (so that the driver's BENCH record
         # carries them): BASELINE configs[4] at its own 64 pairs per GPU, and the headline configuration with the data-parallel

@@ -410,6 +410,45 @@ GROUPS = {
 }
 
 
+def _flag_table(model_cls):
+    import argparse
+    parser, _ = model_cls.add_arguments(argparse.ArgumentParser())
+    return {a.dest: [getattr(a.type, '__name__', None if a.type is None else repr(a.type)), a.default, type(a).__name__]
+            for a in parser._actions if a.dest != 'help'}
+
+
+def case_interfaces(name):
+    """The reference's checkpoint and command-line surface, as data (tests/test_state_dict_compat_cpu.py,
+    tests/test_model_surface_cpu.py): state_dict keys (in order) and shapes of MidasNet (encoder: oracle/resnext.py, as
+    torch.hub would return it), HourglassModel_Embed, SceneFlowFieldNet and the --use_cnn FCNUnet, and the
+    (type, default, action) of every flag of Model.add_arguments."""
+    import json
+    import unittest.mock as mock
+    import third_party.hourglass as RH
+    import third_party.MiDaS as RM
+    import visualize.html_visualizer as HV
+    from networks.FCNUnet import FCNUnet as RefUnet
+    from networks.sceneflow_field import SceneFlowFieldNet as RefMLP
+    from oracle import resnext
+    with mock.patch.object(HV, 'Pool', lambda n: None):
+        from models.scene_flow_motion_field import Model as RefModel
+    with mock.patch.object(torch.hub, 'load', lambda repo, entry, *a, **k: resnext.resnext101_32x8d()), \
+            mock.patch.object(RM.BaseModel, 'load', lambda self, path: None):
+        midas = RM.MidasNet(path=None, non_negative=True)
+    unet = RefUnet({'norm': 'none', 'activation': 'lrelu', 'pad_type': 'reflect', 'stride': 1}, n_down=3, feat=32,
+                   block_type='double_conv', in_channel=4, out_channel=3)
+    nets = {'midas': midas, 'hourglass_embed': RH.HourglassModel_Embed(noexp=False, use_embedding=False),
+            'sceneflow_mlp': RefMLP(net_width=256, n_layers=4, time_dependent=True, N_freq_xyz=16, N_freq_t=16),
+            'fcn_unet': unet}
+    out = {'state_dicts': {k: [[n, list(v.shape)] for n, v in m.state_dict().items()] for k, m in nets.items()},
+           'model_flags': _flag_table(RefModel)}
+    with open(os.path.join(OUT_DIR, name + '.json'), 'w') as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+
+
+CASES['interfaces'] = case_interfaces
+
+
 def main():
     torch.set_num_threads(4)
     names = []

@@ -13,6 +13,12 @@ def load_golden(name):
     return {k: z[k] for k in z.files}
 
 
+def load_golden_json(name):
+    import json
+    with open(os.path.join(GOLDEN, name + '.json')) as f:
+        return json.load(f)
+
+
 def t(a, device='cpu'):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 

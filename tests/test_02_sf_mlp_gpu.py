@@ -1,6 +1,7 @@
 """Parity of the fused scene-flow MLP kernels (through the C ABI) with the
 golden fixture generated from the real reference network and with the oracle.
-Arithmetic: two-term fp16-split MFMA products (three partial products, fp32 accumulation; csrc/sf_mlp.hip, csrc/dvd_split.h) against MKL sgemm on the CPU.
+Arithmetic: two-term fp16-split MFMA products (three partial products, fp32 accumulation; csrc/sf_mlp.hip, csrc/dvd_split.h) against MKL sgemm on the CPU
+(the golden fixture) and against the oracle with its 1x1 convolutions in float64 (the ragged sizes, _oracle_f64).
 Tolerances = about 4x the worst value measured on MI355X (round 3, gpurun_out/r03a/parity.jsonl: every gradient tensor
 agrees to 2.6e-6 of its largest element, median 2e-7; the values are appended to $DVD_PARITY_LOG on every run):
   forward           rtol 1e-4, atol 2e-6
@@ -10,6 +11,7 @@ agrees to 2.6e-6 of its largest element, median 2e-7; the values are appended to
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from helpers import golden_mlp_sd, load_golden, t
 from oracle import sceneflow_mlp as M
@@ -23,6 +25,19 @@ def _net_from_sd(sd, time_dependent=True):
     missing = net.load_state_dict(sd, strict=True)
     assert not missing.missing_keys and not missing.unexpected_keys
     return net.cuda()
+
+
+def _oracle_f64(sd, x, t):
+    """M.mlp_forward with the periodic embedding in fp32 (the reference rounds f * v in fp32, and so does the kernel) and the
+    1x1 convolutions in float64.  An fp32 oracle on the host carries summation-order noise of its own (MKL blocks by thread
+    count) of up to ~0.6 of the forward tolerance on these sizes; against float64 the comparison measures the kernels alone."""
+    h = torch.cat([M.periodic_embed(t, 16), M.periodic_embed(x, 16)], 1).double()
+    n_layers = len([k for k in sd if k.endswith('conv.weight')])
+    for i in range(n_layers):
+        h = F.conv2d(h, sd['convs.%d.conv.weight' % i], sd['convs.%d.conv.bias' % i])
+        if i < n_layers - 1:
+            h = F.leaky_relu(h, M.LRELU_SLOPE)
+    return h
 
 
 def _close(got, want, rel, name, max_outliers=0):
@@ -81,17 +96,17 @@ def test_forward_backward_vs_oracle_ragged(B, H, W):
     x = 3.0 * torch.randn(B, 3, H, W, generator=g)
     tt = torch.rand(B, 1, 1, 1, generator=g).expand(B, 1, H, W).contiguous()
     up = torch.randn(B, 3, H, W, generator=g)
-    sdr = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    sdr = {k: v.double().requires_grad_(True) for k, v in sd.items()}
     xr = x.clone().requires_grad_(True)
-    yr = M.mlp_forward(sdr, xr, tt)
-    (yr * up).sum().backward()
+    yr = _oracle_f64(sdr, xr, tt)
+    (yr * up.double()).sum().backward()
     net = _net_from_sd(sd)
     xg = x.cuda().requires_grad_(True)
     yg = net(xg, tt.cuda())
     (yg * up.cuda()).sum().backward()
     np.testing.assert_allclose(yg.detach().cpu().numpy(), yr.detach().numpy(), rtol=1e-4, atol=2e-6)
-    # The oracle runs live on the box's CPU: a pre-activation within fp32 noise of 0 may take the other LeakyReLU slope
-    # there (MKL blocks by thread count).  No such pixel (what MI355X boxes measured): everything to 1e-5.  Otherwise at
+    # A pre-activation within fp32 noise of 0 may take the other LeakyReLU slope on the GPU than in the float64 oracle.
+    # No such pixel (what MI355X boxes measured): everything to 1e-5.  Otherwise at
     # most 2 pixels of g_x are off and the weight gradients carry that pixel's share (a fraction of a percent).
     flips = _close(xg.grad.cpu().numpy(), xr.grad.numpy(), 1e-5, 'g_x', max_outliers=-1)
     assert flips <= 6, 'g_x: %d elements off' % flips

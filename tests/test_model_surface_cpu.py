@@ -1,11 +1,10 @@
 """Drop-in surface of `Model` that can be checked without a GPU: the flag set of
 `add_arguments` (names, types, defaults) and the attribute contract after construction, compared with the
-reference's own class when the reference checkout is present (build container), and against the recorded
-expectations otherwise."""
+reference's own class as recorded in tests/golden/interfaces.json (tests/golden/make_golden.py, case `interfaces`); the
+--use_cnn network's arithmetic is also compared with the reference's module itself where the reference checkout is present."""
 import argparse
 import os
 import sys
-import unittest.mock as mock
 from types import SimpleNamespace
 
 import pytest
@@ -33,21 +32,12 @@ def test_flag_set():
     from dvd_hip.models.scene_flow_motion_field import Model
     ours = _flags(Model)
     assert set(ours) == EXPECTED_FLAGS | OWN_FLAGS
-    if not os.path.isdir(REF):
-        return
-    sys.path.insert(0, REF)
-    try:
-        import visualize.html_visualizer as HV
-        with mock.patch.object(HV, 'Pool', lambda n: None):
-            from models.scene_flow_motion_field import Model as RefModel
-        ref = _flags(RefModel)
-    finally:
-        sys.path.remove(REF)
-        for m in [m for m in list(sys.modules) if getattr(sys.modules[m], '__file__', None) and REF in sys.modules[m].__file__]:
-            del sys.modules[m]
+    ref = helpers.load_golden_json('interfaces')['model_flags']
     assert set(ref) == EXPECTED_FLAGS                      # the recorded expectation is the reference's flag set
-    for k, v in ref.items():                                  # same type, default and action kind for every shared flag
-        assert ours[k] == v, (k, ours[k], v)
+    for k, (typ, default, action) in ref.items():             # same type, default and action kind for every shared flag
+        got = ours[k]
+        assert (getattr(got[0], '__name__', None if got[0] is None else repr(got[0])), got[1], got[2]) == (typ, default, action), \
+            (k, got, (typ, default, action))
 
 
 def test_attribute_contract_after_construction():
@@ -73,6 +63,8 @@ def test_attribute_contract_after_construction():
     with pytest.warns(UserWarning):
         mc = Model(SimpleNamespace(**dict(o, use_cnn=True)), None)
     assert type(mc.net_sceneflow) is FCNUnet and len(mc.net_sceneflow.state_dict()) == 30
+    assert [[k, list(v.shape)] for k, v in mc.net_sceneflow.state_dict().items()] == \
+        helpers.load_golden_json('interfaces')['state_dicts']['fcn_unet']          # the reference's keys, order and shapes
     if os.path.isdir(REF):
         sys.path.insert(0, REF)
         try:

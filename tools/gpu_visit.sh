@@ -3,7 +3,7 @@
 #   TAG=<name> STAGES="tests bench extras trace pmc sq micro a16" bash tools/gpu_visit.sh
 # Everything lands under gpurun_out/$TAG/; what is to be judged is copied from there into profiles/ and committed.
 #   tests   full `-m gpu` suite with the measured-parity log ($DVD_PARITY_LOG)        (PYTEST_ARGS narrows it)
-#   bench   the headline line: python bench.py (parity + cpu_baseline legs included)
+#   bench   the headline line: python bench.py --full (parity + cpu_baseline legs and the configs4 / rccl_one_rank sub-records)
 #   extras  the other bench lines: fp16 activations (with parity), BASELINE configs[4], frame gaps 2 / 4, hourglass, host feed,
 #           two ranks over gloo on the one GPU
 #   trace   rocprofv3 --kernel-trace --stats of bench.py variants (TRACES="name:args;name:args", default fp32 / fp16 / hourglass)
@@ -39,15 +39,15 @@ if has a16; then
   tail -5 $OUT/pytest_a16.log | cut -c1-300
 fi
 if has bench; then
-  timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   echo "bench exit $?" >> $OUT/bench.err
   tail -1 $OUT/bench.json | cut -c1-250; tail -2 $OUT/bench.err | cut -c1-200
 fi
 if has extras; then
   run() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; tail -1 $OUT/bench_$name.json | cut -c1-230; }
-  run fp16 --act_fp16 --cpu_steps 1
-  run cfg4 --config 4 --no_cpu_baseline --steps 2
-  run cfg4_p32 --config 4 --pairs 32 --no_cpu_baseline --steps 2
+  run fp16 --full --act_fp16 --cpu_steps 1
+  run cfg4 --full --config 4 --no_cpu_baseline --steps 2
+  run cfg4_p32 --full --config 4 --pairs 32 --no_cpu_baseline --steps 2
   run gap2 --gap 2 --no_cpu_baseline
   run gap4 --gap 4 --no_cpu_baseline --steps 2
   run gap4_fp16 --gap 4 --act_fp16 --no_cpu_baseline --steps 2
