@@ -17,7 +17,7 @@ c_float = ctypes.c_float
 c_void_p = ctypes.c_void_p
 
 DVD_OK, DVD_EINVAL, DVD_EHIP, DVD_ENOSPC = 0, -1, -2, -3
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class Cameras(ctypes.Structure):
@@ -152,6 +152,7 @@ SIGNATURES = {
     'dvd_xconv_fwd_h': (c_int, [c_void_p] * 5 + [ctypes.POINTER(BnParams), c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     'dvd_xwgrad3_h': (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 7 + [c_void_p]),
     'dvd_xwgrad1s_h': (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 6 + [c_void_p]),
+    'dvd_xwgradk_h': (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 7 + [c_void_p]),      # ABI 8
     'dvd_bnrelu_fwd_t': (c_int, [c_void_p] * 6 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dvd_bnrelu_bwd_t': (c_int, [c_void_p] * 6 + [c_float] + [c_void_p] * 5 + [c_size_t, c_int, c_void_p, c_int, c_int, c_int,
                                                                              c_int, c_void_p, c_void_p]),
@@ -167,6 +168,10 @@ SIGNATURES = {
     'dvd_head1x1_fwd': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'dvd_head1x1_bwd_workspace_bytes': (c_size_t, [c_int]),
     'dvd_head1x1_bwd': (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    'dvd_head3x3_fwd': (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),                  # ABI 8: the hourglass head
+    'dvd_head3x3_bwd_workspace_bytes': (c_size_t, [c_int] * 4),
+    'dvd_head3x3_bwd': (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 4 + [c_void_p]),
+    'dvd_add_f16': (c_int, [c_void_p] * 3 + [c_longlong, c_void_p, c_void_p]),
     'dvd_gscale_init': (c_int, [c_void_p, c_float, c_void_p]),
     'dvd_gscale_step_begin': (c_int, [c_void_p, c_void_p]),
     'dvd_gscale_begin': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -249,6 +249,84 @@ def head1x1(conv, x, relu_in=True):
     return _Head1x1.apply(x, conv.weight, conv.bias, relu_in)
 
 
+class _Head3x3(torch.autograd.Function):
+    """`Conv2d(C, 1, 3, padding=1)(x)`, the hourglass's `pred_layer` (third_party/hourglass.py), with fp16 features and fp32
+    output: the fp16 / fp32 boundary at that network's end, as _Head1x1 is for MiDaS.  Forward folds max|y| into the forward
+    monitor (state[6]); backward starts the pass's loss scale (dvd_gscale_begin from max|g_out| and the head weights), then writes
+    S * gx as fp16 and the unscaled fp32 weight / bias gradients (csrc/a16.hip dvd_head3x3_*)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = x.contiguous()
+        N, C, H, W = x.shape
+        y = torch.empty(N, 1, H, W, device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().dvd_head3x3_fwd(_p(x), _p(weight), _p(bias), _p(y), _p(_fwd_monitor()), N, C, H, W, _stream()),
+                   'dvd_head3x3_fwd')
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from .ops import amax
+        x, weight = ctx.saved_tensors
+        gy = gy.contiguous().float()
+        N, C, H, W = x.shape
+        lib = _lib.load()
+        state = GRAD_SCALE['state']
+        if state is None:
+            raise RuntimeError('fp16 gradients need a loss-scale state (conv.set_grad_scale_state)')
+        _lib.check(lib.dvd_gscale_begin(_p(state), _p(amax(gy)), _p(weight), weight.numel(), _stream()), 'dvd_gscale_begin')
+        gx = torch.empty_like(x)
+        gw = torch.empty_like(weight)
+        gb = torch.empty(1, device=x.device, dtype=torch.float32) if ctx.has_bias else None
+        ws = _workspace(lib.dvd_head3x3_bwd_workspace_bytes(N, C, H, W), x.device)
+        _lib.check(lib.dvd_head3x3_bwd(_p(x), _p(weight), _p(gy), _p(state), _p(gx), _p(gw), _p(gb), _p(ws),
+                                       ctypes.c_size_t(ws.numel()), N, C, H, W, _stream()), 'dvd_head3x3_bwd')
+        return gx, gw, gb
+
+
+def head3x3_supported(conv, x):
+    """Is `conv` a Conv2d(C <= 64, 1, 3, padding 1) that the boundary kernels take for the fp16 GPU tensor x?"""
+    return (x.is_cuda and _is16(x) and x.dim() == 4 and conv.out_channels == 1 and conv.in_channels <= 64 and
+            conv.kernel_size == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1) and
+            tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros' and
+            conv.weight.dtype == torch.float32)
+
+
+def head3x3(conv, x):
+    """conv(x) with fp16 features in and fp32 out, for a Conv2d(C, 1, 3, padding=1) (see head3x3_supported)."""
+    if not head3x3_supported(conv, x):
+        raise RuntimeError('head3x3: %r on a %s %s tensor is not the fp16 depth head' % (conv, x.device, x.dtype))
+    return _Head3x3.apply(x, conv.weight, conv.bias)
+
+
+class _AddF16(torch.autograd.Function):
+    """a + b for fp16 GPU tensors on csrc/a16.hip (dvd_add_f16), max|a + b| folded into the forward monitor (state[6]) -- an
+    fp16 sum can overflow where its summands did not, and the fused ReLUs downstream would hide the Inf from every later
+    epilogue.  Backward hands the gradient to both summands."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        y = torch.empty_like(a)
+        _lib.check(_lib.load().dvd_add_f16(_p(a), _p(b), _p(y), ctypes.c_longlong(a.numel()), _p(_fwd_monitor()), _stream()),
+                   'dvd_add_f16')
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, g
+
+
+def add_f16(a, b):
+    """a + b of two fp16 GPU tensors of the same shape under the overflow guard (see _AddF16)."""
+    if not (a.is_cuda and _is16(a) and _is16(b) and a.shape == b.shape and a.device == b.device):
+        raise RuntimeError('add_f16: needs two fp16 GPU tensors of one shape (got %s %s, %s %s)' % (a.dtype, tuple(a.shape), b.dtype,
+                                                                                                  tuple(b.shape)))
+    return _AddF16.apply(a, b)
+
+
 class _UpsampleBilinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, out_hw, align_corners):
@@ -1057,11 +1135,17 @@ def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rows
     if _is16(gy):        # fp16 operands: one MFMA per product, result times 1 / (loss scale) (csrc/xwgrad3.hip H16)
         if not _is16(x):
             raise RuntimeError('xconv_wgrad: fp16 gradient with an fp32 activation')
-        if wshape[2] not in (1, 3) or (groups > 1 and wshape[2] != 3):
-            raise RuntimeError('xconv: the fp16 weight gradient exists for 1x1 and 3x3 kernels only (got %s)' % (tuple(wshape),))
+        if wshape[2] not in (1, 3, 5, 7, 11) or (groups > 1 and wshape[2] != 3):
+            raise RuntimeError('xconv: the fp16 weight gradient exists for 1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 '
+                               'kernels (got %s)' % (tuple(wshape),))
         N, Cin, H, W = x.shape
         gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        if wshape[2] == 3:
+        if wshape[2] in (5, 7, 11):      # the hourglass's inception branches (csrc/xwgrad3.hip xwgradk, H16)
+            KS = wshape[2]
+            ws = _workspace(lib.dvd_xwgradk_workspace_bytes(N, Cin, wshape[0], H, W, KS), x.device)
+            _lib.check(lib.dvd_xwgradk_h(_p(x), _p(gy), _p(_gs(1)), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, wshape[0],
+                                         H, W, KS, int(bool(relu_in)), _stream()), 'dvd_xwgradk_h')
+        elif wshape[2] == 3:
             ws = _workspace(lib.dvd_xwgrad3_workspace_bytes(N, Cin, wshape[0], H, W, groups), x.device)
             _lib.check(lib.dvd_xwgrad3_h(_p(x), _p(gy), _p(_gs(1)), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, wshape[0],
                                          H, W, groups, int(bool(relu_in)), _stream()), 'dvd_xwgrad3_h')

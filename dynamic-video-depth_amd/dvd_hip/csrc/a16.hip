@@ -10,6 +10,10 @@
 //     fp16 features and writes the fp32 head output; backward reads the fp32 output gradient (the depth gradient of the
 //     warp+loss kernel, arbitrary magnitude), writes the fp16 feature gradient MULTIPLIED BY THE STEP'S LOSS SCALE S, and the
 //     weight / bias gradients (fp32, from the unscaled fp32 gradient).  HBM bound: 2 C + 4 bytes per pixel forward.
+//   * dvd_head3x3_{fwd,bwd}: the same boundary for the hourglass net, whose head is `pred_layer = Conv2d(64, 1, 3, padding 1)`
+//     (third_party/hourglass.py:175-182), and dvd_add_f16: the sums of its two parallel paths (:60-158) in fp16 with max |y|
+//     folded into the forward monitor (state[6]) -- a sum that overflows would otherwise reach ReLUs that map Inf / NaN to values
+//     no later epilogue flags.
 //   * the loss-scale policy, entirely on the device (no host read-back anywhere in the step):
 //       state[0] = S, state[1] = 1 / S          set by dvd_gscale_begin at the start of every depth-net backward pass: the power
 //                                               of two that puts max|g_out| * max|w_head| at 2^target
@@ -235,6 +239,147 @@ __global__ __launch_bounds__(256) void cast_scale_kernel(const T* __restrict__ i
   }
 }
 
+// ---- the hourglass's depth head `pred_layer = Conv2d(C, 1, 3, padding 1)` (third_party/hourglass.py): fp16 features in, fp32 out.
+// Tap t = 3 ky + kx reads the input at offset (ky - 1, kx - 1); zero padding.  A thread owns one pixel; the C x 9 weights sit in LDS.
+constexpr int kH3CPB = 8;                      // weight gradient: channels per block (9 accumulators each, + the bias)
+
+__global__ __launch_bounds__(256) void head3x3_fwd_kernel(const _Float16* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ y, int C, int H, int W,
+                                                          long long total, float* fmax) {
+  __shared__ float sw[kHeadMaxC * 9];
+  for (int i = threadIdx.x; i < C * 9; i += 256) sw[i] = w[i];
+  __syncthreads();
+  const float b = bias ? bias[0] : 0.0f;
+  const int HW = H * W;
+  float ym = 0.0f;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long n = i / HW;
+    const int p = (int)(i - n * HW), r = p / W, col = p - r * W;
+    bool ok[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) ok[t] = (unsigned)(r + t / 3 - 1) < (unsigned)H && (unsigned)(col + t % 3 - 1) < (unsigned)W;
+    const _Float16* xp = x + (size_t)n * C * HW + p;
+    float acc = b;
+    for (int c = 0; c < C; ++c) {
+      const _Float16* xc = xp + (size_t)c * HW;
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+        if (ok[t]) acc = __builtin_fmaf(sw[c * 9 + t], (float)xc[(t / 3 - 1) * W + (t % 3 - 1)], acc);
+    }
+    y[i] = acc;
+    if (fmax) ym = amax_acc(ym, acc);
+  }
+  if (fmax) wave_amax_to(ym, fmax);       // forward monitor of the fp16 overflow guard: an Inf / NaN feature shows up here
+}
+
+// the 3 x 3 neighbourhood of output gradients that reaches input pixel (r, col): g[t] = gy[r - (ky - 1)][col - (kx - 1)], 0 outside
+__device__ __forceinline__ void head3x3_gy_taps(const float* __restrict__ gyn, int r, int col, int H, int W, float (&g)[9]) {
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int rr = r - (t / 3 - 1), cc = col - (t % 3 - 1);
+    g[t] = ((unsigned)rr < (unsigned)H && (unsigned)cc < (unsigned)W) ? gyn[rr * W + cc] : 0.0f;
+  }
+}
+
+// gx[n][c][q] = S * sum_t w[c][t] * g[t] as _Float16; max |S gx| (before the conversion) -> gmax
+__global__ __launch_bounds__(256) void head3x3_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
+                                                               const float* __restrict__ gstate, _Float16* __restrict__ gx, float* gmax,
+                                                               int C, int H, int W, long long total) {
+  __shared__ float sw[kHeadMaxC * 9];
+  const float S = gstate ? gstate[0] : 1.0f;
+  for (int i = threadIdx.x; i < C * 9; i += 256) sw[i] = w[i] * S;       // (S is a power of two: exact)
+  __syncthreads();
+  const int HW = H * W;
+  float gm = 0.0f;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long n = i / HW;
+    const int q = (int)(i - n * HW), r = q / W, col = q - r * W;
+    float g[9];
+    head3x3_gy_taps(gy + (size_t)n * HW, r, col, H, W, g);
+    _Float16* gxp = gx + (size_t)n * C * HW + q;
+    for (int c = 0; c < C; ++c) {
+      float o = 0.0f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) o = __builtin_fmaf(sw[c * 9 + t], g[t], o);
+      gxp[(size_t)c * HW] = (_Float16)o;
+      gm = amax_acc(gm, o);
+    }
+  }
+  if (gmax) wave_amax_to(gm, gmax);        // observed max of the scaled fp16 gradient (loss-scale policy)
+}
+
+// partial[chunk][c * 9 + t] = sum over the chunk's pixels q of x[c][q] * g[t]; partial[chunk][9 C] = sum gy (channel group 0).
+// blockIdx.x: pixel chunk (fixed range of the flattened N * H * W pixels), blockIdx.y: group of kH3CPB channels.
+__global__ __launch_bounds__(256) void head3x3_bwd_weight_kernel(const _Float16* __restrict__ x, const float* __restrict__ gy,
+                                                                 float* __restrict__ partial, int C, int H, int W, long long total,
+                                                                 long long chunk) {
+  constexpr int NA = kH3CPB * 9 + 1;
+  __shared__ float red[4][NA];
+  const int cg = blockIdx.y * kH3CPB;
+  const int HW = H * W;
+  float s[NA];
+#pragma unroll
+  for (int k = 0; k < NA; ++k) s[k] = 0.0f;
+  const long long i0 = blockIdx.x * chunk, i1 = (i0 + chunk) < total ? (i0 + chunk) : total;
+  for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const long long n = i / HW;
+    const int q = (int)(i - n * HW), r = q / W, col = q - r * W;
+    float g[9];
+    head3x3_gy_taps(gy + (size_t)n * HW, r, col, H, W, g);
+    s[NA - 1] += g[4];                                   // gy[q] itself: the bias gradient
+    const _Float16* xp = x + (size_t)n * C * HW + q;
+#pragma unroll
+    for (int j = 0; j < kH3CPB; ++j) {
+      if (cg + j >= C) continue;                         // uniform
+      const float xv = (float)xp[(size_t)(cg + j) * HW];
+#pragma unroll
+      for (int t = 0; t < 9; ++t) s[j * 9 + t] = __builtin_fmaf(xv, g[t], s[j * 9 + t]);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NA; ++k) {
+    const float v = wave_sum(s[k]);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < NA; k += 256) {
+    const float v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    float* dst = partial + (size_t)blockIdx.x * (C * 9 + 1);
+    if (k < NA - 1) {
+      if (cg + k / 9 < C) dst[(cg + k / 9) * 9 + k % 9] = v;
+    } else if (blockIdx.y == 0) {
+      dst[C * 9] = v;
+    }
+  }
+}
+
+static long long head3x3_chunks(long long total) {      // pixel chunks of the weight gradient (a fixed function of the shape)
+  long long c = (total + 1023) / 1024;
+  return c < 1 ? 1 : (c > 256 ? 256 : c);
+}
+
+// y = a + b for _Float16 tensors (the sum is formed in fp32 and rounded once: the fp16 sum), max |y| -> fmax
+__global__ __launch_bounds__(256) void add_f16_kernel(const _Float16* __restrict__ a, const _Float16* __restrict__ b,
+                                                      _Float16* __restrict__ y, long long n, int vec, float* fmax) {
+  float m = 0.0f;
+  if (vec) {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < (n >> 2); i += (long long)gridDim.x * 256) {
+      const float4 u = ld4(a + i * 4), v = ld4(b + i * 4);
+      const float4 o = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+      st4(y + i * 4, o);
+      m = amax_acc(amax_acc(amax_acc(amax_acc(m, o.x), o.y), o.z), o.w);
+    }
+  } else {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+      const float o = (float)a[i] + (float)b[i];
+      y[i] = (_Float16)o;
+      m = amax_acc(m, o);
+    }
+  }
+  if (fmax) wave_amax_to(m, fmax);
+}
+
 static int blocks_for(long long items) {
   long long b = (items + 255) / 256;
   if (b > 2048) b = 2048;
@@ -323,6 +468,62 @@ int dvd_cast_scale_f32(const void* in, int f16, float* out, long long n, const f
   dvd::bytes_add(DVD_BYTES_ELEMENTWISE, (double)n * ((f16 ? 2.0 : 4.0) + 4.0));
   DVD_DISPATCH_T(f16, hipLaunchKernelGGL(dvd::cast_scale_kernel<T>, dim3(dvd::blocks_for(n >> 2)), dim3(256), 0,
                                          static_cast<hipStream_t>(stream), static_cast<const T*>(in), out, n >> 2, scale));
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+int dvd_head3x3_fwd(const void* x, const float* w, const float* bias, float* y, float* fwd_amax, int N, int C, int H, int W,
+                    dvd_stream_t stream) {
+  DVD_REQUIRE(x && w && y, "head3x3 fwd: null pointer");
+  DVD_REQUIRE(N > 0 && C > 0 && C <= dvd::kHeadMaxC && H > 0 && W > 0 && (long long)C * H * W < (1ll << 31),
+              "head3x3 fwd: bad shape N=%d C=%d H=%d W=%d (C <= 64)", N, C, H, W);
+  const long long total = (long long)N * H * W;
+  dvd::bytes_add(DVD_BYTES_ELEMENTWISE, (double)total * (2.0 * C + 4.0));
+  hipLaunchKernelGGL(dvd::head3x3_fwd_kernel, dim3(dvd::blocks_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const _Float16*>(x), w, bias, y, C, H, W, total, fwd_amax);
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+size_t dvd_head3x3_bwd_workspace_bytes(int N, int C, int H, int W) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)dvd::head3x3_chunks((long long)N * H * W) * (9 * C + 1) * sizeof(float);
+}
+
+int dvd_head3x3_bwd(const void* x, const float* w, const float* gy, const float* gscale_state, void* gx, float* gw, float* gb,
+                    void* workspace, size_t workspace_bytes, int N, int C, int H, int W, dvd_stream_t stream) {
+  DVD_REQUIRE(x && w && gy && gx && workspace, "head3x3 bwd: null pointer");
+  DVD_REQUIRE(N > 0 && C > 0 && C <= dvd::kHeadMaxC && H > 0 && W > 0 && (long long)C * H * W < (1ll << 31),
+              "head3x3 bwd: bad shape N=%d C=%d H=%d W=%d (C <= 64)", N, C, H, W);
+  if (workspace_bytes < dvd_head3x3_bwd_workspace_bytes(N, C, H, W)) {
+    dvd::set_error("head3x3 bwd: workspace too small");
+    return DVD_ENOSPC;
+  }
+  const long long total = (long long)N * H * W;
+  const long long chunks = dvd::head3x3_chunks(total), chunk = (total + chunks - 1) / chunks;
+  dvd::bytes_add(DVD_BYTES_ELEMENTWISE, (double)total * (2.0 * 2 * C + 4.0));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* gmax = gscale_state ? const_cast<float*>(gscale_state) + 3 : nullptr;
+  hipLaunchKernelGGL(dvd::head3x3_bwd_data_kernel, dim3(dvd::blocks_for(total)), dim3(256), 0, s, gy, w, gscale_state,
+                     static_cast<_Float16*>(gx), gmax, C, H, W, total);
+  DVD_LAUNCH_OK();
+  if (gw || gb) {
+    hipLaunchKernelGGL(dvd::head3x3_bwd_weight_kernel, dim3((unsigned)chunks, (C + dvd::kH3CPB - 1) / dvd::kH3CPB), dim3(256), 0, s,
+                       static_cast<const _Float16*>(x), gy, static_cast<float*>(workspace), C, H, W, total, chunk);
+    DVD_LAUNCH_OK();
+    hipLaunchKernelGGL(dvd::head1x1_reduce_kernel, dim3(9 * C + 1), dim3(256), 0, s, static_cast<const float*>(workspace), (int)chunks,
+                       9 * C, gw, gb);
+    DVD_LAUNCH_OK();
+  }
+  return DVD_OK;
+}
+
+int dvd_add_f16(const void* a, const void* b, void* y, long long n, float* fwd_amax, dvd_stream_t stream) {
+  DVD_REQUIRE(a && b && y && n > 0, "add_f16: bad arguments");
+  const int vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(y)) & 7) == 0;
+  dvd::bytes_add(DVD_BYTES_ELEMENTWISE, (double)n * 6.0);
+  hipLaunchKernelGGL(dvd::add_f16_kernel, dim3(dvd::blocks_for(vec ? n >> 2 : n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const _Float16*>(a), static_cast<const _Float16*>(b), static_cast<_Float16*>(y), n, vec, fwd_amax);
   DVD_LAUNCH_OK();
   return DVD_OK;
 }

@@ -421,38 +421,42 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
 // row r + pad + 1 is stored).  The fragment of column offset s is eight pixels starting s pixels off the lane's cell: the
 // lane reads the cell and both neighbours as 16-byte cells (conflict free) and takes the run out of the 12 dwords -- a plain
 // register selection for even s, v_alignbit for odd s (one shared chain of alignbits serves all odd offsets).
-template <int KS, int KX0, int KXN>
+// H16 (fp16 activation storage): the fp16 tensors themselves are the operands -- one term, no operand scale, the staging a copy,
+// ONE MFMA per product instead of three, the LDS of the second term not allocated; the result is multiplied by *out_scale.
+template <bool H16, int KS, int KX0, int KXN>
 __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
   constexpr int PAD = KS / 2, NS = KS + 1, CB = 32, NT = 64 * KS;
+  constexpr int EB = H16 ? 2 : 4, NTERM = H16 ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
-  unsigned char* sG = smem3;                                   // [buffer 2][term 2][co 32][kW3GPitch]
-  unsigned char* sX = smem3 + 2 * 2 * CB * kW3GPitch;          // [term 2][slot NS][ci 32][kW3XPitch]
+  constexpr int kGBuf = NTERM * CB * kW3GPitch;                // one gy buffer: [term NTERM][co 32][kW3GPitch]
+  unsigned char* sG = smem3;                                   // [buffer 2][term][co 32][kW3GPitch]
+  unsigned char* sX = smem3 + 2 * kGBuf;                       // [term][slot NS][ci 32][kW3XPitch]
   constexpr int kXTerm = NS * CB * kW3XPitch;
-  const float sx = pow2_scale(a.x_amax[0]), sg = pow2_scale(a.g_amax[0]);
+  const float sx = H16 ? 1.0f : pow2_scale(a.x_amax[0]), sg = H16 ? 1.0f : pow2_scale(a.g_amax[0]);
   const int tid = threadIdx.x, lane = tid & 63, ky = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int co0 = blockIdx.z * CB, ci0 = blockIdx.y * CB;
   const size_t plane = (size_t)a.H * a.W;
   const int items = a.N * a.nstrips * a.nrseg;
   constexpr int GQ = CB * 16, XQ = CB * 20, NQ = (GQ + XQ + NT - 1) / NT;
-  float4 stg[NQ];
+  typename Quad<H16>::type stg[NQ];
   const bool wvec = (a.W & 3) == 0;
   auto slot_of = [](int row) { return (row + 64) % NS; };      // rows >= -PAD
   auto stage_load = [&](int n, int c0, int grow, int xrow) {   // gy row `grow` (< 0: none) and x row `xrow`
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const int q = i * NT + tid;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      typename Quad<H16>::type v = zero_quad<H16>();
       if (q < GQ) {
         const int ch = q >> 4, px = c0 + ((q & 15) << 2);
         if (grow >= 0 && (co0 + ch) < a.Cout && grow < a.H)
-          v = load_quad<false>(static_cast<const float*>(a.gy) + ((size_t)n * a.Cout + co0 + ch) * plane + (size_t)grow * a.W, px, a.W,
-                               wvec && px + 3 < a.W, false);
+          v = load_quad<H16>(static_cast<const unsigned char*>(a.gy) + (((size_t)n * a.Cout + co0 + ch) * plane + (size_t)grow * a.W) * EB,
+                             px, a.W, wvec && px + 3 < a.W, false);
       } else if (q < GQ + XQ) {
         const int qq = q - GQ;
         const int ch = qq / 20, px = c0 - 8 + ((qq - ch * 20) << 2);
         if ((ci0 + ch) < a.Cin && xrow >= 0 && xrow < a.H)
-          v = load_quad<false>(static_cast<const float*>(a.x) + ((size_t)n * a.Cin + ci0 + ch) * plane + (size_t)xrow * a.W, px, a.W,
-                               wvec && px >= 0 && px + 3 < a.W, a.relu_in != 0);
+          v = load_quad<H16>(static_cast<const unsigned char*>(a.x) + (((size_t)n * a.Cin + ci0 + ch) * plane + (size_t)xrow * a.W) * EB,
+                             px, a.W, wvec && px >= 0 && px + 3 < a.W, a.relu_in != 0);
       }
       stg[i] = v;
     }
@@ -463,10 +467,10 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
       const int q = i * NT + tid;
       if (q >= GQ + XQ) continue;
       if (q < GQ) {
-        store_quad<false>(sG + gbuf * (2 * CB * kW3GPitch) + (q >> 4) * kW3GPitch + ((q & 15) << 3), CB * kW3GPitch, stg[i], sg);
+        store_quad<H16>(sG + gbuf * kGBuf + (q >> 4) * kW3GPitch + ((q & 15) << 3), CB * kW3GPitch, stg[i], sg);
       } else {
         const int qq = q - GQ, ch = qq / 20;
-        store_quad<false>(sX + (xslot * CB + ch) * kW3XPitch + ((qq - ch * 20) << 3), kXTerm, stg[i], sx);
+        store_quad<H16>(sX + (xslot * CB + ch) * kW3XPitch + ((qq - ch * 20) << 3), kXTerm, stg[i], sx);
       }
     }
   };
@@ -496,13 +500,13 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
       stage_store(slot_of(r + 1 + PAD), (r + 1) & 1);
       stage_load(n, c0, r + 2, r + 2 + PAD);
       const unsigned char* xr = xa + slot_of(r - PAD + ky) * (CB * kW3XPitch);
-      const unsigned char* gr = ga + (r & 1) * (2 * CB * kW3GPitch);
+      const unsigned char* gr = ga + (r & 1) * kGBuf;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {                // four K steps of 16 pixels
-        f16x8 A[2];
-        unsigned d[2][12];                         // per term: previous cell, the lane's cell, next cell (24 pixels)
+        f16x8 A[NTERM];
+        unsigned d[NTERM][12];                     // per term: previous cell, the lane's cell, next cell (24 pixels)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        for (int t = 0; t < NTERM; ++t) {
           A[t] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(gr + t * (CB * kW3GPitch) + s * 32));
           const unsigned char* xc = xr + t * kXTerm + s * 32;
           const u32x4 p = *reinterpret_cast<const u32x4*>(xc - 16), c = *reinterpret_cast<const u32x4*>(xc),
@@ -515,9 +519,9 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
         for (int kx = 0; kx < KXN; ++kx) {
           const int sh = KX0 + kx - PAD;           // column offset in pixels (compile-time after unrolling)
           const int st = 8 + sh;                   // first pixel of the run inside the 24-pixel window (3 .. 13)
-          f16x8 B[2];
+          f16x8 B[NTERM];
 #pragma unroll
-          for (int t = 0; t < 2; ++t) {
+          for (int t = 0; t < NTERM; ++t) {
             u32x4 f;
             if ((st & 1) == 0) {
               const int j = st >> 1;
@@ -529,15 +533,19 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
             }
             B[t] = __builtin_bit_cast(f16x8, f);
           }
-          acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], B[0], acc[kx], 0, 0, 0);     // small terms first
-          acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[1], acc[kx], 0, 0, 0);
-          acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[0], acc[kx], 0, 0, 0);
+          if constexpr (H16) {
+            acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[0], acc[kx], 0, 0, 0);
+          } else {
+            acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], B[0], acc[kx], 0, 0, 0);     // small terms first
+            acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[1], acc[kx], 0, 0, 0);
+            acc[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[0], acc[kx], 0, 0, 0);
+          }
         }
       }
     }
   }
   float* dst = a.partial + (size_t)blockIdx.x * (KS * KS) * a.Cout * a.Cin;      // partial[s][tap][Cout][Cin]
-  const float unscale = 1.0f / (sx * sg);
+  const float unscale = H16 ? (a.out_scale ? a.out_scale[0] : 1.0f) : 1.0f / (sx * sg);
 #pragma unroll
   for (int kx = 0; kx < KXN; ++kx) {
     const int tap = ky * KS + KX0 + kx;
@@ -1253,7 +1261,7 @@ size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) {
 }
 
 // ---- 5x5 / 7x7 / 11x11
-static bool wgk_plan(int N, int Cin, int Cout, int H, int W, int KS, dvd::Wg3Plan& p) {
+static bool wgk_plan(int N, int Cin, int Cout, int H, int W, int KS, bool h16, dvd::Wg3Plan& p) {
   if (KS != 5 && KS != 7 && KS != 11) return false;
   p.nco = (Cout + 31) / 32;
   p.nci = (Cin + 31) / 32;
@@ -1267,23 +1275,25 @@ static bool wgk_plan(int N, int Cin, int Cout, int H, int W, int KS, dvd::Wg3Pla
   const long long items = (long long)N * p.nstrips * p.nrseg;
   if (S > items) S = (int)items;
   p.S = S;
-  p.lds = (size_t)2 * 2 * 32 * dvd::kW3GPitch + (size_t)2 * (KS + 1) * 32 * dvd::kW3XPitch;
+  const int nterm = h16 ? 1 : 2;                               // fp16 operands: one term, half the LDS
+  p.lds = (size_t)2 * nterm * 32 * dvd::kW3GPitch + (size_t)nterm * (KS + 1) * 32 * dvd::kW3XPitch;
   return true;
 }
 
 size_t dvd_xwgradk_workspace_bytes(int N, int Cin, int Cout, int H, int W, int KS) {
   dvd::Wg3Plan p;
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !wgk_plan(N, Cin, Cout, H, W, KS, p)) return 0;
-  return (size_t)p.S * KS * KS * Cout * Cin * sizeof(float);
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !wgk_plan(N, Cin, Cout, H, W, KS, false, p)) return 0;
+  return (size_t)p.S * KS * KS * Cout * Cin * sizeof(float);       // (the slice count does not depend on the storage)
 }
 
-int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
-                size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
-  DVD_REQUIRE(x && gy && gw && workspace && x_amax && gy_amax, "xwgradk: null pointer");
+static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
+                        size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, bool h16,
+                        const float* out_scale, dvd_stream_t stream) {
+  DVD_REQUIRE(x && gy && gw && workspace && (h16 || (x_amax && gy_amax)), "xwgradk: null pointer");
   DVD_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "xwgradk: bad shape");
   DVD_REQUIRE((long long)H * W * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 31), "xwgradk: image too large for 32-bit offsets");
   dvd::Wg3Plan p;
-  DVD_REQUIRE(wgk_plan(N, Cin, Cout, H, W, KS, p), "xwgradk: kernel size %d (5, 7 and 11 are covered)", KS);
+  DVD_REQUIRE(wgk_plan(N, Cin, Cout, H, W, KS, h16, p), "xwgradk: kernel size %d (5, 7 and 11 are covered)", KS);
   const size_t need = (size_t)p.S * KS * KS * Cout * Cin * sizeof(float);
   if (workspace_bytes < need) {
     dvd::set_error("xwgradk: workspace %zu < %zu bytes", workspace_bytes, need);
@@ -1295,7 +1305,7 @@ int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const floa
   a.gy = gy;
   a.x_amax = x_amax;
   a.g_amax = gy_amax;
-  a.out_scale = nullptr;
+  a.out_scale = out_scale;
   a.partial = static_cast<float*>(workspace);
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.G = 1; a.nco = p.nco;
@@ -1309,20 +1319,30 @@ int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const floa
     DVD_LAUNCH_OK();
     return DVD_OK;
   };
+  auto run = [&](auto h) -> int {
+    constexpr bool H16 = decltype(h)::value;
+    if (KS == 5) return go(dvd::xwgradk_kernel<H16, 5, 0, 5>, 5);
+    if (KS == 7) return go(dvd::xwgradk_kernel<H16, 7, 0, 7>, 7);
+    if (int e = go(dvd::xwgradk_kernel<H16, 11, 0, 6>, 11)) return e;     // columns 0 .. 5
+    return go(dvd::xwgradk_kernel<H16, 11, 6, 5>, 11);                    // columns 6 .. 10 (disjoint taps of the same partials)
+  };
   dvd::flops_add(DVD_FLOP_XWGRADK, 2.0 * KS * KS * N * (double)Cout * Cin * (double)H * W);
-  if (KS == 5) {
-    if (int e = go(dvd::xwgradk_kernel<5, 0, 5>, 5)) return e;
-  } else if (KS == 7) {
-    if (int e = go(dvd::xwgradk_kernel<7, 0, 7>, 7)) return e;
-  } else {
-    if (int e = go(dvd::xwgradk_kernel<11, 0, 6>, 11)) return e;     // columns 0 .. 5
-    if (int e = go(dvd::xwgradk_kernel<11, 6, 5>, 11)) return e;     // columns 6 .. 10 (disjoint taps of the same partials)
-  }
+  if (int e = h16 ? run(std::true_type{}) : run(std::false_type{})) return e;
   const long long per = (long long)KS * KS * Cout * Cin;
   hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
                      static_cast<const float*>(workspace), gw, p.S, KS * KS, Cout, Cin);
   DVD_LAUNCH_OK();
   return DVD_OK;
+}
+
+int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
+                size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
+  return xwgradk_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, KS, relu_in, false, nullptr, stream);
+}
+
+int dvd_xwgradk_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
+                  int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
+  return xwgradk_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, KS, relu_in, true, out_scale, stream);
 }
 
 int dvd_xwgrad_select(int variant) {

@@ -138,7 +138,8 @@ class Model(NetInterface):
         parser.add_argument('--act_fp16', action='store_true',
                             help='BASELINE configs[4]: store the depth net\'s activations (and their gradients) as fp16 in HBM -- '
                                  'fp32 parameters, fp32 accumulation, fp32 loss sums; gradients carry a power-of-two loss scale kept on '
-                                 'the device (csrc/a16.hip); a step whose fp16 gradients overflow skips its depth-net update.  MiDaS only')
+                                 'the device (csrc/a16.hip); a step whose fp16 gradients overflow skips its depth-net update.  Both '
+                                 'depth nets: MiDaS (--midas) and the hourglass')
         parser.add_argument('--max_act_overflow_skips', type=int, default=25,
                             help='--act_fp16: consecutive steps skipped because an fp16 ACTIVATION overflowed after which the run '
                                  'stops with an error (a warning from the third on): the loss scale cannot cure that')
@@ -217,8 +218,6 @@ class Model(NetInterface):
         self._gscale = None
         self._steps_skipped = 0
         if getattr(self.opt, 'act_fp16', False):
-            if not self.opt.midas:
-                raise NotImplementedError('--act_fp16 covers the MiDaS depth net (BASELINE configs[4])')
             self.net_depth.act_dtype = torch.float16
             self._gscale = ops.gscale_new(self.device)       # lives as long as the model: captured graphs hold its address
             # what each network's guarded Adam step subtracts from its step number (checkpoints carry the effective step)
@@ -445,8 +444,12 @@ class Model(NetInterface):
     def _slot_bytes_per_px(self):
         """Autograd state a kept slot holds per image pixel: measured on the slots captured so far, else an a-priori figure
         (as measured in round 6: MiDaS with fused epilogues 4.8 KB -- 55.8 GB per 48 images at 384x672 --, 2.5 KB with fp16
-        activations, the hourglass 6.7 KB; rounds 4-5 assumed 4.4 / 2.4 KB)."""
-        apriori = (2500.0 if self._gscale is not None else 4900.0) if self.opt.midas else 6700.0
+        activations, the hourglass 6.7 KB; rounds 4-5 assumed 4.4 / 2.4 KB).  The hourglass with fp16 activations: 4.9 KB
+        (Model._keep_per_px after two steps of 48 pairs at 384x672 with 16-image slots on MI355X: 4 878 bytes, fp32 6 657)."""
+        if self.opt.midas:
+            apriori = 2500.0 if self._gscale is not None else 4900.0
+        else:
+            apriori = 4900.0 if self._gscale is not None else 6700.0
         return max(apriori, self._keep_per_px)
 
     def _pick_depth_chunk(self, B, HW, mlp_need, device):

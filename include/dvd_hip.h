@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define DVD_ABI_VERSION 7
+#define DVD_ABI_VERSION 8
 
 typedef void* dvd_stream_t; /* hipStream_t */
 
@@ -513,6 +513,11 @@ int dvd_xwgrad3_h(const void* x, const void* gy, const float* out_scale, float* 
                   int Cin_total, int Cout_total, int H, int W, int groups, int relu_in, dvd_stream_t stream);
 int dvd_xwgrad1s_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
                    int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream);
+/* ABI 8: dvd_xwgradk with fp16 operands -- the 5x5 / 7x7 / 11x11 weight gradients of the hourglass's inception branches
+ * (third_party/hourglass.py:21-57) under fp16 activation storage.  Same walk, plan and workspace (dvd_xwgradk_workspace_bytes) as
+ * dvd_xwgradk; one v_mfma_f32_32x32x16_f16 per product, fp32 accumulation, result times out_scale[0]; deterministic. */
+int dvd_xwgradk_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
+                  int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream);
 int dvd_bnrelu_fwd_t(const void* x, const void* residual, const float* gamma, const float* beta, const float* mean,
                      const float* var, float eps, void* y, int f16, int N, int C, int HW, int relu, dvd_stream_t stream);
 int dvd_bnrelu_bwd_t(const void* gy, const void* y, const void* x, const float* gamma, const float* mean, const float* var,
@@ -549,6 +554,19 @@ int dvd_head1x1_fwd(const void* x, int f16, const float* w, const float* bias, f
 size_t dvd_head1x1_bwd_workspace_bytes(int C);
 int dvd_head1x1_bwd(const void* x, int f16, const float* w, const float* gy, const float* gscale_state, void* gx, float* gw,
                     float* gb, void* workspace, size_t workspace_bytes, int N, int C, int HW, int relu_in, dvd_stream_t stream);
+/* ABI 8: the hourglass's depth head `pred_layer = Conv2d(C, 1, 3, padding 1)` (reference third_party/hourglass.py:175-182), the
+ * fp16 / fp32 boundary of that net: y fp32 [N,1,H,W] = bias + conv(x), x _Float16 [N,C,H,W] (C <= 64); max |y| folded into
+ * fwd_amax (optional, the forward monitor [6] of the loss-scale state).  Backward: gx = S * conv_transpose(gy, w) as _Float16
+ * (max |S gx| folded into gscale_state[3]), gw [C][3][3] and gb [1] fp32 from the unscaled fp32 gy; gscale_state null: S = 1.
+ * Deterministic (fixed-order partial sums). */
+int dvd_head3x3_fwd(const void* x, const float* w, const float* bias, float* y, float* fwd_amax, int N, int C, int H, int W,
+                    dvd_stream_t stream);
+size_t dvd_head3x3_bwd_workspace_bytes(int N, int C, int H, int W);
+int dvd_head3x3_bwd(const void* x, const float* w, const float* gy, const float* gscale_state, void* gx, float* gw, float* gb,
+                    void* workspace, size_t workspace_bytes, int N, int C, int H, int W, dvd_stream_t stream);
+/* ABI 8: y = a + b of two _Float16 tensors (n elements), max |y| folded into fwd_amax (optional; NaN counted as +Inf): the sums of
+ * the hourglass's two parallel paths (third_party/hourglass.py:60-158) under the overflow guard. */
+int dvd_add_f16(const void* a, const void* b, void* y, long long n, float* fwd_amax, dvd_stream_t stream);
 /* Loss scale of the fp16 gradients, kept on the device (state: 16 floats since ABI 7; [0] = S, [1] = 1 / S, [2] = target exponent,
  * [3] = observed max |S g| this step, [4] = skip flag, [5] = skipped steps, [6] = forward monitor: max |activation| the fp16-output
  * convolution epilogues and the depth head folded in this step -- every maximum counts a NaN as +Inf).  begin: S = 2^(target - ceil(log2(max|g| * max|w|)))
