@@ -47,11 +47,12 @@ __global__ __launch_bounds__(256) void scale_add_kernel(float* __restrict__ out,
 // The tail of the MiDaS depth head, `10000 / clamp(relu(v), min=1e-2)` (third_party/MiDaS.py:192-195,240-242), in one pass each
 // way instead of ATen's clamp_min / clamp / reciprocal / mul kernels and their four backward kernels.  Forward: torch evaluates
 // `10000 / t` as reciprocal(t) * 10000 -- two roundings, an IEEE reciprocal and a multiply -- and so does this (bit-identical).
-// Backward: autograd's -(g * 10000) * r * r with r = 1 / v where the clamp passes the value on (v >= 1e-2; the ReLU in front of
-// it passes every such v), 0 elsewhere.
+// Backward: autograd's -(g * 10000) * (r * r) with r = 1 / v (reciprocal's backward squares its result first: bit-identical) where
+// the clamp passes the value on (v >= 1e-2; the ReLU in front of it passes every such v), 0 elsewhere.  A NaN input stays NaN, as
+// through torch's relu and clamp (fmaxf alone would turn it into depth 1e6).
 __device__ __forceinline__ float depth_tail_value(float x) {
   const float r = 1.0f / fmaxf(fmaxf(x, 0.0f), 1e-2f);      // IEEE division (this file is not built with fast-math)
-  return r * 10000.0f;
+  return x != x ? x : r * 10000.0f;
 }
 __global__ __launch_bounds__(256) void depth_tail_fwd_kernel(const float* __restrict__ v, float* __restrict__ out, long long n) {
   const long long n4 = n >> 2;
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void depth_tail_fwd_kernel(const float* __rest
 }
 __device__ __forceinline__ float depth_tail_grad(float x, float g) {
   const float r = 1.0f / x;
-  return x >= 1e-2f ? -(g * 10000.0f) * r * r : 0.0f;
+  return x >= 1e-2f ? -(g * 10000.0f) * (r * r) : 0.0f;
 }
 __global__ __launch_bounds__(256) void depth_tail_bwd_kernel(const float* __restrict__ v, const float* __restrict__ g,
                                                              float* __restrict__ gv, long long n) {

@@ -39,9 +39,21 @@ class FlatNet(object):
         # not -- the host never learns of a skip inside the step -- so the EFFECTIVE step, the one torch.optim.Adam /
         # GradScaler mean and a checkpoint must carry, is step_count - skipped.
         self.skip_count = None
+        self._count_only = None
 
     def _skipped(self):
         return int(self.skip_count.item()) if self.skip_count is not None else 0
+
+    def _skip_pair(self, skip_ptr):
+        """What the guarded kernel reads: the caller's (flag, count) pair, or -- for a step that is never skipped itself (warm
+        steps pass None) on a net that counts skips -- flag 0 and the current count, so that bias correction still takes the
+        effective step.  One device copy, no host read."""
+        if skip_ptr is not None or self.skip_count is None:
+            return skip_ptr
+        if self._count_only is None or self._count_only.device != self.skip_count.device:
+            self._count_only = torch.zeros(2, device=self.skip_count.device, dtype=torch.float32)
+        self._count_only[1:2].copy_(self.skip_count)
+        return self._count_only
 
     def view(self, buf, p_index):
         p, o = self.params[p_index], self.offsets[p_index]
@@ -94,6 +106,7 @@ class FlatNet(object):
             return self.adam_step(skip_ptr=skip_ptr)
         pending = parallel.all_reduce_sum_buckets_async_(self.grad, n_buckets)
         self.step_count += 1
+        skip_ptr = self._skip_pair(skip_ptr)
         for lo, hi, work in pending:
             if work is not None:
                 work.wait()
@@ -104,7 +117,8 @@ class FlatNet(object):
         """param -= Adam(scale * (*scale_ptr) * grad + extra_grad); nothing happens if *skip_ptr != 0."""
         self.step_count += 1
         ops.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas[0],
-                      self.betas[1], self.eps, scale=scale, scale_ptr=scale_ptr, grad2=extra_grad, skip_ptr=skip_ptr)
+                      self.betas[1], self.eps, scale=scale, scale_ptr=scale_ptr, grad2=extra_grad,
+                      skip_ptr=self._skip_pair(skip_ptr))
 
     # Checkpoints carry `optimizer.state_dict()` of a torch.optim.Adam (netinterface.py:528-536, written by
     # ModelSaveLogger with save_optimizer=True); emit and accept exactly that layout -- per-parameter

@@ -58,3 +58,27 @@ def test_state_dict_round_trip():
     for i in range(len(a.params)):               # (the alignment padding between segments carries no state)
         assert torch.equal(a.view(a.exp_avg, i), b.view(b.exp_avg, i))
         assert torch.equal(a.view(a.exp_avg_sq, i), b.view(b.exp_avg_sq, i))
+
+
+def test_steps_without_a_skip_pointer_hand_the_skip_count_to_the_kernel(monkeypatch):
+    """Warm steps call adam_step() without a skip pointer.  A net that counts skipped steps (skip_count) must still give the
+    guarded kernel its count, with the flag 0, so that bias correction takes step_count - skipped like state_dict() (ADVICE
+    round 6, item 3).  The count is copied at every step, and a caller's own pair is passed on unchanged."""
+    from dvd_hip import ops
+    seen = []
+    monkeypatch.setattr(ops, 'adam_step', lambda *a, **k: seen.append((a[4], None if k['skip_ptr'] is None
+                                                                       else k['skip_ptr'].tolist())))
+    fn = flat.FlatNet(_net(), 1e-3, (0.5, 0.9))
+    fn.adam_step()
+    assert seen[-1] == (1, None)
+    st = torch.zeros(16)
+    st[5] = 2.0
+    fn.skip_count = st[5:6]
+    fn.adam_step()
+    assert seen[-1] == (2, [0.0, 2.0])
+    st[5] = 3.0
+    fn.all_reduce_and_adam_step(4)                # single process: the same single launch
+    assert seen[-1] == (3, [0.0, 3.0])
+    fn.adam_step(skip_ptr=torch.tensor([1.0, 3.0]))
+    assert seen[-1] == (4, [1.0, 3.0])
+    assert st.tolist() == [0.0] * 5 + [3.0] + [0.0] * 10
