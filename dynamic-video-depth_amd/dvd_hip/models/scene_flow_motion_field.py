@@ -29,6 +29,7 @@ package's HIP kernels (csrc/); the matrix kernels evaluate fp32 products from tw
 `--act_fp16` (BASELINE configs[4]) stores the depth net's activations and their gradients as fp16 (csrc/a16.hip: the loss scale
 lives on the device); `--use_cnn` swaps the MLP for the reference's U-Net scene-flow network (networks/FCNUnet.py) under autograd.
 """
+import contextlib
 import os
 import sys
 import warnings
@@ -91,6 +92,243 @@ def keep_slot_fits(est, free, total, reserve, spare, kept, budget, head_room=0.0
     kept (0 if this slot completes the step), `kept` = bytes already held by slots, `budget` = --depth_keep_gb.
     `head_room` (head_room_fraction) of the device stays free."""
     return kept + est <= budget and free - est >= reserve + head_room * total + spare
+
+
+class _SfStep:
+    """Phase 2 of `Model._train_on_batch` (geometry + scene-flow network + losses, forward and backward): what its pieces share
+    for ONE step, and the three schedules the MLP's activation stashes allow.  Per-chunk data (stashes, backward scratch) stay
+    locals of the schedule methods: they bound the step's peak HBM; the object itself does not outlive the step."""
+    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg):
+        opt = self.opt = model.opt
+        self.inp, self.mlp, self.flat_sf, self.sf_grad_main = inp, model._mlp, model._flat_sf, model._sf_grad_main
+        self.depth_1, self.depth_2 = depth_1, depth_2
+        self.steps, self.time_step, self.warm, self.do_reg = steps, time_step, warm, do_reg
+        B, _, H, W = inp.img_1.shape
+        self.B, self.H, self.W, self.HW = B, H, W, H * W
+        self.mul = steps if opt.weight_steps else 1
+        self.disp_mode = 1 if opt.use_disp else (2 if opt.use_disp_ratio else 0)
+        self.sums = torch.zeros(8, device=model.device)            # [S0..S3, sum|sf1-sf0|, 0, 0, 0]
+        self.g_d1_main, self.g_d2_main = torch.empty_like(depth_1), torch.empty_like(depth_2)
+        self.g_d1_reg = self.sf_all = self.g_sf_all = None    # allocated by run_late only / by begin_mlp or the U-Net path
+        self.inv_div = 1.0 / opt.sf_mag_div
+        self.mask_2 = inp.mask_2.reshape(B, H, W)
+        # --use_motion_seg (:253-254): the integrated scene flow is multiplied by motion_seg_1 before the
+        # warp; the un-masked field still drives the Euler chain and the regulariser
+        self.mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
+        self.cfg_all = self.warp_cfg(B)
+
+    def warp_cfg(self, n_pairs):
+        opt = self.opt
+        return ops.warp_cfg(n_pairs, self.H, self.W, midas_mask=opt.midas, crit_l2=self.warm, disp_mode=self.disp_mode,
+                            loss_on_sf=not opt.use_disp, flow_mul=opt.flow_mul * self.mul, disp_mul=opt.disp_mul * self.mul)
+
+    def set_global_batch(self, n_global):
+        """n_global: pairs of ALL ranks (parallel.agree_on_step_plan); the regulariser is a mean over them."""
+        self.n_global = n_global
+        self.reg_coef = self.opt.acc_mul / (3.0 * n_global * self.HW + 1e-6)
+
+    def begin_mlp(self, Bc):
+        """The MLP path's batch-wide tensors; Bc pairs go through the MLP kernels at once (Model._pairs_per_chunk)."""
+        k, B, inp = self.flat_sf, self.B, self.inp
+        self.gW_main = [k.view(self.sf_grad_main, 2 * i) for i in range(6)]
+        self.gb_main = [k.view(self.sf_grad_main, 2 * i + 1) for i in range(6)]
+        self.gW_reg = [k.view(k.grad, 2 * i) for i in range(6)]
+        self.gb_reg = [k.view(k.grad, 2 * i + 1) for i in range(6)]
+        self.Bc, self.chunks = Bc, [(b0, min(B, b0 + Bc)) for b0 in range(0, B, Bc)]
+        self.P1_all = ops.unproject(self.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True)
+        self.sf_all = torch.zeros(B, 3, self.H, self.W, device=self.depth_1.device)
+        self.g_sf_all = torch.empty_like(self.sf_all)
+
+    def mlp_forward_chunk(self, b0, b1, keep_first=None, acc=None, with_stash=True):
+        """Euler integration of the scene flow over `steps` frames (:360-367).  keep_first: also
+        return sf_0 and q = P1 + sf_0 of the first evaluation (the regulariser's sf_0, see below).
+        acc: the tensor the integrated flow is accumulated into (default: this chunk of sf_all); with_stash=False: no
+        activation stashes (the first pass of the recompute schedule)."""
+        mlp, steps = self.mlp, self.steps
+        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
+        n_pix = (b1 - b0) * self.HW
+        stashes, p_cur, first = [], self.P1_all[b0:b1], None
+        acc = self.sf_all[b0:b1] if acc is None else acc
+        for i in range(steps):
+            st = mlp.new_stash(n_pix) if with_stash else None
+            want_next = i + 1 < steps or (keep_first and i == 0)
+            p_next = torch.empty_like(p_cur) if want_next else None
+            # the regulariser's two evaluations ARE Euler evaluations 0 and 1 (see merged_backward_chunk): keep their
+            # outputs (evaluation 0's only when it is not the accumulated flow itself)
+            sf_i = torch.empty_like(p_cur) if (keep_first and i < 2 and steps > 1) else None
+            mlp.forward(p_cur, ts, t_offset=i * self.time_step, out_scale=self.inv_div, sf_out=sf_i, p_next=p_next,
+                        acc=acc, stash=st)
+            if keep_first and i == 0:
+                first = [sf_i, p_next, None]    # sf_i is None when steps == 1: sf_0 is the accumulated flow itself
+            if keep_first and i == 1:
+                first[2] = sf_i                 # sf_1 = MLP(P1 + sf_0, t_1 + dt)
+            stashes.append(st)
+            p_cur = p_next
+        return (stashes, first) if keep_first is not None else stashes
+
+    def warp(self, b0, b1):
+        inp, mseg = self.inp, self.mseg
+        sf_used = self.sf_all[b0:b1]
+        if mseg is not None:
+            sf_used = ops.mul_mask(torch.empty_like(sf_used), sf_used, mseg[b0:b1])
+        cfg = self.cfg_all if (b0, b1) == (0, self.B) else self.warp_cfg(b1 - b0)
+        csum = torch.empty(4, device=self.sums.device)
+        ops.warp_loss_fused(cfg, self.depth_1[b0:b1], self.depth_2[b0:b1], inp.flow_1_2[b0:b1], self.mask_2[b0:b1],
+                            sf_used, {kk: getattr(inp, kk)[b0:b1] for kk in CAM_KEYS},
+                            out=(csum, self.g_d1_main[b0:b1], self.g_d2_main[b0:b1], self.g_sf_all[b0:b1]))
+        if mseg is not None:
+            ops.mul_mask(self.g_sf_all[b0:b1], self.g_sf_all[b0:b1], mseg[b0:b1])
+        self.sums[:4] += csum
+
+    def mlp_backward_chunk(self, b0, b1, stashes, gst):
+        """Backward through the Euler chain: g_p_i = g_p_{i+1} + J_i^T (g_acc + g_p_{i+1})."""
+        mlp, inv_div, gW_main, gb_main = self.mlp, self.inv_div, self.gW_main, self.gb_main
+        nb, n_pix = b1 - b0, (b1 - b0) * self.HW
+        g_p = None
+        for i in reversed(range(self.steps)):
+            g_new = torch.empty_like(self.P1_all[b0:b1])
+            mlp.backward_dx(stashes[i], inv_div, self.g_sf_all[b0:b1], g_new, gst, gW_main[5], gb_main[5], (nb, self.H, self.W),
+                            g_out2=g_p, g_p_add=g_p)
+            mlp.backward_dw(stashes[i], gst, n_pix, gW_main[:5], gb_main[:5])
+            g_p = g_new
+        ops.unproject_backward(g_p, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_main[b0:b1], accumulate=True)
+
+    def reg_chunk(self, b0, b1, gst):
+        """Acceleration regulariser (:326-344), P1 un-detached."""
+        mlp, inv_div, gW_reg, gb_reg, sums = self.mlp, self.inv_div, self.gW_reg, self.gb_reg, self.sums
+        n_pix, shape = (b1 - b0) * self.HW, (b1 - b0, self.H, self.W)
+        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
+        P1 = self.P1_all[b0:b1]
+        sa, sb = mlp.new_stash(n_pix), mlp.new_stash(n_pix)
+        sf0, sf1, q = torch.empty_like(P1), torch.empty_like(P1), torch.empty_like(P1)
+        mlp.forward(P1, ts, 0.0, inv_div, sf_out=sf0, p_next=q, stash=sa)
+        mlp.forward(q, ts, self.time_step, inv_div, sf_out=sf1, stash=sb)
+        g1 = torch.empty_like(P1)
+        ops.acc_reg(sf0, sf1, self.reg_coef, g1, sums[4:5], accumulate=True)
+        g_q = torch.empty_like(P1)
+        mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], shape)
+        mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
+        g_P = torch.empty_like(P1)
+        mlp.backward_dx(sa, inv_div, g1, g_P, gst, gW_reg[5], gb_reg[5], shape, gscale=-1.0, g_out2=g_q, g_p_add=g_q)
+        mlp.backward_dw(sa, gst, n_pix, gW_reg[:5], gb_reg[:5])
+        ops.unproject_backward(g_P, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_reg[b0:b1])
+
+    def merged_backward_chunk(self, b0, b1, stashes, first, gst, inv):
+        """Main loss and acceleration regulariser through ONE backward of the first evaluation.
+
+        The regulariser's sf_0 = MLP(P1, t_1) (:329-333) is the first Euler evaluation of the main
+        path (:360-367: same points, same time, same weights), so its forward, stash, dX and dW
+        passes are shared: with G = inv * g_sf (main, late normaliser already known) the first
+        evaluation receives  G + g_p1 - g1 + g_q  where g1 = dR/dsf_1, g_q = J_b^T g1, and
+        g_P1 = g_p1 + g_q + J_0^T(...).  One MLP evaluation per step less than the reference.
+        From gap 2 on the regulariser's sf_1 = MLP(P1 + sf_0, t_1 + dt) (:335-338) is Euler evaluation 1 as well
+        (:360-367), so that one is shared too (round 4): evaluation 1 receives G + g_p2 + g1, and a gap-k step costs k
+        evaluations instead of the reference's k + 2."""
+        mlp, steps, do_reg, inv_div, sums, reg_coef = self.mlp, self.steps, self.do_reg, self.inv_div, self.sums, self.reg_coef
+        gW_reg, gb_reg = self.gW_reg, self.gb_reg
+        n_pix, shape = (b1 - b0) * self.HW, (b1 - b0, self.H, self.W)
+        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
+        P1, g_sf = self.P1_all[b0:b1], self.g_sf_all[b0:b1]
+        g_q = g1 = None
+        shared1 = do_reg and steps > 1      # the regulariser's second evaluation is Euler evaluation 1 as well (:335-338 = :360-367)
+        if do_reg:
+            sf0 = first[0] if first[0] is not None else self.sf_all[b0:b1]
+            g1 = torch.empty_like(P1)
+            if shared1:
+                ops.acc_reg(sf0, first[2], reg_coef, g1, sums[4:5], accumulate=True)
+            else:
+                sb, sf1 = mlp.new_stash(n_pix), torch.empty_like(P1)
+                mlp.forward(first[1], ts, self.time_step, inv_div, sf_out=sf1, stash=sb)
+                ops.acc_reg(sf0, sf1, reg_coef, g1, sums[4:5], accumulate=True)
+                g_q = torch.empty_like(P1)
+                mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], shape)
+                mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
+                del sb, sf1
+        g_p = None
+        for i in reversed(range(1, steps)):
+            g_new = torch.empty_like(P1)
+            g_o2 = g_p
+            if shared1 and i == 1:          # evaluation 1's output also feeds the regulariser: + dR/dsf_1 (not normalised)
+                g_o2 = g1 if g_p is None else ops.scale_add(torch.empty_like(P1), g1, b=g_p)
+            mlp.backward_dx(stashes[i], inv_div, g_sf, g_new, gst, gW_reg[5], gb_reg[5], shape, scale_ptr=inv,
+                            g_out2=g_o2, g_p_add=g_p)
+            mlp.backward_dw(stashes[i], gst, n_pix, gW_reg[:5], gb_reg[:5])
+            g_p = g_new
+        extra, add = g_p, g_p                    # gradient reaching sf_0 besides G, and reaching P1 directly
+        if shared1:                              # g_p already holds everything that reaches q = P1 + sf_0
+            extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_p)          # g_p - g1
+        elif do_reg:
+            extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_q)          # -g1 + g_q
+            add = g_q
+        g_P = torch.empty_like(P1)
+        mlp.backward_dx(stashes[0], inv_div, g_sf, g_P, gst, gW_reg[5], gb_reg[5], shape, scale_ptr=inv,
+                        g_out2=extra, g_p_add=add)
+        mlp.backward_dw(stashes[0], gst, n_pix, gW_reg[:5], gb_reg[:5])
+        ops.unproject_backward(g_P, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_main[b0:b1], accumulate=True)
+
+    def normaliser(self, sums):
+        """All-reduce the loss sums -> the loss scalars and inv = 1/(S0+1e-8) as a device scalar."""
+        parallel.all_reduce_sum_(sums)
+        scalars = ops.loss_finalize(self.cfg_all, self.sums)
+        return scalars, scalars[0:1]
+
+    def warp_whole_batch(self):
+        """ONE warp+loss launch over all pairs.  The batch-global normaliser is then known before the scene-flow network's
+        backward: all-reduce the four loss sums now and hand inv to the backward kernels as a device scalar."""
+        self.warp(0, self.B)
+        scalars, inv = self.normaliser(self.sums[:4])
+        ops.scale_add(self.g_d1_main, self.g_d1_main, scale_ptr=inv)
+        return scalars, inv
+
+    def run_whole_batch(self):
+        """Schedule 1 of 3 (each returns (scalars, inv)): the forward stashes of the whole batch stay alive until the backward."""
+        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
+        kept = [self.mlp_forward_chunk(b0, b1, keep_first=bool(self.do_reg)) for b0, b1 in self.chunks]
+        scalars, inv = self.warp_whole_batch()
+        for (b0, b1), (st, first) in zip(self.chunks, kept):
+            self.merged_backward_chunk(b0, b1, st, first, gst, inv)
+            del st[:]
+        del kept
+        parallel.all_reduce_sum_(self.sums[4:])
+        return scalars, inv
+
+    def run_recompute(self):
+        """Round 6: when the forward stashes of the whole batch do NOT fit (BASELINE configs[4]: 64 pairs at 768 x 1344 = 211 GB
+        of stashes), the late-normaliser schedule costs 3 forward + 3 dX + 3 dW passes per pair and Euler step -- the
+        regulariser cannot share the main path's backward while the normaliser is unknown.  The RECOMPUTE schedule runs the
+        Euler chain once WITHOUT stashes for every pair (the cheapest form of the forward kernel), one warp+loss launch over
+        the whole batch, and then per chunk the stashed forward again + the merged backward: 3 forward + 2 dX + 2 dW at
+        gap 1 (2k + k + k instead of (k + 2) x 3 at gap k), same arithmetic as the whole-batch schedule (the recomputed
+        evaluations are bit-identical: the forward kernel is deterministic).  --mlp_recompute 0 restores the late schedule."""
+        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
+        with ops.counting_recomputed():          # the stashed evaluations below are the ones the backward needs
+            for b0, b1 in self.chunks:
+                self.mlp_forward_chunk(b0, b1, with_stash=False)
+        scalars, inv = self.warp_whole_batch()
+        for b0, b1 in self.chunks:
+            # the same evaluations again, stashed; their flow goes to a scratch accumulator (sf_all already holds it)
+            st, first = self.mlp_forward_chunk(b0, b1, keep_first=bool(self.do_reg), acc=torch.zeros_like(self.sf_all[b0:b1]))
+            self.merged_backward_chunk(b0, b1, st, first, gst, inv)
+            del st[:], first
+        parallel.all_reduce_sum_(self.sums[4:])
+        return scalars, inv
+
+    def run_late(self):
+        """Per-chunk warp+loss launches (--mlp_recompute 0, or another rank needs it): the batch-global normaliser only exists
+        after the last chunk; main-path gradients stay un-normalised in buffers of their own, the regulariser runs apart."""
+        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
+        self.g_d1_reg = torch.zeros_like(self.depth_1) if self.do_reg else None
+        for b0, b1 in self.chunks:
+            st = self.mlp_forward_chunk(b0, b1)
+            self.warp(b0, b1)
+            self.mlp_backward_chunk(b0, b1, st, gst)
+            del st
+            if self.do_reg:
+                self.reg_chunk(b0, b1, gst)
+        del gst
+        scalars, inv = self.normaliser(self.sums)
+        ops.scale_add(self.flat_sf.grad, self.sf_grad_main, scale_ptr=inv, b=self.flat_sf.grad)   # MLP gradient = inv * main + reg
+        return scalars, inv
 
 
 class Model(NetInterface):
@@ -611,8 +849,7 @@ class Model(NetInterface):
         inp = self._input
         B, _, H, W = inp.img_1.shape
         HW, dev = H * W, self.device
-        fid1 = inp.frame_id_1 if not opt.midas else None
-        fid2 = inp.frame_id_2 if not opt.midas else None
+        fid1, fid2 = self._frame_ids(inp)
 
         # ---- phase 1: depth maps; the autograd state of as many chunks as fit stays alive for phase 3 (kept slots),
         #      the rest is a no-graph forward that phase 3 recomputes
@@ -623,7 +860,6 @@ class Model(NetInterface):
             self._auto_chunk = self._pick_depth_chunk(B, HW, self._phase2_bytes(B, HW, steps, do_reg), dev)
         n_slots = -(-B // self._chunk())
         if not keeping:
-            import contextlib
             # (non-warm steps without kept slots: phase 3 recomputes every chunk's forward; a warm-up step has no depth-net backward)
             with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
                 depth_1 = self._depths_nograd(inp.img_1, fid1)
@@ -634,255 +870,69 @@ class Model(NetInterface):
             depth_2 = self._depths_keep(inp.img_2, fid2, n_slots, mlp_need, 2 * n_slots)
             self._trim_keep_slots(dev, mlp_need)
 
-        # ---- phase 2: geometry + scene-flow MLP + losses, forward and backward, in HIP
-        mul = steps if opt.weight_steps else 1
-        disp_mode = 1 if opt.use_disp else (2 if opt.use_disp_ratio else 0)
-        sums = torch.zeros(8, device=dev)            # [S0..S3, sum|sf1-sf0|, 0, 0, 0]
-        g_d1_main = torch.empty_like(depth_1)
-        g_d2_main = torch.empty_like(depth_2)
-        g_d1_reg = None                              # allocated only by the per-chunk fallback path
-        mlp, k = self._mlp, self._flat_sf
+        # ---- phase 2: geometry + scene-flow network + losses, forward and backward (_SfStep)
+        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg)
         if opt.use_cnn:
-            return self._finish_step_cnn(epoch, batch_ind, batch, inp, depth_1, depth_2, steps, time_step, warm, do_reg, n_slots,
-                                         fid1, fid2, mul, disp_mode, sums, g_d1_main, g_d2_main)
-        mlp.pack([p for p in self.net_sceneflow.parameter_list()[0::2]], self.net_sceneflow.parameter_list()[1::2])
-        gW_main = [k.view(self._sf_grad_main, 2 * i) for i in range(6)]
-        gb_main = [k.view(self._sf_grad_main, 2 * i + 1) for i in range(6)]
-        gW_reg = [k.view(k.grad, 2 * i) for i in range(6)]
-        gb_reg = [k.view(k.grad, 2 * i + 1) for i in range(6)]
-        inv_div = 1.0 / opt.sf_mag_div
-        Bc = self._pairs_per_chunk(B, HW, steps, do_reg)
-        mask_2 = inp.mask_2.reshape(B, H, W)
-        # --use_motion_seg (:253-254): the integrated scene flow is multiplied by motion_seg_1 before the
-        # warp; the un-masked field still drives the Euler chain and the regulariser
-        mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
-        cfg_all = ops.warp_cfg(B, H, W, midas_mask=opt.midas, crit_l2=warm, disp_mode=disp_mode,
-                               loss_on_sf=not opt.use_disp, flow_mul=opt.flow_mul * mul, disp_mul=opt.disp_mul * mul)
+            _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
+            step.set_global_batch(n_global)
+            scalars, inv = self._unet_forward_backward(step)
+            return self._finish_step(epoch, batch_ind, batch, step, scalars, inv, True, capturing, n_slots)
+        self._mlp.pack([p for p in self.net_sceneflow.parameter_list()[0::2]], self.net_sceneflow.parameter_list()[1::2])
         # The MLP activation stashes bound how many pairs go through the MLP kernels at once
         # (Bc).  If the forward stashes of the WHOLE batch fit the budget next to one chunk of
         # backward scratch, the warp+loss kernel runs once over all pairs (one launch of
         # B*H*W pixels fills the chip far better than B/Bc smaller ones); otherwise every
-        # chunk gets its own warp+loss launch.
+        # chunk gets its own warp+loss launch -- or, by default, the recompute schedule (_SfStep.run_recompute).
+        Bc = self._pairs_per_chunk(B, HW, steps, do_reg)
         whole = Bc < B and self._whole_batch_fits(B, Bc, HW, steps, do_reg)
+        recompute = Bc < B and not whole and bool(int(getattr(opt, 'mlp_recompute', 1)))
         # ranks may hold different batch sizes / frame gaps: agree on the schedule (early or late normaliser)
         # and on the size of the global batch before the first data-dependent collective
-        # (also agreed across ranks: does ANY rank still have to capture a depth-net graph in phase 3 -- a chunk that is not
-        #  kept and has no recompute graph yet?  Then every rank keeps the MLP-gradient all-reduce out of flight until after
-        #  phase 3, so the order of collectives is the same everywhere)
-        # over the REAL chunk list of both image sets (a ragged last chunk has its own slot / graph keys)
-        may_capture = False
-        if not warm and getattr(opt, 'depth_graphs', 1):
-            cw = self._chunk()
-            for s0, img in ((0, inp.img_1), (n_slots, inp.img_2)):
-                for ci, b0 in enumerate(range(0, B, cw)):
-                    chunk = img[b0:b0 + cw]
-                    kept = self._depth_graphs.get(('keep', s0 + ci, tuple(chunk.shape), bool(opt.midas)))
-                    if kept is None and self._graph_key('fb', chunk) not in self._depth_graphs:
-                        may_capture = True
-        # Round 6: when the forward stashes of the whole batch do NOT fit (BASELINE configs[4]: 64 pairs at 768 x 1344 = 211 GB of
-        # stashes), the late-normaliser schedule below costs 3 forward + 3 dX + 3 dW passes per pair and Euler step -- the
-        # regulariser cannot share the main path's backward while the normaliser is unknown.  The RECOMPUTE schedule runs the
-        # Euler chain once WITHOUT stashes for every pair (the cheapest form of the forward kernel), one warp+loss launch over
-        # the whole batch, and then per chunk the stashed forward again + the merged backward: 3 forward + 2 dX + 2 dW at
-        # gap 1 (2k + k + k instead of (k + 2) x 3 at gap k), same arithmetic as the whole-batch schedule (the recomputed
-        # evaluations are bit-identical: the forward kernel is deterministic).  --mlp_recompute 0 restores the late schedule.
-        recompute = Bc < B and not whole and bool(int(getattr(opt, 'mlp_recompute', 1)))
-        late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B, may_capture)
-        early_norm = not late
-        reg_coef = opt.acc_mul / (3.0 * n_global * HW + 1e-6)
-        chunks = [(b0, min(B, b0 + Bc)) for b0 in range(0, B, Bc)]
-        P1_all = ops.unproject(depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True)
-        sf_all = torch.zeros(B, 3, H, W, device=dev)
-        g_sf_all = torch.empty_like(sf_all)
-
-        def cams_of(b0, b1):
-            return {kk: getattr(inp, kk)[b0:b1] for kk in CAM_KEYS}
-
-        def mlp_forward_chunk(b0, b1, keep_first=None, acc=None, with_stash=True):
-            """Euler integration of the scene flow over `steps` frames (:360-367).  keep_first: also
-            return sf_0 and q = P1 + sf_0 of the first evaluation (the regulariser's sf_0, see below).
-            acc: the tensor the integrated flow is accumulated into (default: this chunk of sf_all); with_stash=False: no
-            activation stashes (the first pass of the recompute schedule)."""
-            ts = inp.time_stamp_1[b0:b1] if opt.time_dependent else None
-            n_pix = (b1 - b0) * HW
-            stashes, p_cur, first = [], P1_all[b0:b1], None
-            acc = sf_all[b0:b1] if acc is None else acc
-            for i in range(steps):
-                st = mlp.new_stash(n_pix) if with_stash else None
-                want_next = i + 1 < steps or (keep_first and i == 0)
-                p_next = torch.empty_like(p_cur) if want_next else None
-                # the regulariser's two evaluations ARE Euler evaluations 0 and 1 (see merged_backward_chunk): keep their
-                # outputs (evaluation 0's only when it is not the accumulated flow itself)
-                sf_i = torch.empty_like(p_cur) if (keep_first and i < 2 and steps > 1) else None
-                mlp.forward(p_cur, ts, t_offset=i * time_step, out_scale=inv_div, sf_out=sf_i, p_next=p_next,
-                            acc=acc, stash=st)
-                if keep_first and i == 0:
-                    first = [sf_i, p_next, None]    # sf_i is None when steps == 1: sf_0 is the accumulated flow itself
-                if keep_first and i == 1:
-                    first[2] = sf_i                 # sf_1 = MLP(P1 + sf_0, t_1 + dt)
-                stashes.append(st)
-                p_cur = p_next
-            return (stashes, first) if keep_first is not None else stashes
-
-        def warp(b0, b1):
-            sf_used = sf_all[b0:b1]
-            if mseg is not None:
-                sf_used = ops.mul_mask(torch.empty_like(sf_used), sf_used, mseg[b0:b1])
-            cfg = cfg_all if (b0, b1) == (0, B) else ops.warp_cfg(
-                b1 - b0, H, W, midas_mask=opt.midas, crit_l2=warm, disp_mode=disp_mode, loss_on_sf=not opt.use_disp,
-                flow_mul=opt.flow_mul * mul, disp_mul=opt.disp_mul * mul)
-            csum = torch.empty(4, device=dev)
-            ops.warp_loss_fused(cfg, depth_1[b0:b1], depth_2[b0:b1], inp.flow_1_2[b0:b1], mask_2[b0:b1],
-                                sf_used, cams_of(b0, b1),
-                                out=(csum, g_d1_main[b0:b1], g_d2_main[b0:b1], g_sf_all[b0:b1]))
-            if mseg is not None:
-                ops.mul_mask(g_sf_all[b0:b1], g_sf_all[b0:b1], mseg[b0:b1])
-            sums[:4] += csum
-
-        def mlp_backward_chunk(b0, b1, stashes, gst):
-            """Backward through the Euler chain: g_p_i = g_p_{i+1} + J_i^T (g_acc + g_p_{i+1})."""
-            nb, n_pix = b1 - b0, (b1 - b0) * HW
-            cams = cams_of(b0, b1)
-            g_p = None
-            for i in reversed(range(steps)):
-                g_new = torch.empty_like(P1_all[b0:b1])
-                mlp.backward_dx(stashes[i], inv_div, g_sf_all[b0:b1], g_new, gst, gW_main[5], gb_main[5], (nb, H, W),
-                                g_out2=g_p, g_p_add=g_p)
-                mlp.backward_dw(stashes[i], gst, n_pix, gW_main[:5], gb_main[:5])
-                g_p = g_new
-            ops.unproject_backward(g_p, True, cams['R_1'], cams['K_inv'], out=g_d1_main[b0:b1], accumulate=True)
-
-        def reg_chunk(b0, b1, gst):
-            """Acceleration regulariser (:326-344), P1 un-detached."""
-            nb, n_pix = b1 - b0, (b1 - b0) * HW
-            cams = cams_of(b0, b1)
-            ts = inp.time_stamp_1[b0:b1] if opt.time_dependent else None
-            P1 = P1_all[b0:b1]
-            sa, sb = mlp.new_stash(n_pix), mlp.new_stash(n_pix)
-            sf0, sf1, q = torch.empty_like(P1), torch.empty_like(P1), torch.empty_like(P1)
-            mlp.forward(P1, ts, 0.0, inv_div, sf_out=sf0, p_next=q, stash=sa)
-            mlp.forward(q, ts, time_step, inv_div, sf_out=sf1, stash=sb)
-            g1 = torch.empty_like(P1)
-            ops.acc_reg(sf0, sf1, reg_coef, g1, sums[4:5], accumulate=True)
-            g_q = torch.empty_like(P1)
-            mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], (nb, H, W))
-            mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
-            g_P = torch.empty_like(P1)
-            mlp.backward_dx(sa, inv_div, g1, g_P, gst, gW_reg[5], gb_reg[5], (nb, H, W), gscale=-1.0, g_out2=g_q,
-                            g_p_add=g_q)
-            mlp.backward_dw(sa, gst, n_pix, gW_reg[:5], gb_reg[:5])
-            ops.unproject_backward(g_P, True, cams['R_1'], cams['K_inv'], out=g_d1_reg[b0:b1])
-
-        def merged_backward_chunk(b0, b1, stashes, first, gst, inv):
-            """Main loss and acceleration regulariser through ONE backward of the first evaluation.
-
-            The regulariser's sf_0 = MLP(P1, t_1) (:329-333) is the first Euler evaluation of the main
-            path (:360-367: same points, same time, same weights), so its forward, stash, dX and dW
-            passes are shared: with G = inv * g_sf (main, late normaliser already known) the first
-            evaluation receives  G + g_p1 - g1 + g_q  where g1 = dR/dsf_1, g_q = J_b^T g1, and
-            g_P1 = g_p1 + g_q + J_0^T(...).  One MLP evaluation per step less than the reference.
-            From gap 2 on the regulariser's sf_1 = MLP(P1 + sf_0, t_1 + dt) (:335-338) is Euler evaluation 1 as well
-            (:360-367), so that one is shared too (round 4): evaluation 1 receives G + g_p2 + g1, and a gap-k step costs k
-            evaluations instead of the reference's k + 2."""
-            nb, n_pix = b1 - b0, (b1 - b0) * HW
-            cams = cams_of(b0, b1)
-            ts = inp.time_stamp_1[b0:b1] if opt.time_dependent else None
-            P1, g_sf = P1_all[b0:b1], g_sf_all[b0:b1]
-            g_q = g1 = None
-            shared1 = do_reg and steps > 1      # the regulariser's second evaluation is Euler evaluation 1 as well (:335-338 = :360-367)
-            if do_reg:
-                sf0 = first[0] if first[0] is not None else sf_all[b0:b1]
-                g1 = torch.empty_like(P1)
-                if shared1:
-                    ops.acc_reg(sf0, first[2], reg_coef, g1, sums[4:5], accumulate=True)
-                else:
-                    sb, sf1 = mlp.new_stash(n_pix), torch.empty_like(P1)
-                    mlp.forward(first[1], ts, time_step, inv_div, sf_out=sf1, stash=sb)
-                    ops.acc_reg(sf0, sf1, reg_coef, g1, sums[4:5], accumulate=True)
-                    g_q = torch.empty_like(P1)
-                    mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], (nb, H, W))
-                    mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
-                    del sb, sf1
-            g_p = None
-            for i in reversed(range(1, steps)):
-                g_new = torch.empty_like(P1)
-                g_o2 = g_p
-                if shared1 and i == 1:          # evaluation 1's output also feeds the regulariser: + dR/dsf_1 (not normalised)
-                    g_o2 = g1 if g_p is None else ops.scale_add(torch.empty_like(P1), g1, b=g_p)
-                mlp.backward_dx(stashes[i], inv_div, g_sf, g_new, gst, gW_reg[5], gb_reg[5], (nb, H, W), scale_ptr=inv,
-                                g_out2=g_o2, g_p_add=g_p)
-                mlp.backward_dw(stashes[i], gst, n_pix, gW_reg[:5], gb_reg[:5])
-                g_p = g_new
-            extra, add = g_p, g_p                    # gradient reaching sf_0 besides G, and reaching P1 directly
-            if shared1:                              # g_p already holds everything that reaches q = P1 + sf_0
-                extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_p)          # g_p - g1
-            elif do_reg:
-                extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_q)          # -g1 + g_q
-                add = g_q
-            g_P = torch.empty_like(P1)
-            mlp.backward_dx(stashes[0], inv_div, g_sf, g_P, gst, gW_reg[5], gb_reg[5], (nb, H, W), scale_ptr=inv,
-                            g_out2=extra, g_p_add=add)
-            mlp.backward_dw(stashes[0], gst, n_pix, gW_reg[:5], gb_reg[:5])
-            ops.unproject_backward(g_P, True, cams['R_1'], cams['K_inv'], out=g_d1_main[b0:b1], accumulate=True)
-
-        gst = mlp.new_gstash(min(Bc, B) * HW)
-        if early_norm and recompute and Bc < B and not whole:
-            with ops.counting_recomputed():          # the stashed evaluations below are the ones the backward needs
-                for b0, b1 in chunks:
-                    mlp_forward_chunk(b0, b1, with_stash=False)
-            warp(0, B)
-            parallel.all_reduce_sum_(sums[:4])
-            scalars = ops.loss_finalize(cfg_all, sums)
-            inv = scalars[0:1]
-            ops.scale_add(g_d1_main, g_d1_main, scale_ptr=inv)
-            for b0, b1 in chunks:
-                # the same evaluations again, stashed; their flow goes to a scratch accumulator (sf_all already holds it)
-                st, first = mlp_forward_chunk(b0, b1, keep_first=bool(do_reg), acc=torch.zeros_like(sf_all[b0:b1]))
-                merged_backward_chunk(b0, b1, st, first, gst, inv)
-                del st[:], first
-            parallel.all_reduce_sum_(sums[4:])
-        elif early_norm:
-            kept = [mlp_forward_chunk(b0, b1, keep_first=bool(do_reg)) for b0, b1 in chunks]
-            warp(0, B)
-            # the batch-global normaliser is known before the MLP backward: all-reduce the four loss sums
-            # now (SURVEY.md section 8e) and hand 1/(S0+1e-8) to the backward kernels as a device scalar
-            parallel.all_reduce_sum_(sums[:4])
-            scalars = ops.loss_finalize(cfg_all, sums)
-            inv = scalars[0:1]
-            ops.scale_add(g_d1_main, g_d1_main, scale_ptr=inv)
-            for (b0, b1), (st, first) in zip(chunks, kept):
-                merged_backward_chunk(b0, b1, st, first, gst, inv)
-                del st[:]
-            del kept
-            parallel.all_reduce_sum_(sums[4:])
+        # (also agreed across ranks: does ANY rank still have to capture a depth-net graph in phase 3?  Then every rank keeps
+        #  the MLP-gradient all-reduce out of flight until after phase 3, so the order of collectives is the same everywhere)
+        late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B,
+                                                                self._may_capture_in_phase3(inp, n_slots))
+        step.set_global_batch(n_global)
+        step.begin_mlp(Bc)
+        if late:
+            scalars, inv = step.run_late()
+        elif recompute:
+            scalars, inv = step.run_recompute()
         else:
-            g_d1_reg = torch.zeros_like(depth_1) if do_reg else None
-            for b0, b1 in chunks:
-                st = mlp_forward_chunk(b0, b1)
-                warp(b0, b1)
-                mlp_backward_chunk(b0, b1, st, gst)
-                del st
-                if do_reg:
-                    reg_chunk(b0, b1, gst)
-        del gst
-        if not early_norm:
-            # per-chunk launches: the batch-global normaliser only exists now.  All-reduce the loss sums
-            # (SURVEY.md section 8e), then scene-flow MLP gradient = inv * main + reg
-            parallel.all_reduce_sum_(sums)
-            scalars = ops.loss_finalize(cfg_all, sums)
-            inv = scalars[0:1]
-            ops.scale_add(k.grad, self._sf_grad_main, scale_ptr=inv, b=k.grad)
+            scalars, inv = step.run_whole_batch()
+        return self._finish_step(epoch, batch_ind, batch, step, scalars, inv, not late, capturing, n_slots)
+
+    def _frame_ids(self, inp):
+        """Frame ids of the two image sets (the hourglass's per-frame embedding); the MiDaS net takes none."""
+        return (None, None) if self.opt.midas else (inp.frame_id_1, inp.frame_id_2)
+
+    def _may_capture_in_phase3(self, inp, n_slots):
+        """Will phase 3 still have to capture a depth-net graph -- is there a chunk that is not kept and has no recompute
+        graph yet?  Over the REAL chunk list of both image sets (a ragged last chunk has its own slot / graph keys)."""
+        if self.warm or not getattr(self.opt, 'depth_graphs', 1):
+            return False
+        cw = self._chunk()
+        for s0, img in ((0, inp.img_1), (n_slots, inp.img_2)):
+            for ci, b0 in enumerate(range(0, img.shape[0], cw)):
+                chunk = img[b0:b0 + cw]
+                kept = self._depth_graphs.get(('keep', s0 + ci, tuple(chunk.shape), bool(self.opt.midas)))
+                if kept is None and self._graph_key('fb', chunk) not in self._depth_graphs:
+                    return True
+        return False
+
+    def _finish_step(self, epoch, batch_ind, batch, step, scalars, inv, early_norm, capturing, n_slots):
+        """Phase 3 and the end of the step, for the MLP and the U-Net path alike.  early_norm: phase 2 has already normalised
+        g_d1_main (regulariser included); else (_SfStep.run_late) inv * main + reg is formed here."""
+        opt, inp, warm, k = self.opt, step.inp, step.warm, self._flat_sf
         # the MLP gradient all-reduce overlaps the depth-net backward, except in a step that still has to
         # capture the depth net's forward+backward graph (no collective in flight during a capture)
         h_sf = None if capturing else k.all_reduce_grads(async_op=True)
 
         # ---- phase 3: depth-net backward from the depth gradients
         if not warm:
-            if early_norm:
-                g_d1 = g_d1_main                      # already normalised, regulariser included
-            else:
-                g_d1 = ops.scale_add(g_d1_main, g_d1_main, scale_ptr=inv, b=g_d1_reg)
-            g_d2 = ops.scale_add(g_d2_main, g_d2_main, scale_ptr=inv)
+            fid1, fid2 = self._frame_ids(inp)
+            g_d1 = step.g_d1_main if early_norm else ops.scale_add(step.g_d1_main, step.g_d1_main, scale_ptr=inv, b=step.g_d1_reg)
+            g_d2 = ops.scale_add(step.g_d2_main, step.g_d2_main, scale_ptr=inv)
             self._depth_backward(inp.img_1, fid1, g_d1, slot0=0)
             self._depth_backward(inp.img_2, fid2, g_d2, slot0=n_slots)
             # 421 MB (MiDaS) in --grad_buckets large all-reduces, each bucket's Adam launch overlapping the next
@@ -909,42 +959,33 @@ class Model(NetInterface):
         #  (flag, count) pair [8], [9] of the loss-scale state counts activation overflows only)
         k.adam_step(skip_ptr=None if (warm or self._gscale is None) else self._gscale[8:10])
 
-        host = self._step_scalars_to_host(scalars, sums, warm)    # the only host synchronisation of the step
-        acc_reg = opt.acc_mul * host[8] / (3.0 * n_global * HW + 1e-6) if do_reg else 0
+        host = self._step_scalars_to_host(scalars, step.sums, warm)    # the only host synchronisation of the step
+        acc_reg = opt.acc_mul * host[8] / (3.0 * step.n_global * step.HW + 1e-6) if step.do_reg else 0
         # --weight_steps scales the gradient only: the logged loss is the unweighted one (`**loss_data`
         # overwrites 'loss' at :226)
-        batch_log = {'size': opt.batch_size, 'loss': host[1] / mul, 'total_loss': host[1] / mul, 'flow_loss_1_2': host[2],
-                     'disp_loss_1_2': host[3], 'sf_loss': host[4], 'acc_reg': acc_reg}
+        batch_log = {'size': opt.batch_size, 'loss': host[1] / step.mul, 'total_loss': host[1] / step.mul,
+                     'flow_loss_1_2': host[2], 'disp_loss_1_2': host[3], 'sf_loss': host[4], 'acc_reg': acc_reg}
         if self._gscale is not None:
             batch_log['steps_skipped'] = self._steps_skipped
-        self._last = {'depth_1': depth_1, 'depth_2': depth_2, 'mask_sum': host[5], 'sf_all': sf_all, 'mseg': mseg}
+        self._last = {'depth_1': step.depth_1, 'depth_2': step.depth_2, 'mask_sum': host[5], 'sf_all': step.sf_all,
+                      'mseg': step.mseg}
         self._export_train_visuals(epoch, batch_ind, batch)
         return batch_log
 
-    # -- --use_cnn: phases 2 and 3 with the U-Net scene-flow network ------------------------------------------------------
+    # -- --use_cnn: phase 2 with the U-Net scene-flow network -------------------------------------------------------------
     def _sf_net_cnn(self, p, t):
         """Model.forward_sf_net with --use_cnn (:346-357)."""
         x = torch.cat([p, t], 1) if self.opt.time_dependent else p
         return self.net_sceneflow(x) / self.opt.sf_mag_div
 
-    def _finish_step_cnn(self, epoch, batch_ind, batch, inp, depth_1, depth_2, steps, time_step, warm, do_reg, n_slots, fid1,
-                         fid2, mul, disp_mode, sums, g_d1_main, g_d2_main):
-        """Everything downstream of the depth maps when the scene-flow network is the U-Net (networks/FCNUnet.py): the
-        network runs under PyTorch autograd on this package's convolution kernels, the geometry and the losses stay the ONE
-        fused warp+loss launch -- its scene-flow gradient is what the U-Net's backward starts from, with the batch-global
-        normaliser applied as a device scalar.  The regulariser's first evaluation is Euler evaluation 0, as in the MLP path."""
-        opt, dev = self.opt, self.device
-        B, _, H, W = inp.img_1.shape
-        HW = H * W
-        k = self._flat_sf
-        cams = {kk: getattr(inp, kk) for kk in CAM_KEYS}
-        mask_2 = inp.mask_2.reshape(B, H, W)
-        mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
-        cfg = ops.warp_cfg(B, H, W, midas_mask=opt.midas, crit_l2=warm, disp_mode=disp_mode, loss_on_sf=not opt.use_disp,
-                           flow_mul=opt.flow_mul * mul, disp_mul=opt.disp_mul * mul)
-        _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
-        reg_coef = opt.acc_mul / (3.0 * n_global * HW + 1e-6)
-        P1 = ops.unproject(depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True).requires_grad_(True)
+    def _unet_forward_backward(self, step):
+        """Phase 2 when the scene-flow network is the U-Net (networks/FCNUnet.py): the network runs under PyTorch autograd on
+        this package's convolution kernels, the geometry and the losses stay the ONE fused warp+loss launch -- its scene-flow
+        gradient is what the U-Net's backward starts from, with the batch-global normaliser applied as a device scalar.  The
+        regulariser's first evaluation is Euler evaluation 0, as in the MLP path.  Returns (scalars, inv) like the schedules."""
+        dev, inp, steps, time_step, do_reg = self.device, step.inp, step.steps, step.time_step, step.do_reg
+        B, H, W, HW, sums = step.B, step.H, step.W, step.HW, step.sums
+        P1 = ops.unproject(step.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True).requires_grad_(True)
         ts = inp.time_stamp_1
         # the whole batch goes through the U-Net under autograd: fail early, with the numbers, instead of somewhere inside it
         evals = steps + (1 if do_reg else 0)
@@ -956,7 +997,7 @@ class Model(NetInterface):
                    % (B, H, W, evals, self._cnn_bytes_per_px(), need / 2 ** 30, free / 2 ** 30))
             if self._cnn_px_measured > 0:        # a measured footprint: fail early, with the numbers
                 raise RuntimeError(msg)
-            import warnings                       # an a-priori estimate must not reject a configuration that may well run
+            # an a-priori estimate must not reject a configuration that may well run
             warnings.warn(msg + ' (a-priori estimate: nothing has been measured yet, trying anyway)')
         mem0 = torch.cuda.memory_allocated(dev)
         with torch.enable_grad():
@@ -969,17 +1010,9 @@ class Model(NetInterface):
         # measured footprint of an evaluation (like _keep_per_px for the depth net's slots): the planner's next decisions
         # use it instead of the a-priori figure
         self._cnn_px_measured = max(self._cnn_px_measured, (torch.cuda.memory_allocated(dev) - mem0) / float(B * HW * steps))
-        sf_all = sf_acc.detach().contiguous()
-        sf_used = ops.mul_mask(torch.empty_like(sf_all), sf_all, mseg) if mseg is not None else sf_all
-        csum, g_sf = torch.empty(4, device=dev), torch.empty_like(sf_all)
-        ops.warp_loss_fused(cfg, depth_1, depth_2, inp.flow_1_2, mask_2, sf_used, cams, out=(csum, g_d1_main, g_d2_main, g_sf))
-        if mseg is not None:
-            ops.mul_mask(g_sf, g_sf, mseg)
-        sums[:4] += csum
-        parallel.all_reduce_sum_(sums[:4])
-        scalars = ops.loss_finalize(cfg, sums)
-        inv = scalars[0:1]
-        ops.scale_add(g_d1_main, g_d1_main, scale_ptr=inv)
+        step.sf_all = sf_acc.detach().contiguous()
+        step.g_sf_all = g_sf = torch.empty_like(step.sf_all)
+        scalars, inv = step.warp_whole_batch()
         ops.scale_add(g_sf, g_sf, scale_ptr=inv)
         sf_acc.backward(g_sf, retain_graph=bool(do_reg))        # parameter gradients land in the flat buffer's views
         if do_reg:
@@ -987,42 +1020,10 @@ class Model(NetInterface):
                 sf1 = self._sf_net_cnn(P1 + sf0, ts + time_step)
                 dsum = (sf1 - sf0).abs().sum()
             sums[4:5] += dsum.detach()
-            (dsum * reg_coef).backward()
+            (dsum * step.reg_coef).backward()
         parallel.all_reduce_sum_(sums[4:])
-        ops.unproject_backward(P1.grad.contiguous(), True, cams['R_1'], cams['K_inv'], out=g_d1_main, accumulate=True)
-        h_sf = None if capturing else k.all_reduce_grads(async_op=True)
-        if not warm:
-            g_d2 = ops.scale_add(g_d2_main, g_d2_main, scale_ptr=inv)
-            self._depth_backward(inp.img_1, fid1, g_d1_main, slot0=0)
-            self._depth_backward(inp.img_2, fid2, g_d2, slot0=n_slots)
-            skip = None
-            if self._gscale is not None:
-                if parallel.is_distributed():          # both monitors: gradients [3], forward activations [6]
-                    both = torch.stack([self._gscale[3], self._gscale[6]])
-                    torch.distributed.all_reduce(both, op=torch.distributed.ReduceOp.MAX)
-                    self._gscale[3:4].copy_(both[0:1])
-                    self._gscale[6:7].copy_(both[1:2])
-                ops.gscale_end(self._gscale)
-                skip = self._gscale[4:5]
-            self._flat_depth.all_reduce_and_adam_step(getattr(opt, 'grad_buckets', 4), skip_ptr=skip)
-        if capturing:
-            k.all_reduce_grads()
-        if h_sf is not None:
-            h_sf.wait()
-        # (fp16 activations: an ACTIVATION that overflowed fp16 makes the depth map, and with it the scene-flow network's
-        #  gradient, non-finite: that step skips BOTH updates.  A mere loss-scale overflow of the depth net's fp16 GRADIENTS
-        #  leaves the depth maps finite and the scene-flow network's fp32 gradients valid: its update goes through -- the
-        #  (flag, count) pair [8], [9] of the loss-scale state counts activation overflows only)
-        k.adam_step(skip_ptr=None if (warm or self._gscale is None) else self._gscale[8:10])
-        host = self._step_scalars_to_host(scalars, sums, warm)    # the only host synchronisation of the step
-        acc_reg = opt.acc_mul * host[8] / (3.0 * n_global * HW + 1e-6) if do_reg else 0
-        batch_log = {'size': opt.batch_size, 'loss': host[1] / mul, 'total_loss': host[1] / mul, 'flow_loss_1_2': host[2],
-                     'disp_loss_1_2': host[3], 'sf_loss': host[4], 'acc_reg': acc_reg}
-        if self._gscale is not None:
-            batch_log['steps_skipped'] = self._steps_skipped
-        self._last = {'depth_1': depth_1, 'depth_2': depth_2, 'mask_sum': host[5], 'sf_all': sf_all, 'mseg': mseg}
-        self._export_train_visuals(epoch, batch_ind, batch)
-        return batch_log
+        ops.unproject_backward(P1.grad.contiguous(), True, inp.R_1, inp.K_inv, out=step.g_d1_main, accumulate=True)
+        return scalars, inv
 
     def _step_scalars_to_host(self, scalars, sums, warm):
         """The step's ONE device -> host copy: the loss scalars, the regulariser sum and -- with fp16 activation storage --
@@ -1036,7 +1037,6 @@ class Model(NetInterface):
         self._steps_skipped = int(host[10])
         run = 0 if warm else int(host[13])
         if run >= 3:
-            import warnings
             limit = int(getattr(self.opt, 'max_act_overflow_skips', 25))
             msg = ('fp16 activation storage: an activation of the depth network left fp16\'s range in %d consecutive steps; '
                    'every one of them was skipped (%d skipped steps in all).  The loss scale cannot cure this: lower the '
