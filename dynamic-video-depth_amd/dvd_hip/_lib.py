@@ -181,6 +181,11 @@ SIGNATURES = {
     'dvd_maxpool3s2_bwd': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
     'dvd_adam_step_guarded': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_float,
                                       c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
+    # --optim sgd (additions within ABI 8)
+    'dvd_sgd_step': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float, c_float,
+                             c_float, c_int, c_void_p]),
+    'dvd_sgd_step_guarded': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float,
+                                     c_float, c_float, c_int, c_void_p, c_void_p]),
 }
 
 _lock = threading.Lock()

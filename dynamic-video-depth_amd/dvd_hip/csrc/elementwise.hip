@@ -1,10 +1,12 @@
 // Small HBM-bound helpers of the training step (gfx950): gradient combination with a
-// device-side scalar, the acceleration regulariser's elementwise part, and fused Adam.
+// device-side scalar, the acceleration regulariser's elementwise part, and fused Adam / SGD.
 //
 // Reference counterparts (/root/reference):
 //   models/scene_flow_motion_field.py:326-344   _opt_reg: |sf1 - sf0| mean and its gradient
 //   models/scene_flow_motion_field.py:113-115,212-213 + torch.optim.Adam  (betas 0.5/0.9,
 //       options/options_train.py:84-87): one fused pass over a flat parameter buffer
+//   the same with torch.optim.SGD under --optim sgd (models/netinterface.py:96-102,126-135; momentum, dampening and
+//       weight decay from options/options_train.py:88-93)
 //   the 1/(sum(mask)+1e-8) normaliser of _calc_loss (:297-306) applied late, as a device
 //       scalar, so that no host synchronisation sits between the loss and the backward.
 // All kernels: 16-byte accesses, grid-stride, <= 2048 blocks.
@@ -205,6 +207,60 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #undef DVD_ADAM
 }
 
+// torch.optim.SGD, no nesterov, not maximize (torch/optim/sgd.py _single_tensor_sgd), same operation order per element:
+//   d = g + wd p                                  (wd != 0)
+//   buf = d  at the first effective step, else  buf = (buf * momentum) + (1 - dampening) d      (momentum != 0)
+//   p = p - lr (momentum != 0 ? buf : d)
+// with g = s * g1 + g2 formed as adam_kernel forms it.  buf is null when momentum is 0.  The skip pair follows adam_kernel:
+// skip[0] != 0 leaves p and buf untouched, and the effective step is step - skip[1] -- so steps skipped before the first real
+// one leave buf uninitialised, and the first non-skipped step (effective step 1) sets buf = d.  The host never learns of a skip.
+__device__ __forceinline__ float sgd_elem(float p, float g, float* b, bool first, float lr, float momentum, float omd, float wd) {
+  float d = g;
+  if (wd != 0.0f) d = d + wd * p;
+  if (b) {
+    *b = first ? d : *b * momentum + omd * d;
+    d = *b;
+  }
+  return p - lr * d;
+}
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g1, float sa,
+                                                  const float* __restrict__ sa_ptr, const float* __restrict__ g2,
+                                                  float* __restrict__ buf, long long n, float lr, float momentum, float omd,
+                                                  float wd, const float* __restrict__ skip, int step) {
+  if (skip && skip[0] != 0.0f) return;
+  const bool first = step - (skip ? (int)skip[1] : 0) <= 1;
+  const float s = sa * (sa_ptr ? sa_ptr[0] : 1.0f);
+  const long long n4 = n >> 2;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    float4 g = reinterpret_cast<const float4*>(g1)[i];
+    g.x *= s;
+    g.y *= s;
+    g.z *= s;
+    g.w *= s;
+    if (g2) {
+      const float4 w = reinterpret_cast<const float4*>(g2)[i];
+      g.x += w.x;
+      g.y += w.y;
+      g.z += w.z;
+      g.w += w.w;
+    }
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    float4 bb = buf ? reinterpret_cast<float4*>(buf)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* bp = buf ? &bb.x : nullptr;
+    pp.x = sgd_elem(pp.x, g.x, bp, first, lr, momentum, omd, wd);
+    pp.y = sgd_elem(pp.y, g.y, bp ? &bb.y : nullptr, first, lr, momentum, omd, wd);
+    pp.z = sgd_elem(pp.z, g.z, bp ? &bb.z : nullptr, first, lr, momentum, omd, wd);
+    pp.w = sgd_elem(pp.w, g.w, bp ? &bb.w : nullptr, first, lr, momentum, omd, wd);
+    if (buf) reinterpret_cast<float4*>(buf)[i] = bb;
+    reinterpret_cast<float4*>(p)[i] = pp;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    const float g = s * g1[i] + (g2 ? g2[i] : 0.0f);
+    p[i] = sgd_elem(p[i], g, buf ? &buf[i] : nullptr, first, lr, momentum, omd, wd);
+  }
+}
+
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace dvd
@@ -294,6 +350,30 @@ int dvd_adam_step_guarded(float* param, const float* grad1, float scale, const f
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), param, grad1,
                      scale, scale_ptr, grad2, exp_avg, exp_avg_sq, n, beta1, beta2, eps, step_size, inv_sqrt_bc2, skip_flag, step, lr);
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+int dvd_sgd_step(float* param, const float* grad1, float scale, const float* scale_ptr, const float* grad2, float* momentum_buf,
+                 long long n, float lr, float momentum, float dampening, float weight_decay, int step, dvd_stream_t stream) {
+  return dvd_sgd_step_guarded(param, grad1, scale, scale_ptr, grad2, momentum_buf, n, lr, momentum, dampening, weight_decay, step,
+                              nullptr, stream);
+}
+
+int dvd_sgd_step_guarded(float* param, const float* grad1, float scale, const float* scale_ptr, const float* grad2,
+                         float* momentum_buf, long long n, float lr, float momentum, float dampening, float weight_decay, int step,
+                         const float* skip_flag, dvd_stream_t stream) {
+  using namespace dvd;
+  DVD_REQUIRE(param && grad1 && n > 0 && step >= 1, "sgd_step: bad argument");
+  DVD_REQUIRE(momentum == 0.0f || momentum_buf, "sgd_step: momentum != 0 needs a momentum buffer");
+  DVD_REQUIRE(al16(param) && al16(grad1) && al16(grad2) && al16(momentum_buf), "sgd_step: pointers must be 16-byte aligned");
+  float* buf = momentum != 0.0f ? momentum_buf : nullptr;
+  // the fused optimiser step's bytes: param and grad1 (+ grad2) in, param out, the momentum buffer in and out
+  bytes_add(DVD_BYTES_ADAM, 4.0 * (double)n * (3 + (grad2 ? 1 : 0) + (buf ? 2 : 0)));
+  // torch passes alpha = 1 - dampening as a Python float: formed in double, rounded once
+  const float omd = (float)(1.0 - (double)dampening);
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, static_cast<hipStream_t>(stream), param, grad1, scale,
+                     scale_ptr, grad2, buf, n, lr, momentum, omd, weight_decay, skip_flag, step);
   DVD_LAUNCH_OK();
   return DVD_OK;
 }

@@ -95,9 +95,16 @@ class NetInterface(object):
         self._internal_logger = _EpochMean()
         self.opt = opt
         self.full_logdir = getattr(opt, 'full_logdir', None)
-        if opt.optim != 'adam':
-            raise NotImplementedError('the fused HIP step implements Adam (the shipped --optim); got %s' % opt.optim)
-        self.optim_params = {'betas': (opt.adam_beta1, opt.adam_beta2)}
+        # optim_params as netinterface.py:126-135 fills them; the fused HIP step (flat.FlatNet) implements both kinds.  The SGD
+        # flags are read under --optim sgd only, with options_train.py:88-93's defaults
+        if opt.optim == 'adam':
+            self.optim_params = {'betas': (opt.adam_beta1, opt.adam_beta2)}
+        elif opt.optim == 'sgd':
+            self.optim_params = {'momentum': getattr(opt, 'sgd_momentum', 0.9),
+                                 'dampening': getattr(opt, 'sgd_dampening', 0),
+                                 'weight_decay': getattr(opt, 'wdecay', 0.0)}
+        else:
+            raise NotImplementedError('the fused HIP step implements --optim adam and sgd; got %s' % opt.optim)
         self._nets, self._optimizers, self._metrics = [], [], []
         self._moveable_vars = []
         self.input_names, self.gt_names, self.aux_names = [], [], []

@@ -22,7 +22,7 @@ What is different is HOW a step runs.  The reference builds one autograd graph o
      reproduce the single-device result on the concatenated batch;
   3. (not in the warm-up phase) depth nets backward from the depth gradients of phase 2: a replay of each kept slot's
      backward graph (or a forward+backward recompute graph); then one RCCL all-reduce per net over its flat gradient
-     buffer and one fused Adam launch per net.
+     buffer and one fused optimiser launch per net (Adam, or SGD under --optim sgd).
 
 Every convolution (the 7x7 stride-2 stem included, round 4), BatchNorm+ReLU, pooling, up-sampling and the MLP run on this
 package's HIP kernels (csrc/); the matrix kernels evaluate fp32 products from two fp16 terms per operand (csrc/dvd_split.h).
@@ -440,14 +440,19 @@ class Model(NetInterface):
         self._step_no = 0
         self.warm = False
 
-    # flat parameter buffers + fused Adam replace the two torch.optim.Adam objects (:113-115)
+    # flat parameter buffers + fused Adam (or SGD, --optim sgd) replace the two torch.optim objects (:113-115)
     def to(self, device):
         super().to(device)
         if self.device.type != 'cuda':
             raise RuntimeError('dvd_hip Model runs on a GPU only (the reference CPU path is the oracle)')
-        betas = self.optim_params['betas']
-        self._flat_depth = flat.FlatNet(self.net_depth, self.opt.lr, betas)
-        self._flat_sf = flat.FlatNet(self.net_sceneflow, self.opt.lr * self.opt.scene_lr_mul, betas)
+        if self.opt.optim == 'sgd':
+            def make(net, lr):
+                return flat.FlatNet.sgd(net, lr, **self.optim_params)
+        else:
+            def make(net, lr):
+                return flat.FlatNet(net, lr, self.optim_params['betas'])
+        self._flat_depth = make(self.net_depth, self.opt.lr)
+        self._flat_sf = make(self.net_sceneflow, self.opt.lr * self.opt.scene_lr_mul)
         self.optimizer_depth, self.optimizer_scene = self._flat_depth, self._flat_sf
         self._optimizers = [self._flat_depth, self._flat_sf]
         self._sf_grad_main = torch.zeros_like(self._flat_sf.grad)
@@ -948,7 +953,7 @@ class Model(NetInterface):
                     self._gscale[6:7].copy_(both[1:2])
                 ops.gscale_end(self._gscale)
                 skip = self._gscale[4:5]
-            self._flat_depth.all_reduce_and_adam_step(getattr(opt, 'grad_buckets', 4), skip_ptr=skip)
+            self._flat_depth.all_reduce_and_step(getattr(opt, 'grad_buckets', 4), skip_ptr=skip)
         if capturing:
             k.all_reduce_grads()
         if h_sf is not None:
@@ -957,7 +962,7 @@ class Model(NetInterface):
         #  gradient, non-finite: that step skips BOTH updates.  A mere loss-scale overflow of the depth net's fp16 GRADIENTS
         #  leaves the depth maps finite and the scene-flow network's fp32 gradients valid: its update goes through -- the
         #  (flag, count) pair [8], [9] of the loss-scale state counts activation overflows only)
-        k.adam_step(skip_ptr=None if (warm or self._gscale is None) else self._gscale[8:10])
+        k.step(skip_ptr=None if (warm or self._gscale is None) else self._gscale[8:10])
 
         host = self._step_scalars_to_host(scalars, step.sums, warm)    # the only host synchronisation of the step
         acc_reg = opt.acc_mul * host[8] / (3.0 * step.n_global * step.HW + 1e-6) if step.do_reg else 0

@@ -290,7 +290,7 @@ BYTE_CLASS_KERNELS = {
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel',), 'geometry': ('unproject_',),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 
@@ -584,7 +584,7 @@ def acc_reg(sf0, sf1, coef, g_sf1, abs_sum, accumulate=True):
                                sf0.numel(), _stream()), 'dvd_acc_reg')
 
 
-# Bumped by every optimiser step: the fused Adam kernel rewrites parameters behind autograd's back
+# Bumped by every optimiser step: the fused Adam / SGD kernels rewrite parameters behind autograd's back
 # (no `_version` change), and per-weight derived buffers (fragment-ordered conv weights) key on it.
 WEIGHT_EPOCH = [0]
 
@@ -597,6 +597,17 @@ def adam_step(param, grad1, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps=1e-
     _lib.check(lib.dvd_adam_step_guarded(_p(param), _p(grad1), float(scale), _p(scale_ptr), _p(grad2), _p(exp_avg),
                                          _p(exp_avg_sq), param.numel(), float(lr), float(beta1), float(beta2), float(eps),
                                          int(step), _p(skip_ptr), _stream()), 'dvd_adam_step')
+
+
+def sgd_step(param, grad1, momentum_buf, step, lr, momentum, dampening=0.0, weight_decay=0.0, scale=1.0, scale_ptr=None,
+             grad2=None, skip_ptr=None):
+    """torch.optim.SGD on a flat slice (momentum_buf may be None at momentum 0).  skip_ptr: the (flag, count) pair of
+    ops.adam_step; `step` - count == 1 is the first effective step (buf = d), decided on the device."""
+    WEIGHT_EPOCH[0] += 1
+    lib = _lib.load()
+    _lib.check(lib.dvd_sgd_step_guarded(_p(param), _p(grad1), float(scale), _p(scale_ptr), _p(grad2), _p(momentum_buf),
+                                        param.numel(), float(lr), float(momentum), float(dampening), float(weight_decay),
+                                        int(step), _p(skip_ptr), _stream()), 'dvd_sgd_step')
 
 
 def gscale_new(device, target_exponent=4.0):

@@ -80,7 +80,7 @@ enum {
   DVD_BYTES_POOL = 6,       /* max-pool of the stem, forward and backward                                                         */
   DVD_BYTES_GCONV = 7,      /* grouped 3x3 with 8 channels per group on the vector unit (ResNeXt stage 1), all three passes       */
   DVD_BYTES_ELEMENTWISE = 8,/* scale_add, mul_mask, acc_reg, cast_scale, depth head                                               */
-  DVD_BYTES_ADAM = 9,       /* the fused Adam step: param, grad, two moments in, param and moments out                            */
+  DVD_BYTES_ADAM = 9,       /* the fused optimiser step: param, grad(s), optimiser state in, param and state out (Adam or SGD)     */
   DVD_BYTES_GEOMETRY = 10,  /* unproject forward / backward                                                                       */
   DVD_BYTES_CLASSES = 11
 };
@@ -588,6 +588,18 @@ int dvd_cast_scale_f32(const void* in, int f16, float* out, long long n, const f
 int dvd_adam_step_guarded(float* param, const float* grad1, float scale, const float* scale_ptr, const float* grad2,
                           float* exp_avg, float* exp_avg_sq, long long n, float lr, float beta1, float beta2, float eps,
                           int step, const float* skip_flag, dvd_stream_t stream);
+/* dvd_sgd_step: torch.optim.SGD as the reference builds it under --optim sgd (models/netinterface.py:96-102,126-135: momentum =
+ * opt.sgd_momentum, dampening = opt.sgd_dampening, weight_decay = opt.wdecay; defaults options/options_train.py:88-93; no
+ * nesterov) on a flat buffer with grad = s*grad1 + grad2 as in dvd_adam_step:  d = g + wd p;  buf = d at the first step, else
+ * momentum buf + (1 - dampening) d;  p -= lr (momentum != 0 ? buf : d).  momentum_buf may be null when momentum == 0. */
+int dvd_sgd_step(float* param, const float* grad1, float scale, const float* scale_ptr, const float* grad2, float* momentum_buf,
+                 long long n, float lr, float momentum, float dampening, float weight_decay, int step, dvd_stream_t stream);
+/* dvd_sgd_step that does nothing -- momentum buffer untouched -- when skip_flag[0] != 0, and takes step - skip_flag[1] as the
+ * effective step, as dvd_adam_step_guarded does (torch.amp's GradScaler skips optimizer.step(), models/netinterface.py:96-102):
+ * effective step 1 is the first step of torch.optim.SGD (buf = d, no dampening), decided on the device. */
+int dvd_sgd_step_guarded(float* param, const float* grad1, float scale, const float* scale_ptr, const float* grad2,
+                         float* momentum_buf, long long n, float lr, float momentum, float dampening, float weight_decay, int step,
+                         const float* skip_flag, dvd_stream_t stream);
 
 /* nn.MaxPool2d(3, stride 2, padding 1) of the ResNeXt stem (third_party/midas_blocks.py:35-45), ATen's semantics (the first
  * maximum of a window takes the gradient).  x fp32 [planes][H][W] -> y [planes][Ho][Wo] (Ho = (H - 1) / 2 + 1) in fp32 or
