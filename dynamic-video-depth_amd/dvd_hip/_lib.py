@@ -53,6 +53,11 @@ class XPackItem(ctypes.Structure):          # struct dvd_xpack_item
                 ('Cout', c_int), ('Cin', c_int), ('KS', c_int), ('groups', c_int), ('transposed', c_int)]
 
 
+class GatherItem(ctypes.Structure):         # struct dvd_gather_item
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes_per_pair', c_longlong)]
+
+
+GATHER_MAX = 32
 PtrArr6 = c_void_p * 6
 PtrArr5 = c_void_p * 5
 
@@ -186,6 +191,8 @@ SIGNATURES = {
                              c_float, c_int, c_void_p]),
     'dvd_sgd_step_guarded': (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_longlong, c_float, c_float,
                                      c_float, c_float, c_int, c_void_p, c_void_p]),
+    # mixed frame gaps: the batched pair permutation (addition within ABI 8)
+    'dvd_gather_pairs': (c_int, [ctypes.POINTER(GatherItem), c_int, c_void_p, c_int, c_void_p]),
 }
 
 _lock = threading.Lock()

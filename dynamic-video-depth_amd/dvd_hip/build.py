@@ -39,6 +39,7 @@ SOURCES = [
     ('consistency.hip', ['-ffp-contract=off']),
     ('a16.hip', []),
     ('pool.hip', []),
+    ('gather.hip', []),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -94,18 +94,64 @@ def keep_slot_fits(est, free, total, reserve, spare, kept, budget, head_room=0.0
     return kept + est <= budget and free - est >= reserve + head_room * total + spare
 
 
+def pairs_per_chunk(B, budget_bytes, stash_bytes, gstash_bytes, steps, with_reg):
+    """Pairs that go through the scene-flow MLP kernels at once: what --mlp_stash_gb (`budget_bytes`) holds of one pair's
+    activation stashes (`stash_bytes` per Euler evaluation; the regulariser needs two) and backward scratch (`gstash_bytes`)."""
+    per_pair = stash_bytes * max(steps, 2 if with_reg else 1) + gstash_bytes
+    return int(max(1, min(B, budget_bytes // per_pair)))
+
+
+def gap_plan(steps_per_pair, budget_bytes, stash_bytes, gstash_bytes, with_reg):
+    """The schedule of a step whose pairs differ in frame gap.  steps_per_pair: Euler steps of every pair, in the caller's
+    order.  Returns a dict:
+      perm    the gap-grouped order: pairs sorted by their step count, stable (grouped[j] = caller[perm[j]]);
+      groups  [(b0, b1, steps)] over the grouped order, one per distinct step count, ascending;
+      chunks  [(b0, b1, steps)]: what goes through the MLP kernels at once -- pairs_per_chunk(...) pairs of ONE group, never
+              across a group boundary;
+      whole_bytes  stashes of a step that keeps every forward stash until its backward (sum_b steps_b stashes + the backward
+                   scratch of the largest chunk + the regulariser's extra stash for the largest gap-1 chunk);
+      chunk_bytes  stashes of the most expensive single chunk (late-normaliser / recompute schedules).
+    A list whose entries are all equal gives ONE group, the identity permutation and the chunk list and byte figures of a
+    uniform-gap step."""
+    steps_per_pair = [int(v) for v in steps_per_pair]
+    B = len(steps_per_pair)
+    perm = sorted(range(B), key=lambda b: steps_per_pair[b])        # sorted() is stable
+    groups, chunks = [], []
+    b0 = 0
+    while b0 < B:
+        st = steps_per_pair[perm[b0]]
+        b1 = b0
+        while b1 < B and steps_per_pair[perm[b1]] == st:
+            b1 += 1
+        groups.append((b0, b1, st))
+        Bc = pairs_per_chunk(B, budget_bytes, stash_bytes, gstash_bytes, st, with_reg)
+        chunks.extend((c0, min(b1, c0 + Bc), st) for c0 in range(b0, b1, Bc))
+        b0 = b1
+    longest = max(c1 - c0 for c0, c1, _ in chunks)
+    longest_gap1 = max([c1 - c0 for c0, c1, st in chunks if st == 1] or [0]) if with_reg else 0
+    whole = sum(steps_per_pair) * stash_bytes + longest * gstash_bytes + longest_gap1 * stash_bytes
+    chunk = max((c1 - c0) * (stash_bytes * max(st, 2 if with_reg else 1) + gstash_bytes) for c0, c1, st in chunks)
+    return {'perm': perm, 'groups': groups, 'chunks': chunks, 'whole_bytes': whole, 'chunk_bytes': chunk}
+
+
 class _SfStep:
     """Phase 2 of `Model._train_on_batch` (geometry + scene-flow network + losses, forward and backward): what its pieces share
     for ONE step, and the three schedules the MLP's activation stashes allow.  Per-chunk data (stashes, backward scratch) stay
     locals of the schedule methods: they bound the step's peak HBM; the object itself does not outlive the step."""
-    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg):
+    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups=None):
         opt = self.opt = model.opt
         self.inp, self.mlp, self.flat_sf, self.sf_grad_main = inp, model._mlp, model._flat_sf, model._sf_grad_main
         self.depth_1, self.depth_2 = depth_1, depth_2
         self.steps, self.time_step, self.warm, self.do_reg = steps, time_step, warm, do_reg
         B, _, H, W = inp.img_1.shape
         self.B, self.H, self.W, self.HW = B, H, W, H * W
-        self.mul = steps if opt.weight_steps else 1
+        # frame gaps: one group [(0, B, steps)] for a uniform batch; a mixed batch is in gap-grouped order (gap_plan) and
+        # `steps` is its largest count -- every chunk of the MLP path carries its own
+        self.groups = groups if groups else [(0, B, steps)]
+        self.mixed = len(self.groups) > 1
+        # --weight_steps (:189-190): a uniform batch scales flow_mul / disp_mul of the ONE warp+loss launch and divides the
+        # logged loss again; a mixed batch weights per gap group (group_mul) and logs the unweighted sums as they are
+        self.mul = steps if (opt.weight_steps and not self.mixed) else 1
         self.disp_mode = 1 if opt.use_disp else (2 if opt.use_disp_ratio else 0)
         self.sums = torch.zeros(8, device=model.device)            # [S0..S3, sum|sf1-sf0|, 0, 0, 0]
         self.g_d1_main, self.g_d2_main = torch.empty_like(depth_1), torch.empty_like(depth_2)
@@ -117,34 +163,41 @@ class _SfStep:
         self.mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
         self.cfg_all = self.warp_cfg(B)
 
-    def warp_cfg(self, n_pairs):
+    def warp_cfg(self, n_pairs, mul=None):
         opt = self.opt
+        mul = self.mul if mul is None else mul
         return ops.warp_cfg(n_pairs, self.H, self.W, midas_mask=opt.midas, crit_l2=self.warm, disp_mode=self.disp_mode,
-                            loss_on_sf=not opt.use_disp, flow_mul=opt.flow_mul * self.mul, disp_mul=opt.disp_mul * self.mul)
+                            loss_on_sf=not opt.use_disp, flow_mul=opt.flow_mul * mul, disp_mul=opt.disp_mul * mul)
+
+    def group_mul(self, steps):
+        """--weight_steps in a mixed batch: the gradient weight of a pair with `steps` Euler steps (else None = self.mul)."""
+        return steps if (self.opt.weight_steps and self.mixed) else None
 
     def set_global_batch(self, n_global):
         """n_global: pairs of ALL ranks (parallel.agree_on_step_plan); the regulariser is a mean over them."""
         self.n_global = n_global
         self.reg_coef = self.opt.acc_mul / (3.0 * n_global * self.HW + 1e-6)
 
-    def begin_mlp(self, Bc):
-        """The MLP path's batch-wide tensors; Bc pairs go through the MLP kernels at once (Model._pairs_per_chunk)."""
+    def begin_mlp(self, Bc, chunks=None):
+        """The MLP path's batch-wide tensors; Bc pairs go through the MLP kernels at once (Model._pairs_per_chunk).  chunks:
+        the (b0, b1, steps) list of a mixed batch (gap_plan: no chunk crosses a gap group), Bc its longest chunk."""
         k, B, inp = self.flat_sf, self.B, self.inp
         self.gW_main = [k.view(self.sf_grad_main, 2 * i) for i in range(6)]
         self.gb_main = [k.view(self.sf_grad_main, 2 * i + 1) for i in range(6)]
         self.gW_reg = [k.view(k.grad, 2 * i) for i in range(6)]
         self.gb_reg = [k.view(k.grad, 2 * i + 1) for i in range(6)]
-        self.Bc, self.chunks = Bc, [(b0, min(B, b0 + Bc)) for b0 in range(0, B, Bc)]
+        self.Bc = Bc
+        self.chunks = list(chunks) if chunks else [(b0, min(B, b0 + Bc), self.steps) for b0 in range(0, B, Bc)]
         self.P1_all = ops.unproject(self.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True)
         self.sf_all = torch.zeros(B, 3, self.H, self.W, device=self.depth_1.device)
         self.g_sf_all = torch.empty_like(self.sf_all)
 
-    def mlp_forward_chunk(self, b0, b1, keep_first=None, acc=None, with_stash=True):
+    def mlp_forward_chunk(self, b0, b1, steps, keep_first=None, acc=None, with_stash=True):
         """Euler integration of the scene flow over `steps` frames (:360-367).  keep_first: also
         return sf_0 and q = P1 + sf_0 of the first evaluation (the regulariser's sf_0, see below).
         acc: the tensor the integrated flow is accumulated into (default: this chunk of sf_all); with_stash=False: no
         activation stashes (the first pass of the recompute schedule)."""
-        mlp, steps = self.mlp, self.steps
+        mlp = self.mlp
         ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
         n_pix = (b1 - b0) * self.HW
         stashes, p_cur, first = [], self.P1_all[b0:b1], None
@@ -166,12 +219,12 @@ class _SfStep:
             p_cur = p_next
         return (stashes, first) if keep_first is not None else stashes
 
-    def warp(self, b0, b1):
+    def warp(self, b0, b1, mul=None):
         inp, mseg = self.inp, self.mseg
         sf_used = self.sf_all[b0:b1]
         if mseg is not None:
             sf_used = ops.mul_mask(torch.empty_like(sf_used), sf_used, mseg[b0:b1])
-        cfg = self.cfg_all if (b0, b1) == (0, self.B) else self.warp_cfg(b1 - b0)
+        cfg = self.cfg_all if ((b0, b1) == (0, self.B) and mul is None) else self.warp_cfg(b1 - b0, mul)
         csum = torch.empty(4, device=self.sums.device)
         ops.warp_loss_fused(cfg, self.depth_1[b0:b1], self.depth_2[b0:b1], inp.flow_1_2[b0:b1], self.mask_2[b0:b1],
                             sf_used, {kk: getattr(inp, kk)[b0:b1] for kk in CAM_KEYS},
@@ -180,12 +233,12 @@ class _SfStep:
             ops.mul_mask(self.g_sf_all[b0:b1], self.g_sf_all[b0:b1], mseg[b0:b1])
         self.sums[:4] += csum
 
-    def mlp_backward_chunk(self, b0, b1, stashes, gst):
+    def mlp_backward_chunk(self, b0, b1, steps, stashes, gst):
         """Backward through the Euler chain: g_p_i = g_p_{i+1} + J_i^T (g_acc + g_p_{i+1})."""
         mlp, inv_div, gW_main, gb_main = self.mlp, self.inv_div, self.gW_main, self.gb_main
         nb, n_pix = b1 - b0, (b1 - b0) * self.HW
         g_p = None
-        for i in reversed(range(self.steps)):
+        for i in reversed(range(steps)):
             g_new = torch.empty_like(self.P1_all[b0:b1])
             mlp.backward_dx(stashes[i], inv_div, self.g_sf_all[b0:b1], g_new, gst, gW_main[5], gb_main[5], (nb, self.H, self.W),
                             g_out2=g_p, g_p_add=g_p)
@@ -213,7 +266,7 @@ class _SfStep:
         mlp.backward_dw(sa, gst, n_pix, gW_reg[:5], gb_reg[:5])
         ops.unproject_backward(g_P, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_reg[b0:b1])
 
-    def merged_backward_chunk(self, b0, b1, stashes, first, gst, inv):
+    def merged_backward_chunk(self, b0, b1, steps, stashes, first, gst, inv):
         """Main loss and acceleration regulariser through ONE backward of the first evaluation.
 
         The regulariser's sf_0 = MLP(P1, t_1) (:329-333) is the first Euler evaluation of the main
@@ -224,7 +277,7 @@ class _SfStep:
         From gap 2 on the regulariser's sf_1 = MLP(P1 + sf_0, t_1 + dt) (:335-338) is Euler evaluation 1 as well
         (:360-367), so that one is shared too (round 4): evaluation 1 receives G + g_p2 + g1, and a gap-k step costs k
         evaluations instead of the reference's k + 2."""
-        mlp, steps, do_reg, inv_div, sums, reg_coef = self.mlp, self.steps, self.do_reg, self.inv_div, self.sums, self.reg_coef
+        mlp, do_reg, inv_div, sums, reg_coef = self.mlp, self.do_reg, self.inv_div, self.sums, self.reg_coef
         gW_reg, gb_reg = self.gW_reg, self.gb_reg
         n_pix, shape = (b1 - b0) * self.HW, (b1 - b0, self.H, self.W)
         ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
@@ -275,7 +328,13 @@ class _SfStep:
     def warp_whole_batch(self):
         """ONE warp+loss launch over all pairs.  The batch-global normaliser is then known before the scene-flow network's
         backward: all-reduce the four loss sums now and hand inv to the backward kernels as a device scalar."""
-        self.warp(0, self.B)
+        if self.mixed and self.opt.weight_steps:
+            # per-pair weights: one launch per gap group, its flow_mul / disp_mul times the group's step count (the gradients
+            # carry the weight); the loss sums are added as they are -- the logged losses are the unweighted ones (:226)
+            for b0, b1, st in self.groups:
+                self.warp(b0, b1, self.group_mul(st))
+        else:
+            self.warp(0, self.B)
         scalars, inv = self.normaliser(self.sums[:4])
         ops.scale_add(self.g_d1_main, self.g_d1_main, scale_ptr=inv)
         return scalars, inv
@@ -283,10 +342,10 @@ class _SfStep:
     def run_whole_batch(self):
         """Schedule 1 of 3 (each returns (scalars, inv)): the forward stashes of the whole batch stay alive until the backward."""
         gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
-        kept = [self.mlp_forward_chunk(b0, b1, keep_first=bool(self.do_reg)) for b0, b1 in self.chunks]
+        kept = [self.mlp_forward_chunk(b0, b1, n, keep_first=bool(self.do_reg)) for b0, b1, n in self.chunks]
         scalars, inv = self.warp_whole_batch()
-        for (b0, b1), (st, first) in zip(self.chunks, kept):
-            self.merged_backward_chunk(b0, b1, st, first, gst, inv)
+        for (b0, b1, n), (st, first) in zip(self.chunks, kept):
+            self.merged_backward_chunk(b0, b1, n, st, first, gst, inv)
             del st[:]
         del kept
         parallel.all_reduce_sum_(self.sums[4:])
@@ -302,13 +361,13 @@ class _SfStep:
         evaluations are bit-identical: the forward kernel is deterministic).  --mlp_recompute 0 restores the late schedule."""
         gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
         with ops.counting_recomputed():          # the stashed evaluations below are the ones the backward needs
-            for b0, b1 in self.chunks:
-                self.mlp_forward_chunk(b0, b1, with_stash=False)
+            for b0, b1, n in self.chunks:
+                self.mlp_forward_chunk(b0, b1, n, with_stash=False)
         scalars, inv = self.warp_whole_batch()
-        for b0, b1 in self.chunks:
+        for b0, b1, n in self.chunks:
             # the same evaluations again, stashed; their flow goes to a scratch accumulator (sf_all already holds it)
-            st, first = self.mlp_forward_chunk(b0, b1, keep_first=bool(self.do_reg), acc=torch.zeros_like(self.sf_all[b0:b1]))
-            self.merged_backward_chunk(b0, b1, st, first, gst, inv)
+            st, first = self.mlp_forward_chunk(b0, b1, n, keep_first=bool(self.do_reg), acc=torch.zeros_like(self.sf_all[b0:b1]))
+            self.merged_backward_chunk(b0, b1, n, st, first, gst, inv)
             del st[:], first
         parallel.all_reduce_sum_(self.sums[4:])
         return scalars, inv
@@ -318,10 +377,10 @@ class _SfStep:
         after the last chunk; main-path gradients stay un-normalised in buffers of their own, the regulariser runs apart."""
         gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
         self.g_d1_reg = torch.zeros_like(self.depth_1) if self.do_reg else None
-        for b0, b1 in self.chunks:
-            st = self.mlp_forward_chunk(b0, b1)
-            self.warp(b0, b1)
-            self.mlp_backward_chunk(b0, b1, st, gst)
+        for b0, b1, n in self.chunks:
+            st = self.mlp_forward_chunk(b0, b1, n)
+            self.warp(b0, b1, self.group_mul(n))
+            self.mlp_backward_chunk(b0, b1, n, st, gst)
             del st
             if self.do_reg:
                 self.reg_chunk(b0, b1, gst)
@@ -439,6 +498,8 @@ class Model(NetInterface):
         self._keep_denied = {}       # slot key -> step at which it was last denied / trimmed (retried 16 steps later)
         self._step_no = 0
         self.warm = False
+        self.steps, self.steps_per_pair = 0, []     # Euler steps of the last training batch: largest count / per pair (caller's order)
+        self._inv_perm = None        # set while self._input holds a batch in gap-grouped order (mixed frame gaps)
 
     # flat parameter buffers + fused Adam (or SGD, --optim sgd) replace the two torch.optim objects (:113-115)
     def to(self, device):
@@ -476,6 +537,10 @@ class Model(NetInterface):
         if parallel.is_distributed():      # every rank starts from rank 0's weights (train.py:290-292)
             parallel.broadcast_(self._flat_depth.flat)
             parallel.broadcast_(self._flat_sf.flat)
+
+    def load_batch(self, batch, include_gt=True):
+        self._inv_perm = None        # a freshly loaded batch is in the caller's order
+        super().load_batch(batch, include_gt)
 
     # ------------------------------------------------------------------------------------
     def _depth_forward(self, img, frame_ids):
@@ -710,11 +775,23 @@ class Model(NetInterface):
                 return cc
         return min(16, B)
 
+    def _gap_plan(self, steps_per_pair, HW, with_reg):
+        """gap_plan with this model's stash sizes and --mlp_stash_gb (MLP path only)."""
+        return gap_plan(steps_per_pair, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
+                        self._mlp.gstash_floats(HW) * 4, with_reg)
+
     def _phase2_bytes(self, B, HW, steps, do_reg):
         """What phase 2 will allocate (the room phase 1 leaves free): the MLP stashes of the whole batch if they fit
         --mlp_whole_batch_gb, else those of ONE chunk (late-normaliser / recompute schedules).  (Rounds 1-5 reserved
         min(whole batch, the ceiling) in the chunked case too: 160 GB for 48 GB of stashes at BASELINE configs[4]'s 64 pairs,
-        and not one depth-net slot was kept there.)"""
+        and not one depth-net slot was kept there.)  steps: an int, or the per-pair counts of a mixed batch."""
+        if not isinstance(steps, int):
+            if self._mlp is None:        # --use_cnn: one U-Net evaluation per pair and Euler step, + the regulariser's
+                evals = sum(steps) + (B if do_reg else 0)
+                return HW * self._cnn_bytes_per_px() * evals + 24 * B * HW * 4
+            plan = self._gap_plan(steps, HW, do_reg)
+            fits = plan['whole_bytes'] <= float(getattr(self.opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
+            return (plan['whole_bytes'] if (len(plan['chunks']) == 1 or fits) else plan['chunk_bytes']) + 24 * B * HW * 4
         Bc0 = self._pairs_per_chunk(B, HW, steps, do_reg)
         if self._mlp is None:        # --use_cnn: autograd state of the U-Net, per pixel and evaluation (measured)
             return B * HW * self._cnn_bytes_per_px() * (steps + (1 if do_reg else 0)) + 24 * B * HW * 4
@@ -803,6 +880,53 @@ class Model(NetInterface):
         gap = torch.mean(ts2.float() - ts1.float())
         return int((gap / time_step).round().long().item()), time_step
 
+    def _steps_per_pair(self, batch):
+        """(steps, steps_per_pair, time_step): the Euler steps of every pair, round((ts2[b] - ts1[b]) / time_step) -- time
+        stamps are constant per pair (datasets/davis_sequence.py) --, in the caller's order, with ONE device-to-host read.
+        steps: for a uniform batch exactly _integer_steps' value (the rounded mean gap, :248-250), else the largest count."""
+        ts1, ts2, step = batch['time_stamp_1'], batch['time_stamp_2'], batch['time_step']
+        time_step = float(step.squeeze().item()) if torch.is_tensor(step) else float(step)
+        d = ts2.float() - ts1.float()
+        B = int(d.shape[0]) if d.dim() > 0 else 1
+        both = torch.cat([(d.reshape(B, -1)[:, 0] / time_step).round(), (torch.mean(d) / time_step).round().reshape(1)]).tolist()
+        if not all(np.isfinite(both)):          # (the uniform path keeps whatever it does with such time stamps)
+            steps = self._integer_steps(batch)[0]
+            return steps, [steps] * B, time_step
+        per_pair, mean = [int(v) for v in both[:B]], int(both[B])
+        if all(v == per_pair[0] for v in per_pair):
+            return mean, [mean] * B, time_step
+        for b, v in enumerate(per_pair):
+            if v < 1:
+                raise ValueError('pair %d of a batch that mixes frame gaps has time stamps %g frames apart (%d Euler steps): '
+                                 'every pair needs at least one' % (b, float(ts2[b].flatten()[0] - ts1[b].flatten()[0]) / time_step, v))
+        return max(per_pair), per_pair, time_step
+
+    def _group_input(self, perm):
+        """Bring the loaded batch (self._input) into gap-grouped order: ONE dvd_gather_pairs launch over every per-pair
+        tensor.  The caller's batch dict is not touched; exports go back through the inverse (_caller_order)."""
+        inp = self._input
+        B = len(perm)
+        names = [n for n in self.input_names if torch.is_tensor(getattr(inp, n, None)) and getattr(inp, n).dim() > 0 and
+                 getattr(inp, n).shape[0] == B and getattr(inp, n).numel() > 0]
+        perm_dev = torch.tensor(perm, dtype=torch.int32).to(self.device, non_blocking=True)
+        for n, t in zip(names, ops.gather_pairs([getattr(inp, n) for n in names], perm_dev)):
+            setattr(inp, n, t)
+        inv = [0] * B
+        for j, b in enumerate(perm):
+            inv[b] = j
+        self._inv_perm = torch.tensor(inv, dtype=torch.int32).to(self.device, non_blocking=True)
+
+    def _caller_order(self, tensors):
+        """dict of per-pair GPU tensors of the last step, in its gap-grouped order -> the same in the caller's pair order."""
+        inv = getattr(self, '_inv_perm', None)
+        if inv is None:
+            return tensors
+        B = inv.numel()
+        keys = [k for k, v in tensors.items() if torch.is_tensor(v) and v.is_cuda and v.dim() > 0 and v.shape[0] == B]
+        out = dict(tensors)
+        out.update(zip(keys, ops.gather_pairs([tensors[k] for k in keys], inv)))
+        return out
+
     def _cnn_bytes_per_px(self):
         """Autograd state of ONE U-Net evaluation per pixel (--use_cnn): the measured value once a step has run; before that
         an a-priori figure that grows with the depth of the U-Net -- 2.6 KB per pixel was measured for n_down = 3 on the
@@ -815,8 +939,8 @@ class Model(NetInterface):
     def _pairs_per_chunk(self, B, HW, steps, with_reg):
         if self._mlp is None:            # --use_cnn: the whole batch goes through the U-Net at once
             return B
-        per_pair = self._mlp.stash_floats(HW) * 4 * max(steps, 2 if with_reg else 1) + self._mlp.gstash_floats(HW) * 4
-        return int(max(1, min(B, (self.opt.mlp_stash_gb * 2 ** 30) // per_pair)))
+        return pairs_per_chunk(B, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
+                               self._mlp.gstash_floats(HW) * 4, steps, with_reg)
 
     def _whole_batch_fits(self, B, Bc, HW, steps, with_reg):
         """Forward stashes of all B pairs + the backward / regulariser scratch of one chunk."""
@@ -848,21 +972,32 @@ class Model(NetInterface):
         for k, v in batch.items():                   # strip the DataLoader dimension (:177-179)
             if type(v) != list:
                 batch[k] = v.squeeze(0)
-        steps, time_step = self._integer_steps(batch)
-        self.steps = steps
+        steps, steps_pp, time_step = self._steps_per_pair(batch)
+        self.steps, self.steps_per_pair = steps, steps_pp
         self.load_batch(batch)
         inp = self._input
         B, _, H, W = inp.img_1.shape
         HW, dev = H * W, self.device
+        do_reg = opt.interp_steps > 0 and (not warm or opt.warm_reg) and opt.acc_mul > 0
+        # pairs of different frame gaps: everything below works on the batch in gap-grouped order (gap_plan), each group
+        # integrated over its own number of Euler steps; `plan_steps` is what the memory planner takes in place of `steps`
+        groups, chunks, plan_steps = None, None, steps
+        if any(v != steps_pp[0] for v in steps_pp):
+            if opt.use_cnn:
+                plan = gap_plan(steps_pp, 1.0, 1, 0, do_reg)
+            else:
+                plan = self._gap_plan(steps_pp, HW, do_reg)
+            groups, chunks, plan_steps = plan['groups'], plan['chunks'], sorted(steps_pp)
+            if plan['perm'] != list(range(B)):
+                self._group_input(plan['perm'])
         fid1, fid2 = self._frame_ids(inp)
 
         # ---- phase 1: depth maps; the autograd state of as many chunks as fit stays alive for phase 3 (kept slots),
         #      the rest is a no-graph forward that phase 3 recomputes
-        do_reg = opt.interp_steps > 0 and (not warm or opt.warm_reg) and opt.acc_mul > 0
         keeping = not (warm or not getattr(opt, 'depth_graphs', 1) or float(getattr(opt, 'depth_keep_gb', 150.0)) <= 0)
         if keeping and int(opt.depth_chunk) <= 0 and self._auto_chunk is None:
             # decided ONCE, at the first training step that keeps slots (graphs and slots are per chunk shape)
-            self._auto_chunk = self._pick_depth_chunk(B, HW, self._phase2_bytes(B, HW, steps, do_reg), dev)
+            self._auto_chunk = self._pick_depth_chunk(B, HW, self._phase2_bytes(B, HW, plan_steps, do_reg), dev)
         n_slots = -(-B // self._chunk())
         if not keeping:
             # (non-warm steps without kept slots: phase 3 recomputes every chunk's forward; a warm-up step has no depth-net backward)
@@ -870,13 +1005,13 @@ class Model(NetInterface):
                 depth_1 = self._depths_nograd(inp.img_1, fid1)
                 depth_2 = self._depths_nograd(inp.img_2, fid2)
         else:
-            mlp_need = self._phase2_bytes(B, HW, steps, do_reg)
+            mlp_need = self._phase2_bytes(B, HW, plan_steps, do_reg)
             depth_1 = self._depths_keep(inp.img_1, fid1, 0, mlp_need, 2 * n_slots)
             depth_2 = self._depths_keep(inp.img_2, fid2, n_slots, mlp_need, 2 * n_slots)
             self._trim_keep_slots(dev, mlp_need)
 
         # ---- phase 2: geometry + scene-flow network + losses, forward and backward (_SfStep)
-        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg)
+        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups)
         if opt.use_cnn:
             _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
             step.set_global_batch(n_global)
@@ -888,8 +1023,12 @@ class Model(NetInterface):
         # backward scratch, the warp+loss kernel runs once over all pairs (one launch of
         # B*H*W pixels fills the chip far better than B/Bc smaller ones); otherwise every
         # chunk gets its own warp+loss launch -- or, by default, the recompute schedule (_SfStep.run_recompute).
-        Bc = self._pairs_per_chunk(B, HW, steps, do_reg)
-        whole = Bc < B and self._whole_batch_fits(B, Bc, HW, steps, do_reg)
+        if chunks is None:
+            Bc = self._pairs_per_chunk(B, HW, steps, do_reg)
+            whole = Bc < B and self._whole_batch_fits(B, Bc, HW, steps, do_reg)
+        else:        # mixed gaps: "one chunk" is what Bc >= B says of a uniform batch
+            Bc = B if len(chunks) == 1 else max(b1 - b0 for b0, b1, _ in chunks)
+            whole = Bc < B and plan['whole_bytes'] <= float(getattr(opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
         recompute = Bc < B and not whole and bool(int(getattr(opt, 'mlp_recompute', 1)))
         # ranks may hold different batch sizes / frame gaps: agree on the schedule (early or late normaliser)
         # and on the size of the global batch before the first data-dependent collective
@@ -898,7 +1037,8 @@ class Model(NetInterface):
         late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B,
                                                                 self._may_capture_in_phase3(inp, n_slots))
         step.set_global_batch(n_global)
-        step.begin_mlp(Bc)
+        step.begin_mlp(Bc, chunks)
+        self._last_chunks = list(step.chunks)
         if late:
             scalars, inv = step.run_late()
         elif recompute:
@@ -993,7 +1133,7 @@ class Model(NetInterface):
         P1 = ops.unproject(step.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True).requires_grad_(True)
         ts = inp.time_stamp_1
         # the whole batch goes through the U-Net under autograd: fail early, with the numbers, instead of somewhere inside it
-        evals = steps + (1 if do_reg else 0)
+        evals = steps + (1 if do_reg else 0)        # (a mixed batch: its largest step count, an upper bound)
         need = B * HW * self._cnn_bytes_per_px() * evals
         free, _total = self._free_hbm(dev)
         if need > free:
@@ -1006,15 +1146,21 @@ class Model(NetInterface):
             warnings.warn(msg + ' (a-priori estimate: nothing has been measured yet, trying anyway)')
         mem0 = torch.cuda.memory_allocated(dev)
         with torch.enable_grad():
-            sf_acc, p, t, sf0 = None, P1, ts, None
-            for i in range(steps):
-                s_i = self._sf_net_cnn(p, t)
-                sf0 = s_i if i == 0 else sf0
-                sf_acc = s_i if sf_acc is None else sf_acc + s_i
-                p, t = p + s_i, t + time_step
+            accs, firsts = [], []
+            for b0, b1, n in step.groups:        # mixed frame gaps: the U-Net runs per gap group (one group otherwise)
+                whole = (b0, b1) == (0, B)
+                sf_acc, p, t, sf0 = None, (P1 if whole else P1[b0:b1]), (ts if whole else ts[b0:b1]), None
+                for i in range(n):
+                    s_i = self._sf_net_cnn(p, t)
+                    sf0 = s_i if i == 0 else sf0
+                    sf_acc = s_i if sf_acc is None else sf_acc + s_i
+                    p, t = p + s_i, t + time_step
+                accs.append(sf_acc)
+                firsts.append(sf0)
+            sf_acc, sf0 = (accs[0], firsts[0]) if len(accs) == 1 else (torch.cat(accs, 0), torch.cat(firsts, 0))
         # measured footprint of an evaluation (like _keep_per_px for the depth net's slots): the planner's next decisions
         # use it instead of the a-priori figure
-        self._cnn_px_measured = max(self._cnn_px_measured, (torch.cuda.memory_allocated(dev) - mem0) / float(B * HW * steps))
+        self._cnn_px_measured = max(self._cnn_px_measured, (torch.cuda.memory_allocated(dev) - mem0) / float(HW * sum(n * (b1 - b0) for b0, b1, n in step.groups)))
         step.sf_all = sf_acc.detach().contiguous()
         step.g_sf_all = g_sf = torch.empty_like(step.sf_all)
         scalars, inv = step.warp_whole_batch()
@@ -1080,8 +1226,11 @@ class Model(NetInterface):
             img_1 = img_2 = batch['img']
         output = {'batch_size': batch_size, 'img_1': img_1, 'img_2': img_2, **pred_all}
         if 'img' not in batch:
-            output['flow_1_2'] = self._input.flow_1_2.cpu().numpy()
-            output['flow_2_1'] = self._input.flow_2_1.cpu().numpy()
+            flows = {'flow_1_2': self._input.flow_1_2, 'flow_2_1': self._input.flow_2_1}
+            if flows['flow_1_2'].is_cuda and flows['flow_1_2'].shape[0] == batch_size:
+                flows = self._caller_order(flows)
+            output['flow_1_2'] = flows['flow_1_2'].cpu().numpy()
+            output['flow_2_1'] = flows['flow_2_1'].cpu().numpy()
             if 'depth_pred_1' in batch:
                 output['depth_nn_1'] = batch['depth_pred_1'].cpu().numpy()
         else:
@@ -1129,7 +1278,7 @@ class Model(NetInterface):
         pred['global_p1'] = dflow['global_p1'].squeeze(3).permute(0, 3, 1, 2)
         pred['sf_by_dep_1_2'] = dflow['sf_by_depth']
         pred['sf_loss_pp'] = torch.abs(dflow['sf_by_depth'].squeeze(3).permute(0, 3, 1, 2) - sf).sum(1)
-        return pred
+        return self._caller_order(pred)      # (a step that mixed frame gaps ran in gap-grouped order)
 
     @staticmethod
     def depth2disp(depth):

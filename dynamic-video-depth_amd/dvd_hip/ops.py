@@ -283,14 +283,14 @@ FLOP_CLASS_KERNELS = {          # mangled (rocpd database) and demangled (rocpro
 # same way (include/dvd_hip.h: dvd_byte_counters), and the kernel-name fragments tools/mfma_roofline.py joins a trace on.
 # They travel through the same snapshot / replay bookkeeping as the matrix classes, under their own keys.
 BYTE_CLASSES = ('bnrelu_fwd', 'bnrelu_bwd', 'upsample_fwd', 'upsample_bwd', 'amax', 'pack', 'pool', 'gconv_c8', 'elementwise',
-                'adam', 'geometry')
+                'adam', 'geometry', 'gather')
 BYTE_CLASS_KERNELS = {
     'bnrelu_fwd': ('bnrelu_fwd_kernel',), 'bnrelu_bwd': ('bnrelu_bwd', 'bn_mask', 'bnrelu_sum'),
     'upsample_fwd': ('upsample_bilinear_fwd',), 'upsample_bwd': ('upsample_bilinear_bwd', 'upsample_bwd'),
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel',),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 
@@ -351,6 +351,47 @@ def executed_flops():
     """Per kernel class: work launched eagerly plus work of replayed graphs, since process start (take differences)."""
     now = flop_counters()
     return {k: now[k] + REPLAYED[k] for k in ALL_CLASSES}
+
+
+def gather_pairs(tensors, perm, out=None):
+    """Batched pair permutation (dvd_gather_pairs): returns a list of new tensors with out_k[b] = tensors_k[perm[b]] for
+    every tensor of `tensors` (GPU tensors of any dtype that share their first dimension B), ONE launch per
+    _lib.GATHER_MAX tensors.  perm: a GPU integer tensor of B indices in [0, B) (int32 is used as it is), or a host
+    sequence of ints.  out: optional list of destination tensors (same shapes and dtypes, no overlap with the sources)."""
+    tensors = list(tensors)
+    if not tensors:
+        return []
+    B = int(tensors[0].shape[0]) if (torch.is_tensor(tensors[0]) and tensors[0].dim() > 0) else 0
+    srcs = []
+    for i, t in enumerate(tensors):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError('gather_pairs: tensor %d must be a GPU tensor (dvd_hip has no CPU path)' % i)
+        if t.dim() < 1 or t.shape[0] != B or t.numel() == 0:
+            raise RuntimeError('gather_pairs: tensor %d has shape %s, expected %d pairs in dim 0' % (i, tuple(t.shape), B))
+        srcs.append(t if t.is_contiguous() else t.contiguous())
+    if not torch.is_tensor(perm):
+        idx = [int(i) for i in perm]
+        if len(idx) != B or any(i < 0 or i >= B for i in idx):
+            raise RuntimeError('gather_pairs: perm must hold %d indices in [0, %d)' % (B, B))
+        perm = torch.tensor(idx, dtype=torch.int32).to(tensors[0].device, non_blocking=True)
+    if not perm.is_cuda or perm.numel() != B or perm.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError('gather_pairs: perm must be a GPU int32 / int64 tensor of %d indices' % B)
+    perm = perm.to(torch.int32).contiguous()
+    if out is None:
+        out = [torch.empty_like(t) for t in srcs]
+    else:
+        out = list(out)
+        if len(out) != len(srcs) or any(o.shape != t.shape or o.dtype != t.dtype or not o.is_cuda or not o.is_contiguous()
+                                        for o, t in zip(out, srcs)):
+            raise RuntimeError('gather_pairs: out must match the sources in number, shape and dtype (contiguous GPU tensors)')
+    lib = _lib.load()
+    for k0 in range(0, len(srcs), _lib.GATHER_MAX):
+        part = list(zip(srcs[k0:k0 + _lib.GATHER_MAX], out[k0:k0 + _lib.GATHER_MAX]))
+        items = (_lib.GatherItem * len(part))()
+        for it, (t, o) in zip(items, part):
+            it.src, it.dst, it.bytes_per_pair = t.data_ptr(), o.data_ptr(), t.numel() // B * t.element_size()
+        _lib.check(lib.dvd_gather_pairs(items, len(part), _p(perm), B, _stream()), 'dvd_gather_pairs')
+    return out
 
 
 def warp_loss_select(variant='tiled', tile=-1, px=0, strip_rows=0, strip_shape=0):

@@ -31,9 +31,15 @@ def make_batch(B, H, W, gap=1, seed=1234, rank=0, device='cpu', n_frames=100,
     behind_camera_pairs: the last k pairs get a camera-2 translation along +z
       large enough that every reprojected point has z < 1e-3, which exercises
       the behind-camera index mask (losses/scene_flow_projection.py:253-256).
+    gap: frames between the two images of a pair -- an int, or a sequence of B ints for a batch that mixes frame gaps
+      (camera motion, frame ids and time stamps of pair b follow gap[b]; everything drawn at random is the same
+      whatever the gaps).
     far_depth_frac is consumed by `make_depths` (pixels with depth 150 to
       exercise the [depth < 100] masks); kept here so one seed describes a case.
     """
+    if not isinstance(gap, int):
+        return _make_mixed_batch(B, H, W, [int(v) for v in gap], seed, rank, device, n_frames, behind_camera_pairs,
+                                 with_images)
     g = torch.Generator().manual_seed(seed + rank)
     K, Kinv = _intrinsics(H, W)
     batch = {}
@@ -80,6 +86,23 @@ def make_batch(B, H, W, gap=1, seed=1234, rank=0, device='cpu', n_frames=100,
     out = {}
     for k, v in batch.items():
         out[k] = v.to(device) if k != 'time_step' else v
+    return out
+
+
+def _make_mixed_batch(B, H, W, gaps, seed, rank, device, n_frames, behind_camera_pairs, with_images):
+    """make_batch for per-pair gaps: the gap-1 batch of the same seed with the gap-dependent entries of pair b (camera 2,
+    frame ids, time stamps) taken from the uniform batch of gap gaps[b]."""
+    if len(gaps) != B:
+        raise ValueError('make_batch: %d gaps for %d pairs' % (len(gaps), B))
+    out = make_batch(B, H, W, 1, seed, rank, device, n_frames, behind_camera_pairs, 0.0, with_images)
+    for gap in sorted(set(gaps)):
+        if gap == 1:
+            continue
+        sel = [b for b in range(B) if gaps[b] == gap]
+        # (the cheap entries only: no images, nothing is drawn twice for the keys copied here)
+        other = make_batch(B, H, W, gap, seed, rank, device, n_frames, behind_camera_pairs, 0.0, False)
+        for k in ('R_2', 'R_2_T', 't_2', 'frame_id_1', 'frame_id_2', 'time_stamp_1', 'time_stamp_2'):
+            out[k][sel] = other[k][sel]
     return out
 
 

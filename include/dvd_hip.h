@@ -82,7 +82,8 @@ enum {
   DVD_BYTES_ELEMENTWISE = 8,/* scale_add, mul_mask, acc_reg, cast_scale, depth head                                               */
   DVD_BYTES_ADAM = 9,       /* the fused optimiser step: param, grad(s), optimiser state in, param and state out (Adam or SGD)     */
   DVD_BYTES_GEOMETRY = 10,  /* unproject forward / backward                                                                       */
-  DVD_BYTES_CLASSES = 11
+  DVD_BYTES_GATHER = 11,    /* dvd_gather_pairs: every tensor of the table read once and written once, + the permutation          */
+  DVD_BYTES_CLASSES = 12
 };
 int dvd_byte_counters(double* out, int n, int reset);
 
@@ -622,6 +623,23 @@ int dvd_avgpool_fwd(const void* x, void* y, int f16, long long planes, int H, in
                     dvd_stream_t stream);
 int dvd_avgpool_bwd(const void* gy, void* gx, int f16, long long planes, int H, int W, int k, int stride, int pad,
                     dvd_stream_t stream);
+
+
+/* Batched pair permutation (an addition within ABI 8; no counterpart in the reference, which runs one pair per step): ONE launch
+ * that copies dst_k[b] = src_k[perm[b]], b < B, for every tensor k of a table of n_items <= DVD_GATHER_MAX per-pair tensors of
+ * any element type (bytes_per_pair = bytes of one index of dim 0).  A step that mixes frame gaps brings its batch into
+ * gap-grouped order with it, and its exports back into the caller's order with the inverse permutation
+ * (models/scene_flow_motion_field.py).  `items` is a HOST array (it travels in the kernel arguments), `perm` a DEVICE array of B
+ * ints in [0, B) -- an index outside the batch copies nothing for that pair.  16-byte accesses where a tensor's two base addresses
+ * and bytes_per_pair are multiples of 16, 4-byte accesses for multiples of 4, bytes otherwise.  src and dst of a tensor must not
+ * overlap; more than DVD_GATHER_MAX tensors, an overlap or a null pointer return DVD_EINVAL before anything is launched. */
+#define DVD_GATHER_MAX 32
+typedef struct dvd_gather_item {
+  const void* src;
+  void* dst;
+  long long bytes_per_pair;
+} dvd_gather_item;
+int dvd_gather_pairs(const dvd_gather_item* items, int n_items, const int* perm, int B, dvd_stream_t stream);
 
 #ifdef __cplusplus
 }
