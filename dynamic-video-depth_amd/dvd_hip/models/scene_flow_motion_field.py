@@ -31,7 +31,6 @@ lives on the device); `--use_cnn` swaps the MLP for the reference's U-Net scene-
 """
 import contextlib
 import os
-import sys
 import warnings
 from os import makedirs
 from os.path import join
@@ -45,53 +44,10 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
+from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 
 CAM_KEYS = ops.CAM_KEYS
-
-
-def head_room_fraction(world, total_bytes=None):
-    """Fraction of the device the memory planner leaves untouched: allocator fragmentation, and -- with several ranks --
-    whatever RCCL's collectives allocate while the step runs (its communicator is created BEFORE the planner reads the free
-    memory, parallel.init_from_env, so its channel / staging buffers are already counted as used).  Single process: 8 % (23 GB
-    of 288); data parallel: 10 % (29 GB), derated automatically -- the benchmark configuration still keeps both of its slots
-    (225 GB free - 60 GB slot >= 130 GB of stashes + 29 GB)."""
-    frac = 0.08 if world <= 1 else 0.10
-    # DVD_HEAD_ROOM_GB: an explicit head room in GB for runs that must leave more to other tenants of the device -- the 8-rank
-    # run's RCCL buffers when the communicator is created late, or a memory-capped deployment.  Absolute: it is divided by the
-    # device's REAL size (keep_slot_fits multiplies the fraction by that same total), not by a hard-coded 288 GB.
-    gb = _head_room_gb_from_env()
-    if gb:
-        if total_bytes is None:
-            total_bytes = torch.cuda.mem_get_info()[1] if torch.cuda.is_available() else 288 * 2 ** 30
-        frac = max(frac, min(0.9, gb * 2 ** 30 / float(total_bytes)))
-    return frac
-
-
-def _head_room_gb_from_env():
-    """DVD_HEAD_ROOM_GB, validated (also once at import: a malformed value must not first surface in the middle of step
-    planning)."""
-    raw = os.environ.get('DVD_HEAD_ROOM_GB')
-    if not raw:
-        return 0.0
-    try:
-        gb = float(raw)
-    except ValueError:
-        raise ValueError('DVD_HEAD_ROOM_GB=%r is not a number of gigabytes' % raw)
-    if not (0.0 <= gb < 1e5):
-        raise ValueError('DVD_HEAD_ROOM_GB=%r: expected a non-negative number of gigabytes' % raw)
-    return gb
-
-
-_head_room_gb_from_env()        # validate at import
-
-
-def keep_slot_fits(est, free, total, reserve, spare, kept, budget, head_room=0.08):
-    """May one more kept-activation slot of `est` bytes be captured?  `free` = HBM available to ordinary allocations,
-    `reserve` = what phase 2 (the MLP stashes) will allocate, `spare` = room for the recompute graph of a chunk that is not
-    kept (0 if this slot completes the step), `kept` = bytes already held by slots, `budget` = --depth_keep_gb.
-    `head_room` (head_room_fraction) of the device stays free."""
-    return kept + est <= budget and free - est >= reserve + head_room * total + spare
 
 
 def pairs_per_chunk(B, budget_bytes, stash_bytes, gstash_bytes, steps, with_reg):
@@ -138,16 +94,16 @@ class _SfStep:
     """Phase 2 of `Model._train_on_batch` (geometry + scene-flow network + losses, forward and backward): what its pieces share
     for ONE step, and the three schedules the MLP's activation stashes allow.  Per-chunk data (stashes, backward scratch) stay
     locals of the schedule methods: they bound the step's peak HBM; the object itself does not outlive the step."""
-    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups=None):
+    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups):
         opt = self.opt = model.opt
         self.inp, self.mlp, self.flat_sf, self.sf_grad_main = inp, model._mlp, model._flat_sf, model._sf_grad_main
         self.depth_1, self.depth_2 = depth_1, depth_2
         self.steps, self.time_step, self.warm, self.do_reg = steps, time_step, warm, do_reg
         B, _, H, W = inp.img_1.shape
         self.B, self.H, self.W, self.HW = B, H, W, H * W
-        # frame gaps: one group [(0, B, steps)] for a uniform batch; a mixed batch is in gap-grouped order (gap_plan) and
+        # frame gaps (gap_plan's groups): one group (0, B, steps) for a uniform batch; a mixed batch is in gap-grouped order and
         # `steps` is its largest count -- every chunk of the MLP path carries its own
-        self.groups = groups if groups else [(0, B, steps)]
+        self.groups = groups
         self.mixed = len(self.groups) > 1
         # --weight_steps (:189-190): a uniform batch scales flow_mul / disp_mul of the ONE warp+loss launch and divides the
         # logged loss again; a mixed batch weights per gap group (group_mul) and logs the unweighted sums as they are
@@ -178,16 +134,16 @@ class _SfStep:
         self.n_global = n_global
         self.reg_coef = self.opt.acc_mul / (3.0 * n_global * self.HW + 1e-6)
 
-    def begin_mlp(self, Bc, chunks=None):
-        """The MLP path's batch-wide tensors; Bc pairs go through the MLP kernels at once (Model._pairs_per_chunk).  chunks:
-        the (b0, b1, steps) list of a mixed batch (gap_plan: no chunk crosses a gap group), Bc its longest chunk."""
+    def begin_mlp(self, Bc, chunks):
+        """The MLP path's batch-wide tensors.  chunks: gap_plan's (b0, b1, steps) list -- what goes through the MLP kernels at
+        once; no chunk crosses a gap group --, Bc its longest chunk."""
         k, B, inp = self.flat_sf, self.B, self.inp
         self.gW_main = [k.view(self.sf_grad_main, 2 * i) for i in range(6)]
         self.gb_main = [k.view(self.sf_grad_main, 2 * i + 1) for i in range(6)]
         self.gW_reg = [k.view(k.grad, 2 * i) for i in range(6)]
         self.gb_reg = [k.view(k.grad, 2 * i + 1) for i in range(6)]
         self.Bc = Bc
-        self.chunks = list(chunks) if chunks else [(b0, min(B, b0 + Bc), self.steps) for b0 in range(0, B, Bc)]
+        self.chunks = list(chunks)
         self.P1_all = ops.unproject(self.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True)
         self.sf_all = torch.zeros(B, 3, self.H, self.W, device=self.depth_1.device)
         self.g_sf_all = torch.empty_like(self.sf_all)
@@ -488,15 +444,8 @@ class Model(NetInterface):
         self.visualizer = None
         self._flat_depth = self._flat_sf = None     # created by .to(device)
         self._optimizers = []
-        self._depth_graphs = {}
+        self._depth = None              # the depth net's DepthRunner (graphs, kept slots, their memory), created by .to(device)
         self._cnn_px_measured = 0.0     # --use_cnn: measured autograd bytes per pixel and U-Net evaluation
-        self._graph_flops = {}          # id(CUDAGraph) -> algorithmic work per kernel class, counted at its capture
-        self._keep_bytes = 0         # HBM held by kept-activation graph slots
-        self._keep_per_px = 0.0      # measured bytes per image pixel of a captured slot
-        self._auto_chunk = None      # --depth_chunk 0: images per slot, chosen at the first training step that keeps slots
-        self._pool_bytes = 0         # HBM reserved by the private pools of all captured graphs
-        self._keep_denied = {}       # slot key -> step at which it was last denied / trimmed (retried 16 steps later)
-        self._step_no = 0
         self.warm = False
         self.steps, self.steps_per_pair = 0, []     # Euler steps of the last training batch: largest count / per pair (caller's order)
         self._inv_perm = None        # set while self._input holds a batch in gap-grouped order (mixed frame gaps)
@@ -531,6 +480,7 @@ class Model(NetInterface):
                 # the scene-flow MLP's fp16 stash shares the forward monitor: a hidden activation beyond fp16's range (stored
                 # as Inf, contracted into the weight gradients) skips the step like a depth-net activation does
                 self._mlp.set_forward_monitor(self._gscale[6:7])
+        self._depth = DepthRunner(self.opt, self.net_depth, self._flat_depth, act_fp16=self._gscale is not None)
         if self._pending_optimizer_state is not None:      # checkpoint restored before .to() (train.py:256,279)
             self._apply_optimizer_state(self._pending_optimizer_state)
             self._pending_optimizer_state = None
@@ -542,333 +492,44 @@ class Model(NetInterface):
         self._inv_perm = None        # a freshly loaded batch is in the caller's order
         super().load_batch(batch, include_gt)
 
-    # ------------------------------------------------------------------------------------
-    def _depth_forward(self, img, frame_ids):
-        if self.opt.midas:
-            return self.net_depth(img)
-        return self.net_depth(img, frame_ids.long() if frame_ids is not None else None)
-
-    # -- HIP graphs for the depth net -------------------------------------------------------
-    # A MiDaS forward+backward of one chunk is ~2 000 kernel launches; 12 chunk passes per step make the
-    # step launch-bound on hosts with slower cores (rocprofv3: 1.95 s of kernels in a 2.8 s step on one
-    # box, 1.97 s wall on another).  With --depth_graphs 1 (default since the convolutions run on this
-    # package's own kernels: round 1's replay through MIOpen was erratic)
-    # each chunk shape is captured once (forward-only graph for phase 1, forward+backward graph for
-    # phase 3, static input / output / output-gradient buffers; parameter gradients accumulate in place
-    # into the flat gradient buffer) and replayed; anything that cannot be captured falls back to eager.
-    def _graph_key(self, kind, img):
-        return (kind, tuple(img.shape), bool(self.opt.midas))
-
-    def _capture_depth_graph(self, kind, img, fid):
-        """Returns (graph, static_in, static_out, static_gout) or None if capture is not possible."""
-        key = self._graph_key(kind, img)
-        if key in self._depth_graphs:
-            return self._depth_graphs[key]
-        entry = None
-        try:
-            import gc
-            gc.collect()        # graphs of discarded models must not be destroyed while this capture is open
-            static_in = img.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            grad_backup = self._flat_depth.grad.clone() if kind == 'fb' else None
-            with torch.cuda.stream(side):                  # warm-up outside the capture (allocator, MIOpen handles)
-                for _ in range(2):
-                    if kind == 'f':
-                        with torch.no_grad():
-                            self._depth_forward(static_in, fid)
-                    else:
-                        self._flat_depth.detach_grads()
-                        with torch.enable_grad():
-                            d = self._depth_forward(static_in, fid)
-                        d.backward(torch.zeros_like(d))
-                        self._flat_depth.absorb_grads()
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            # thread_local: calls made by other threads (the RCCL watchdog polling its events) do not invalidate
-            # the capture; the step also keeps collectives out of flight while a graph is being captured
-            mode = dict(capture_error_mode='thread_local')
-            conv.PACK_PLAN.extend()        # the packings the warm-up passes asked for: persistent buffers, two launches per step
-            ops.begin_capture()
-            f0 = ops.flop_counters()       # (bench.py roofline_mfma: the graph's algorithmic work, added at every replay)
-            if kind == 'f':
-                with torch.no_grad(), torch.cuda.graph(graph, **mode):
-                    static_out = self._depth_forward(static_in, fid)
-                entry = (graph, static_in, static_out, None)
-            else:
-                static_g = torch.zeros(img.shape[0], 1, img.shape[2], img.shape[3], device=img.device)
-                # parameter gradients: the engine hands over fresh tensors (no pre-attached .grad) and ONE multi-tensor add
-                # per chunk, captured with the rest, folds them into the flat buffer -- ~620 tiny accumulate kernels
-                # per replay otherwise
-                self._flat_depth.detach_grads()
-                with torch.cuda.graph(graph, **mode):
-                    with torch.enable_grad():
-                        static_out = self._depth_forward(static_in, fid)
-                    static_out.backward(static_g)
-                    self._flat_depth.absorb_grads()
-                entry = (graph, static_in, static_out, static_g)
-                self._flat_depth.grad.copy_(grad_backup)   # warm-up / capture passes used zero output gradients
-            self._graph_flops[id(graph)] = ops.flops_since(f0)
-            self._pool_bytes += self._pool_size(graph.pool(), img.device)
-        except Exception as e:                             # noqa: BLE001 -- capture is an optimisation only
-            warnings.warn('depth-net HIP graph capture failed (%s); running eagerly' % (str(e).splitlines()[0],))
-            torch.cuda.synchronize()
-            self._flat_depth.reattach_grads()
-            entry = None
-        self._depth_graphs[key] = entry
-        return entry
-
-    # -- kept activations -----------------------------------------------------------------------
-    # With this package's kernels a MiDaS forward keeps ~1 GB of autograd state per 384x672 image (round 1, through
-    # MIOpen/ATen: 3 GB), so the state of ALL chunks of a 48-pair step (95 GB) fits next to the MLP stashes: phase 1 runs
-    # every chunk's forward WITH its graph state into a slot of its own (forward graph + backward graph on one private
-    # memory pool), phase 3 replays the slot's backward graph -- the forward is computed once per step instead of twice.
-    def _keep_slot(self, slot, chunk, fid, reserve_bytes, last_and_all_kept=False):
-        key = ('keep', slot, tuple(chunk.shape), bool(self.opt.midas))
-        if key in self._depth_graphs:
-            entry = self._depth_graphs[key]
-            # a slot that was denied (or trimmed) for lack of room is tried again every 16 steps: one transient
-            # low-memory moment must not pin its chunk to the recompute path for the rest of the run
-            if entry is not None or self._step_no - self._keep_denied.get(key, self._step_no) < 16:
-                return entry
-            del self._depth_graphs[key]
-        # slots captured for another chunk shape at this position (the last, smaller batch of an epoch) hold HBM this
-        # shape needs: release them
-        for k in [k for k, v in self._depth_graphs.items() if k[0] == 'keep' and k[1] == slot and k != key and v is not None]:
-            self._keep_bytes -= self._depth_graphs[k][5]
-            self._pool_bytes -= self._depth_graphs[k][5]
-            del self._depth_graphs[k]
-        entry = None
-        # bytes a slot will hold: measured on the slots captured so far (per image and pixel), a-priori figure (MiDaS with
-        # fused epilogues: ~4.1 KB per pixel, ~2.2 KB with fp16 activations) for the first one, + packed weights
-        n_px = chunk.shape[0] * chunk.shape[2] * chunk.shape[3]
-        est = int(n_px * self._slot_bytes_per_px() + 1.5 * 2 ** 30)
-        free, total = self._free_hbm(chunk.device)
-        budget = float(getattr(self.opt, 'depth_keep_gb', 150.0)) * 2 ** 30
-        # room that must stay free: the MLP stashes of phase 2 + 8 % head room + (unless this is the last slot of a step
-        # whose other slots are all kept) the pool of the forward+backward recompute graph a non-kept chunk will need
-        # (the recompute graph of a non-kept chunk frees its activations as its backward proceeds: its pool measures 0.26-0.31
-        #  of a kept slot's -- 8.0 vs 25.6 GB for 16 hourglass images, 9.7 vs 37.9 GB for 16 MiDaS images at 768x1344 -- so half
-        #  the slot's estimate is room enough; rounds 4-5 asked for all of it and kept one slot fewer)
-        spare = 0 if last_and_all_kept else est // 2
-        if os.environ.get('DVD_KEEP_DEBUG'):
-            print('keep slot %d: est %.1f GB, free %.1f, reserve %.1f + %.1f + spare %.1f, kept so far %.1f, pools %.1f' % (
-                slot, est / 2 ** 30, free / 2 ** 30, reserve_bytes / 2 ** 30,
-                head_room_fraction(parallel.world_size(), total) * total / 2 ** 30, spare / 2 ** 30,
-                self._keep_bytes / 2 ** 30, self._pool_bytes / 2 ** 30), file=sys.stderr, flush=True)
-        hr = head_room_fraction(parallel.world_size(), total)
-        if not keep_slot_fits(est, free, total, reserve_bytes, spare, self._keep_bytes, budget, hr):
-            self._depth_graphs[key] = None
-            self._keep_denied[key] = self._step_no
-            return None
-        try:
-            import gc
-            gc.collect()
-            static_in = chunk.clone()
-            grad_backup = self._flat_depth.grad.clone()
-            if not any(k[0] == 'keep' and v is not None for k, v in self._depth_graphs.items()):
-                side = torch.cuda.Stream()                 # warm-up outside the capture (allocator, handles), once
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._flat_depth.detach_grads()
-                        with torch.enable_grad():
-                            d = self._depth_forward(static_in, fid)
-                        d.backward(torch.zeros_like(d))
-                        self._flat_depth.absorb_grads()
-                        del d
-                torch.cuda.current_stream().wait_stream(side)
-            mode = dict(capture_error_mode='thread_local')
-            pool = torch.cuda.graph_pool_handle()
-            g_f, g_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            conv.PACK_PLAN.extend()
-            ops.begin_capture()
-            f0 = ops.flop_counters()
-            with torch.cuda.graph(g_f, pool=pool, **mode):
-                with torch.enable_grad():
-                    static_out = self._depth_forward(static_in, fid)
-            self._graph_flops[id(g_f)] = ops.flops_since(f0)
-            static_g = torch.zeros(chunk.shape[0], 1, chunk.shape[2], chunk.shape[3], device=chunk.device)
-            self._flat_depth.detach_grads()
-            ops.begin_capture()         # its own generation: g_b's scalars are zero-filled by g_b's replay
-            f0 = ops.flop_counters()
-            with torch.cuda.graph(g_b, pool=pool, **mode):
-                static_out.backward(static_g)
-                self._flat_depth.absorb_grads()
-            self._graph_flops[id(g_b)] = ops.flops_since(f0)
-            self._flat_depth.grad.copy_(grad_backup)
-            used = self._pool_size(pool, chunk.device)
-            self._keep_bytes += used
-            self._pool_bytes += used
-            self._keep_per_px = max(self._keep_per_px, used / float(n_px))
-            entry = (g_f, g_b, static_in, static_out, static_g, used)
-        except Exception as e:                             # noqa: BLE001 -- an optimisation only
-            warnings.warn('keeping the depth net\'s activations in HIP graphs failed (%s); recomputing' % (str(e).splitlines()[0],))
-            torch.cuda.synchronize()
-            self._flat_depth.reattach_grads()
-            entry = None
-        self._depth_graphs[key] = entry
-        return entry
-
-    @staticmethod
-    def _pool_size(pool_id, device):
-        """Bytes of the caching allocator's segments that belong to a graph's private pool (the reserved-bytes counter does
-        not tell: a new pool may be carved from memory the process had reserved before)."""
-        pid = tuple(pool_id)
-        return sum(seg['total_size'] for seg in torch.cuda.memory_snapshot()
-                   if tuple(seg.get('segment_pool_id', (0, 0))) == pid and seg.get('device', device.index) == device.index)
-
-    def _free_hbm(self, device):
-        """(bytes available to ordinary allocations: free on the device + cached by the allocator, total bytes).  The
-        private pools of captured graphs are reserved but not `allocated` once the capture's temporaries are released, and
-        they are NOT reusable: they are subtracted."""
-        free, total = torch.cuda.mem_get_info(device)
-        cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device) - self._pool_bytes
-        return free + max(0, cached), total
-
-    def _trim_keep_slots(self, device, need_bytes):
-        """After phase 1: if the slots left less than phase 2 needs (a first slot larger than its a-priori estimate),
-        give the newest slots back -- their chunks take the recompute path in phase 3, the step stays correct."""
-        free, total = self._free_hbm(device)
-        if os.environ.get('DVD_KEEP_DEBUG'):
-            print('after phase 1: free %.1f GB, phase 2 needs %.1f, pools %.1f' % (free / 2 ** 30, need_bytes / 2 ** 30,
-                                                                               self._pool_bytes / 2 ** 30), file=sys.stderr, flush=True)
-        kept = [k for k, v in self._depth_graphs.items() if k[0] == 'keep' and v is not None]
-        while kept and free < need_bytes + 0.5 * head_room_fraction(parallel.world_size(), total) * total:
-            key = kept.pop()
-            self._keep_bytes -= self._depth_graphs[key][5]
-            self._pool_bytes -= self._depth_graphs[key][5]
-            self._depth_graphs[key] = None
-            self._keep_denied[key] = self._step_no
-            import gc
-            gc.collect()
-            free, total = self._free_hbm(device)
-
+    # -- read-only views of the depth-net runner (the benchmark and the tools report them); valid before .to() as well ----
     def _chunk(self):
-        """Images per depth-net chunk: --depth_chunk, or (0 = auto) what _pick_depth_chunk chose at the first training step."""
-        c = int(getattr(self.opt, 'depth_chunk', 48))
-        return max(1, c if c > 0 else int(self._auto_chunk or 48))
+        """Images per depth-net chunk (depth_runner.images_per_chunk)."""
+        return self._depth.chunk() if self._depth is not None else images_per_chunk(self.opt)
 
-    def _slot_bytes_per_px(self):
-        """Autograd state a kept slot holds per image pixel: measured on the slots captured so far, else an a-priori figure
-        (as measured in round 6: MiDaS with fused epilogues 4.8 KB -- 55.8 GB per 48 images at 384x672 --, 2.5 KB with fp16
-        activations, the hourglass 6.7 KB; rounds 4-5 assumed 4.4 / 2.4 KB).  The hourglass with fp16 activations: 4.9 KB
-        (Model._keep_per_px after two steps of 48 pairs at 384x672 with 16-image slots on MI355X: 4 878 bytes, fp32 6 657)."""
-        if self.opt.midas:
-            apriori = 2500.0 if self._gscale is not None else 4900.0
+    @property
+    def _pool_bytes(self):
+        return self._depth.pool_bytes if self._depth is not None else 0
+
+    @property
+    def _depth_graphs(self):
+        return self._depth.graphs if self._depth is not None else {}
+
+    # ------------------------------------------------------------------------------------
+    def _plan_step(self, steps_per_pair, HW, do_reg):
+        """The ONE plan of a step, uniform gaps or mixed: gap_plan with this model's stash sizes and --mlp_stash_gb, and
+          reserve  what phase 2 will allocate (the room phase 1 leaves free): the MLP stashes of the whole batch if they are one
+                   chunk or fit --mlp_whole_batch_gb, else those of ONE chunk (late-normaliser / recompute schedules).  (Rounds
+                   1-5 reserved min(whole batch, the ceiling) in the chunked case too: 160 GB for 48 GB of stashes at BASELINE
+                   configs[4]'s 64 pairs, and not one depth-net slot was kept there.)
+          Bc       the longest chunk (B if there is one chunk);
+          whole    several chunks, but the forward stashes of the whole batch fit and stay alive until the backward."""
+        B = len(steps_per_pair)
+        if self._mlp is None:
+            # --use_cnn: the whole batch goes through the U-Net at once (the plan gives the gap groups only); its autograd
+            # state per pixel and evaluation is measured: one evaluation per pair and Euler step, + the regulariser's
+            plan = gap_plan(steps_per_pair, 1.0, 1, 0, do_reg)
+            need = HW * self._cnn_bytes_per_px() * (sum(steps_per_pair) + (B if do_reg else 0))
         else:
-            apriori = 4900.0 if self._gscale is not None else 6700.0
-        return max(apriori, self._keep_per_px)
-
-    def _pick_depth_chunk(self, B, HW, mlp_need, device):
-        """--depth_chunk 0: the largest of 48 / 24 / 16 images per slot for which EVERY slot of the step is expected to fit
-        beside phase 2's allocations (then nothing is recomputed, and larger launches are a little faster: 16 / 24 / 48
-        measured 0.840 / 0.843 / 0.851 iters/s); if no size fits, the finest -- slots are kept one by one, so smaller slots
-        keep more of the batch (hourglass at 384x672: one of two 48-image slots, or all six 16-image ones)."""
-        free, total = self._free_hbm(device)
-        budget = float(getattr(self.opt, 'depth_keep_gb', 150.0)) * 2 ** 30
-        avail = min(budget, free - mlp_need - head_room_fraction(parallel.world_size(), total) * total)
-        per_img = HW * self._slot_bytes_per_px()
-        for c in (48, 24, 16):
-            cc = min(c, B)
-            if 2 * B * per_img + 2 * (-(-B // cc)) * 1.5 * 2 ** 30 <= avail:
-                return cc
-        return min(16, B)
-
-    def _gap_plan(self, steps_per_pair, HW, with_reg):
-        """gap_plan with this model's stash sizes and --mlp_stash_gb (MLP path only)."""
-        return gap_plan(steps_per_pair, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
-                        self._mlp.gstash_floats(HW) * 4, with_reg)
-
-    def _phase2_bytes(self, B, HW, steps, do_reg):
-        """What phase 2 will allocate (the room phase 1 leaves free): the MLP stashes of the whole batch if they fit
-        --mlp_whole_batch_gb, else those of ONE chunk (late-normaliser / recompute schedules).  (Rounds 1-5 reserved
-        min(whole batch, the ceiling) in the chunked case too: 160 GB for 48 GB of stashes at BASELINE configs[4]'s 64 pairs,
-        and not one depth-net slot was kept there.)  steps: an int, or the per-pair counts of a mixed batch."""
-        if not isinstance(steps, int):
-            if self._mlp is None:        # --use_cnn: one U-Net evaluation per pair and Euler step, + the regulariser's
-                evals = sum(steps) + (B if do_reg else 0)
-                return HW * self._cnn_bytes_per_px() * evals + 24 * B * HW * 4
-            plan = self._gap_plan(steps, HW, do_reg)
+            plan = gap_plan(steps_per_pair, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
+                            self._mlp.gstash_floats(HW) * 4, do_reg)
+            one = len(plan['chunks']) == 1
             fits = plan['whole_bytes'] <= float(getattr(self.opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
-            return (plan['whole_bytes'] if (len(plan['chunks']) == 1 or fits) else plan['chunk_bytes']) + 24 * B * HW * 4
-        Bc0 = self._pairs_per_chunk(B, HW, steps, do_reg)
-        if self._mlp is None:        # --use_cnn: autograd state of the U-Net, per pixel and evaluation (measured)
-            return B * HW * self._cnn_bytes_per_px() * (steps + (1 if do_reg else 0)) + 24 * B * HW * 4
-        stash, gstash = self._mlp.stash_floats(HW) * 4, self._mlp.gstash_floats(HW) * 4
-        if Bc0 >= B or self._whole_batch_fits(B, Bc0, HW, steps, do_reg):
-            need = B * steps * stash + min(Bc0, B) * (gstash + (stash if (do_reg and steps == 1) else 0))
-        else:
-            need = Bc0 * (stash * max(steps, 2 if do_reg else 1) + gstash)
-        return need + 24 * B * HW * 4
-
-    def _depths_keep(self, img, frame_ids, slot0, reserve_bytes, n_slots_total):
-        """Depth maps of phase 1 with the autograd state of as many chunks as fit kept for phase 3."""
-        out = []
-        c = self._chunk()
-        for ci, b0 in enumerate(range(0, img.shape[0], c)):
-            fid = frame_ids[b0:b0 + c] if frame_ids is not None else None
-            chunk = img[b0:b0 + c]
-            others_kept = all(v is not None for k, v in self._depth_graphs.items() if k[0] == 'keep') and \
-                sum(1 for k in self._depth_graphs if k[0] == 'keep') == n_slots_total - 1
-            e = self._keep_slot(slot0 + ci, chunk, fid, reserve_bytes, others_kept) if self._use_graphs(chunk, fid) else None
-            if e is not None:
-                e[2].copy_(chunk)
-                conv.PACK_PLAN.ensure_current()      # (packed weights follow the optimiser: two launches after a step)
-                e[0].replay()
-                ops.note_replay(self._graph_flops.get(id(e[0])))
-                out.append(e[3].detach().clone())
-            else:
-                with ops.counting_recomputed():      # phase 3 runs this chunk's forward again (forward+backward graph)
-                    out.append(self._depths_nograd(chunk, fid))
-        return torch.cat(out, 0).contiguous()
-
-    def _use_graphs(self, img, frame_ids):
-        return bool(getattr(self.opt, 'depth_graphs', 1)) and (frame_ids is None or not self.opt.use_embedding)
-
-    def _depths_nograd(self, img, frame_ids):
-        out = []
-        c = self._chunk()
-        with torch.no_grad():
-            for b0 in range(0, img.shape[0], c):
-                fid = frame_ids[b0:b0 + c] if frame_ids is not None else None
-                chunk = img[b0:b0 + c]
-                g = self._capture_depth_graph('f', chunk, fid) if self._use_graphs(chunk, fid) else None
-                if g is not None:
-                    g[1].copy_(chunk)
-                    conv.PACK_PLAN.ensure_current()      # (packed weights follow the optimiser: two launches after a step)
-                    g[0].replay()
-                    ops.note_replay(self._graph_flops.get(id(g[0])))
-                    out.append(g[2].clone())
-                else:
-                    out.append(self._depth_forward(chunk, fid))
-        return torch.cat(out, 0).contiguous()
-
-    def _depth_backward(self, img, frame_ids, g_depth, slot0=None):
-        c = self._chunk()
-        for ci, b0 in enumerate(range(0, img.shape[0], c)):
-            fid = frame_ids[b0:b0 + c] if frame_ids is not None else None
-            chunk = img[b0:b0 + c]
-            kept = None if slot0 is None else self._depth_graphs.get(('keep', slot0 + ci, tuple(chunk.shape), bool(self.opt.midas)))
-            if kept is not None:                        # the forward of phase 1 left this chunk's graph state in its slot
-                kept[4].copy_(g_depth[b0:b0 + c])
-                conv.PACK_PLAN.ensure_current()      # (packed weights follow the optimiser: two launches after a step)
-                kept[1].replay()
-                ops.note_replay(self._graph_flops.get(id(kept[1])))
-                continue
-            g = self._capture_depth_graph('fb', chunk, fid) if self._use_graphs(chunk, fid) else None
-            if g is not None:
-                g[1].copy_(chunk)
-                g[3].copy_(g_depth[b0:b0 + c])
-                conv.PACK_PLAN.ensure_current()      # (packed weights follow the optimiser: two launches after a step)
-                g[0].replay()
-                ops.note_replay(self._graph_flops.get(id(g[0])))
-                continue
-            self._flat_depth.detach_grads()          # one multi-tensor accumulation per chunk instead of ~620 adds
-            with torch.enable_grad():
-                d = self._depth_forward(chunk, fid)
-            d.backward(g_depth[b0:b0 + c])
-            self._flat_depth.absorb_grads()
+            plan['Bc'] = B if one else max(b1 - b0 for b0, b1, _ in plan['chunks'])
+            plan['whole'] = fits and not one
+            need = plan['whole_bytes'] if (one or fits) else plan['chunk_bytes']
+        plan['reserve'] = need + 24 * B * HW * 4
+        return plan
 
     def _integer_steps(self, batch_or_input):
         """Euler steps of this batch = round(mean(ts2 - ts1) / time_step) (:248-250), recomputed every step:
@@ -936,26 +597,10 @@ class Model(NetInterface):
             return self._cnn_px_measured
         return 2600.0 * 1.5 * (1.0 + 0.15 * max(0, int(getattr(self.opt, 'n_down', 3)) - 3))
 
-    def _pairs_per_chunk(self, B, HW, steps, with_reg):
-        if self._mlp is None:            # --use_cnn: the whole batch goes through the U-Net at once
-            return B
-        return pairs_per_chunk(B, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
-                               self._mlp.gstash_floats(HW) * 4, steps, with_reg)
-
-    def _whole_batch_fits(self, B, Bc, HW, steps, with_reg):
-        """Forward stashes of all B pairs + the backward / regulariser scratch of one chunk."""
-        if self._mlp is None:
-            return True
-        stash, gstash = self._mlp.stash_floats(HW) * 4, self._mlp.gstash_floats(HW) * 4
-        # (merged backward: the regulariser's second evaluation needs a stash of its own only at gap 1; from gap 2 on it is
-        #  Euler evaluation 1)
-        need = B * steps * stash + Bc * (gstash + (stash if (with_reg and steps == 1) else 0))
-        return need <= float(getattr(self.opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
-
     # ------------------------------------------------------------------------------------
     def _train_on_batch(self, epoch, batch_ind, batch):
         opt = self.opt
-        self._step_no += 1
+        self._depth.begin_step()
         conv.set_grad_scale_state(self._gscale)      # the loss-scale state of THIS model's fp16 gradients (None: fp32 storage)
         if self._gscale is not None:
             # the forward monitor counts for THIS step's forward passes only: warm-up epochs, validation and inference fold
@@ -980,38 +625,30 @@ class Model(NetInterface):
         HW, dev = H * W, self.device
         do_reg = opt.interp_steps > 0 and (not warm or opt.warm_reg) and opt.acc_mul > 0
         # pairs of different frame gaps: everything below works on the batch in gap-grouped order (gap_plan), each group
-        # integrated over its own number of Euler steps; `plan_steps` is what the memory planner takes in place of `steps`
-        groups, chunks, plan_steps = None, None, steps
-        if any(v != steps_pp[0] for v in steps_pp):
-            if opt.use_cnn:
-                plan = gap_plan(steps_pp, 1.0, 1, 0, do_reg)
-            else:
-                plan = self._gap_plan(steps_pp, HW, do_reg)
-            groups, chunks, plan_steps = plan['groups'], plan['chunks'], sorted(steps_pp)
-            if plan['perm'] != list(range(B)):
-                self._group_input(plan['perm'])
+        # integrated over its own number of Euler steps; a uniform batch is ONE group in the caller's order
+        plan = self._plan_step(steps_pp, HW, do_reg)
+        if plan['perm'] != list(range(B)):
+            self._group_input(plan['perm'])
         fid1, fid2 = self._frame_ids(inp)
 
         # ---- phase 1: depth maps; the autograd state of as many chunks as fit stays alive for phase 3 (kept slots),
         #      the rest is a no-graph forward that phase 3 recomputes
         keeping = not (warm or not getattr(opt, 'depth_graphs', 1) or float(getattr(opt, 'depth_keep_gb', 150.0)) <= 0)
-        if keeping and int(opt.depth_chunk) <= 0 and self._auto_chunk is None:
-            # decided ONCE, at the first training step that keeps slots (graphs and slots are per chunk shape)
-            self._auto_chunk = self._pick_depth_chunk(B, HW, self._phase2_bytes(B, HW, plan_steps, do_reg), dev)
+        if keeping:
+            self._depth.choose_chunk(B, HW, plan['reserve'], dev)
         n_slots = -(-B // self._chunk())
         if not keeping:
             # (non-warm steps without kept slots: phase 3 recomputes every chunk's forward; a warm-up step has no depth-net backward)
             with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
-                depth_1 = self._depths_nograd(inp.img_1, fid1)
-                depth_2 = self._depths_nograd(inp.img_2, fid2)
+                depth_1 = self._depth.forward(inp.img_1, fid1)
+                depth_2 = self._depth.forward(inp.img_2, fid2)
         else:
-            mlp_need = self._phase2_bytes(B, HW, plan_steps, do_reg)
-            depth_1 = self._depths_keep(inp.img_1, fid1, 0, mlp_need, 2 * n_slots)
-            depth_2 = self._depths_keep(inp.img_2, fid2, n_slots, mlp_need, 2 * n_slots)
-            self._trim_keep_slots(dev, mlp_need)
+            depth_1 = self._depth.forward_keep(inp.img_1, fid1, 0, plan['reserve'], 2 * n_slots)
+            depth_2 = self._depth.forward_keep(inp.img_2, fid2, n_slots, plan['reserve'], 2 * n_slots)
+            self._depth.trim(dev, plan['reserve'])
 
         # ---- phase 2: geometry + scene-flow network + losses, forward and backward (_SfStep)
-        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups)
+        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg, plan['groups'])
         if opt.use_cnn:
             _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
             step.set_global_batch(n_global)
@@ -1023,21 +660,16 @@ class Model(NetInterface):
         # backward scratch, the warp+loss kernel runs once over all pairs (one launch of
         # B*H*W pixels fills the chip far better than B/Bc smaller ones); otherwise every
         # chunk gets its own warp+loss launch -- or, by default, the recompute schedule (_SfStep.run_recompute).
-        if chunks is None:
-            Bc = self._pairs_per_chunk(B, HW, steps, do_reg)
-            whole = Bc < B and self._whole_batch_fits(B, Bc, HW, steps, do_reg)
-        else:        # mixed gaps: "one chunk" is what Bc >= B says of a uniform batch
-            Bc = B if len(chunks) == 1 else max(b1 - b0 for b0, b1, _ in chunks)
-            whole = Bc < B and plan['whole_bytes'] <= float(getattr(opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
+        Bc, whole = plan['Bc'], plan['whole']
         recompute = Bc < B and not whole and bool(int(getattr(opt, 'mlp_recompute', 1)))
         # ranks may hold different batch sizes / frame gaps: agree on the schedule (early or late normaliser)
         # and on the size of the global batch before the first data-dependent collective
         # (also agreed across ranks: does ANY rank still have to capture a depth-net graph in phase 3?  Then every rank keeps
         #  the MLP-gradient all-reduce out of flight until after phase 3, so the order of collectives is the same everywhere)
-        late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B,
-                                                                self._may_capture_in_phase3(inp, n_slots))
+        will_capture = not warm and self._depth.backward_will_capture((0, inp.img_1), (n_slots, inp.img_2))
+        late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B, will_capture)
         step.set_global_batch(n_global)
-        step.begin_mlp(Bc, chunks)
+        step.begin_mlp(Bc, plan['chunks'])
         self._last_chunks = list(step.chunks)
         if late:
             scalars, inv = step.run_late()
@@ -1050,20 +682,6 @@ class Model(NetInterface):
     def _frame_ids(self, inp):
         """Frame ids of the two image sets (the hourglass's per-frame embedding); the MiDaS net takes none."""
         return (None, None) if self.opt.midas else (inp.frame_id_1, inp.frame_id_2)
-
-    def _may_capture_in_phase3(self, inp, n_slots):
-        """Will phase 3 still have to capture a depth-net graph -- is there a chunk that is not kept and has no recompute
-        graph yet?  Over the REAL chunk list of both image sets (a ragged last chunk has its own slot / graph keys)."""
-        if self.warm or not getattr(self.opt, 'depth_graphs', 1):
-            return False
-        cw = self._chunk()
-        for s0, img in ((0, inp.img_1), (n_slots, inp.img_2)):
-            for ci, b0 in enumerate(range(0, img.shape[0], cw)):
-                chunk = img[b0:b0 + cw]
-                kept = self._depth_graphs.get(('keep', s0 + ci, tuple(chunk.shape), bool(self.opt.midas)))
-                if kept is None and self._graph_key('fb', chunk) not in self._depth_graphs:
-                    return True
-        return False
 
     def _finish_step(self, epoch, batch_ind, batch, step, scalars, inv, early_norm, capturing, n_slots):
         """Phase 3 and the end of the step, for the MLP and the U-Net path alike.  early_norm: phase 2 has already normalised
@@ -1078,8 +696,8 @@ class Model(NetInterface):
             fid1, fid2 = self._frame_ids(inp)
             g_d1 = step.g_d1_main if early_norm else ops.scale_add(step.g_d1_main, step.g_d1_main, scale_ptr=inv, b=step.g_d1_reg)
             g_d2 = ops.scale_add(step.g_d2_main, step.g_d2_main, scale_ptr=inv)
-            self._depth_backward(inp.img_1, fid1, g_d1, slot0=0)
-            self._depth_backward(inp.img_2, fid2, g_d2, slot0=n_slots)
+            self._depth.backward(inp.img_1, fid1, g_d1, slot0=0)
+            self._depth.backward(inp.img_2, fid2, g_d2, slot0=n_slots)
             # 421 MB (MiDaS) in --grad_buckets large all-reduces, each bucket's Adam launch overlapping the next
             # bucket's reduction
             skip = None
@@ -1135,7 +753,7 @@ class Model(NetInterface):
         # the whole batch goes through the U-Net under autograd: fail early, with the numbers, instead of somewhere inside it
         evals = steps + (1 if do_reg else 0)        # (a mixed batch: its largest step count, an upper bound)
         need = B * HW * self._cnn_bytes_per_px() * evals
-        free, _total = self._free_hbm(dev)
+        free, _total = self._depth.free_hbm(dev)
         if need > free:
             msg = ('--use_cnn: the U-Net\'s autograd state for %d pairs at %dx%d (%d evaluations, %.0f B per pixel and '
                    'evaluation) needs %.1f GB, %.1f GB are free: use fewer pairs per step or a smaller --depth_keep_gb'
@@ -1158,7 +776,7 @@ class Model(NetInterface):
                 accs.append(sf_acc)
                 firsts.append(sf0)
             sf_acc, sf0 = (accs[0], firsts[0]) if len(accs) == 1 else (torch.cat(accs, 0), torch.cat(firsts, 0))
-        # measured footprint of an evaluation (like _keep_per_px for the depth net's slots): the planner's next decisions
+        # measured footprint of an evaluation (like DepthRunner.keep_per_px for the depth net's slots): the planner's next decisions
         # use it instead of the a-priori figure
         self._cnn_px_measured = max(self._cnn_px_measured, (torch.cuda.memory_allocated(dev) - mem0) / float(HW * sum(n * (b1 - b0) for b0, b1, n in step.groups)))
         step.sf_all = sf_acc.detach().contiguous()
@@ -1247,7 +865,7 @@ class Model(NetInterface):
             return self._train_pred()
         inp = self._input
         fid = inp.frame_id_1 if not self.opt.midas else None
-        depth = self._depths_nograd(inp.img, fid)
+        depth = self._depth.forward(inp.img, fid)
         P = ops.unproject(depth, inp.R_1, inp.t_1, inp.K_inv, planar=True)
         if self.opt.use_cnn:
             with torch.no_grad():

@@ -1,7 +1,7 @@
 """ops.new_scalar / the max|.| scalar pool across back-to-back HIP-graph captures.
 
 A scalar chunk lives in the private pool of the graph that allocated it, and its zero-fill node replays with that graph
-only.  Two captures in a row (the kept slots of Model._keep_slot: g_f, g_b, then the next slot's g_f, g_b with no eager
+only.  Two captures in a row (the kept slots of DepthRunner._capture_slot: g_f, g_b, then the next slot's g_f, g_b with no eager
 kernel call in between) must therefore never share a chunk, and a scalar tagged in one capture must not be served in
 another.  No GPU here: the capture state and the allocation are mocked."""
 import pytest

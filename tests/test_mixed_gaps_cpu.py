@@ -15,7 +15,7 @@ STASH, GSTASH = 5700 * 32 * 48, 3100 * 32 * 48          # bytes per pair: about 
 
 def _today(B, budget, steps, with_reg):
     """Chunk list and byte figures of a uniform-gap step as the model computed them before gaps could be mixed
-    (Model._pairs_per_chunk, _SfStep.begin_mlp, _whole_batch_fits, _phase2_bytes)."""
+    (the formulas of its uniform-gap planner path; the model now takes every step's figures from gap_plan)."""
     per_pair = STASH * max(steps, 2 if with_reg else 1) + GSTASH
     Bc = int(max(1, min(B, budget // per_pair)))
     chunks = [(b0, min(B, b0 + Bc)) for b0 in range(0, B, Bc)]
@@ -25,7 +25,7 @@ def _today(B, budget, steps, with_reg):
 
 
 @pytest.mark.parametrize('with_reg', [True, False])
-@pytest.mark.parametrize('steps', [1, 2, 4])
+@pytest.mark.parametrize('steps', [0, 1, 2, 4])
 @pytest.mark.parametrize('B,budget', [(48, 48.0 * GB), (48, 0.2 * GB), (7, 0.05 * GB), (5, 1e-6 * GB), (1, 1.0 * GB)])
 def test_an_all_equal_list_gives_todays_chunks_and_bytes(B, budget, steps, with_reg):
     from dvd_hip.models.scene_flow_motion_field import gap_plan, pairs_per_chunk

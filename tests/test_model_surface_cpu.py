@@ -88,14 +88,14 @@ def test_automatic_depth_chunk_choice():
     (DVD_KEEP_DEBUG logs): the headline line keeps two 48-image slots, the hourglass, frame gap 2 and configs[4] above 24 pairs
     take 16-image slots, configs[4] at 24 pairs one slot per image set."""
     from types import SimpleNamespace
-    from dvd_hip.models.scene_flow_motion_field import Model
+    from dvd_hip.models.depth_runner import DepthRunner
     G = 2 ** 30
 
     def pick(B, HW, mlp_need_gb, free_gb, midas=True, fp16=False, budget=150.0, measured=0.0):
-        fake = SimpleNamespace(opt=SimpleNamespace(depth_keep_gb=budget, midas=midas), _gscale=object() if fp16 else None,
-                               _keep_per_px=measured, _free_hbm=lambda dev: (free_gb * G, 288 * G))
-        fake._slot_bytes_per_px = lambda: Model._slot_bytes_per_px(fake)
-        return Model._pick_depth_chunk(fake, B, HW, mlp_need_gb * G, None)
+        runner = DepthRunner(SimpleNamespace(depth_keep_gb=budget, midas=midas), None, None, act_fp16=fp16)
+        runner.keep_per_px = measured
+        runner.free_hbm = lambda dev: (free_gb * G, 288 * G)
+        return runner.pick_chunk(B, HW, mlp_need_gb * G, None)
     hw, hw4 = 384 * 672, 768 * 1344
     assert pick(48, hw, 109.2, 286.4) == 48                              # headline: 96 images x 1.06 GB + two pools fit
     assert pick(48, hw, 109.2, 286.4, midas=False) == 16                 # hourglass: 6.2 KB per pixel, 154 GB for 96 images
@@ -105,6 +105,102 @@ def test_automatic_depth_chunk_choice():
     assert pick(32, hw4, 145.1, 283.8, fp16=True, budget=160.0) == 16    # ... at 32 pairs
     assert pick(24, hw4, 100.0, 284.0, fp16=True) == 24                  # ... at 24 pairs: one slot per image set
     assert pick(2, 32 * 48, 0.1, 280.0) == 2                             # tiny batches: one slot per image set
+
+
+def test_kept_slot_bookkeeping(monkeypatch):
+    """DepthRunner's slot bookkeeping, which the GPU tests never reach (they do not run out of memory): denial and the retry
+    16 steps later, the release of a slot of another chunk shape, the trim after phase 1 and the zero spare reserve of the slot
+    that completes a step.  The capture itself is stubbed (an entry of a given size), and so is the free memory."""
+    import torch
+    from types import SimpleNamespace
+    from dvd_hip.models import depth_runner
+    from dvd_hip.models.depth_runner import DepthRunner
+    monkeypatch.delenv('DVD_HEAD_ROOM_GB', raising=False)
+    monkeypatch.delenv('DVD_KEEP_DEBUG', raising=False)
+    G = 2 ** 30
+    total = 288 * G
+    head_room = 0.08 * total                                # one process
+    chunk, ragged = torch.zeros(2, 3, 8, 12), torch.zeros(1, 3, 8, 12)
+    est = int(2 * 8 * 12 * 4900.0 + 1.5 * G)                # a-priori MiDaS figure + packed weights; spare = est // 2
+
+    def make(free_gb, slot_bytes=10 * G, budget=150.0):
+        r = DepthRunner(SimpleNamespace(depth_keep_gb=budget, midas=True, depth_graphs=1, depth_chunk=2, use_embedding=False),
+                        None, None, act_fp16=False)
+        r.looked = 0
+        r.free = free_gb * G
+
+        def free_hbm(dev):
+            r.looked += 1
+            return r.free, total
+        r.free_hbm = free_hbm
+        r._capture_slot = lambda c, fid: depth_runner._Slot(None, None, None, None, None, slot_bytes)
+        return r
+
+    def key(slot, c):
+        return ('keep', slot, tuple(c.shape), True)
+
+    # 1. denial and retry: no room -> None is recorded; 15 steps of refusal without a look at the free memory; the 16th looks again
+    r = make(free_gb=20)
+    r.step_no = 1
+    assert r._keep_slot(0, chunk, None, 0, 2) is None                   # 20 GB free < 23 GB head room
+    assert r.graphs == {key(0, chunk): None} and r.denied == {key(0, chunk): 1} and r.looked == 1
+    r.free = 280 * G                                                    # room enough from now on: not looked at for 15 steps
+    for _ in range(15):
+        r.begin_step()
+        assert r._keep_slot(0, chunk, None, 0, 2) is None
+    assert r.looked == 1 and r.graphs == {key(0, chunk): None} and r.step_no == 16
+    r.begin_step()                                                      # step 17 = 16 steps after the denial
+    e = r._keep_slot(0, chunk, None, 0, 2)
+    assert e is not None and r.looked == 2 and r.graphs[key(0, chunk)] is e
+    assert r.keep_bytes == 10 * G and r.pool_bytes == 10 * G and r.keep_per_px == 10 * G / (2 * 8 * 12.0)
+    assert r._keep_slot(0, chunk, None, 0, 2) is e and r.looked == 2    # a live slot is served as it is
+
+    # 2. shape change: the slot of another chunk shape at this position is released BEFORE the fit test
+    r = make(free_gb=280)
+    r.pool_bytes = 3 * G                                                # (a recompute graph's pool: not a slot's)
+    assert r._keep_slot(0, chunk, None, 0, 4) is not None and r._keep_slot(1, chunk, None, 0, 4) is not None
+    assert (r.keep_bytes, r.pool_bytes) == (20 * G, 23 * G)
+    seen = []
+    r.free_hbm = lambda dev: (seen.append((sorted(r.graphs), r.keep_bytes, r.pool_bytes)), (0, total))[1]   # ... and no room
+    assert r._keep_slot(1, ragged, None, 0, 4) is None
+    assert seen == [([key(0, chunk)], 10 * G, 13 * G)]                  # key deleted, both counters down, when the memory is read
+    assert r.graphs == {key(0, chunk): r.graphs[key(0, chunk)], key(1, ragged): None} and r.graphs[key(0, chunk)] is not None
+    assert (r.keep_bytes, r.pool_bytes) == (10 * G, 13 * G) and r.denied == {key(1, ragged): 0}
+
+    # 3. trim: newest slots first, until free >= need + half the head room; released keys stay, as None, with a denial stamp
+    r = make(free_gb=280)
+    for slot in range(3):
+        assert r._keep_slot(slot, chunk, None, 0, 3) is not None
+    r.begin_step()
+    need = 100 * G
+    frees = [need + 0.5 * head_room - 1, need + 0.5 * head_room - 1, need + 0.5 * head_room]
+    r.free_hbm = lambda dev: (frees.pop(0), total)
+    r.trim(None, need)
+    assert not frees                                                    # read once at the start and once after every release
+    assert [k for k, v in r.graphs.items() if v is None] == [key(1, chunk), key(2, chunk)] and r.graphs[key(0, chunk)] is not None
+    assert r.denied == {key(1, chunk): 1, key(2, chunk): 1}
+    assert (r.keep_bytes, r.pool_bytes) == (10 * G, 10 * G)
+    r.free_hbm = lambda dev: (need + 0.5 * head_room, total)
+    r.trim(None, need)                                                  # enough is free: nothing is given back
+    assert r.graphs[key(0, chunk)] is not None and (r.keep_bytes, r.pool_bytes) == (10 * G, 10 * G)
+
+    # 4. the spare reserve (half a slot, for a recompute graph) is waived only for the slot that completes a step whose other
+    #    slots are all live: free memory that fits the slot without the spare but not with it tells the two apart
+    def last_slot(n_live, n_denied, n_slots_total):
+        r = make(free_gb=280, slot_bytes=2 * 8 * 12 * 1000)     # (measures less per pixel than the a-priori figure: est stays)
+        for slot in range(n_live):
+            assert r._keep_slot(slot, chunk, None, 0, 99) is not None
+        for slot in range(n_live, n_live + n_denied):
+            r.graphs[key(slot, chunk)] = None
+            r.denied[key(slot, chunk)] = r.step_no
+        r.free = est + head_room + est // 2 - 1
+        return r._keep_slot(n_live + n_denied, chunk, None, 0, n_slots_total) is not None
+    assert last_slot(3, 0, 4)                   # three live slots of four: this one completes the step
+    assert not last_slot(2, 1, 4)               # one of the others was denied: its chunk needs a recompute graph
+    assert not last_slot(3, 0, 5)               # not the last slot of its step
+    assert not last_slot(3, 0, 3)               # (more 'keep' keys than the step has other slots)
+    assert not last_slot(0, 0, 2)               # the first slot of two
+    assert last_slot(0, 0, 1)                   # a one-slot step
 
 
 def test_kept_activation_slot_planning_arithmetic():
