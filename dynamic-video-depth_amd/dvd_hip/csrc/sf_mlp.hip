@@ -649,6 +649,7 @@ struct BwdArgs {
   float* g_p;
   float* gW5;
   float* gb5;
+  float* part5;        // [gridDim.x][kDx5Partial]: the workgroups' shares of dW5 / db5 (the head of the dW workspace in gstash)
   PackLayout L;
   Geometry g;
   long long n_pix;
@@ -656,11 +657,15 @@ struct BwdArgs {
   float out_scale, gscale;
 };
 
+// floats per workgroup of the dX kernel: its share of dW5 [3][256], then of db5 [3] (+ 1 pad)
+constexpr int kDx5Partial = 3 * kWidth + 4;
+
 // LDS: X (gradient tile, split; at the end fp32 g_in [<= 256][64]) | gz5 [4][64] | gz5p [4][64] | w5 [3][256] | tmx [8] | dw5s [3][256]
 constexpr size_t kBwdLds = (size_t)kXBytes + 2 * 4 * kTM * 4 + 3 * kWidth * 4 + 8 * 4 + 3 * kWidth * 4;
 
 // NW as in the forward.  The input gradient and the gradient stash are bit-identical for NW = 4 and 8 (the last layer's
-// parameter gradients are float atomics over workgroups in both).
+// parameter gradients are per-workgroup shares summed in workgroup order by mlp_dx5_reduce_kernel: reproducible for one NW,
+// equal to rounding between the two, whose grids differ).
 template <bool S16, int NW>
 __global__ __launch_bounds__(64 * NW, DVD_MLP_DX_OCC) void mlp_bwd_dx_kernel(const BwdArgs a) {
   constexpr int RT = 8 / NW, NT = 64 * NW;
@@ -937,13 +942,38 @@ __global__ __launch_bounds__(64 * NW, DVD_MLP_DX_OCC) void mlp_bwd_dx_kernel(con
       }
     }
   }
-  // flush the last layer's parameter gradients
+  // this workgroup's share of the last layer's parameter gradients (every workgroup of the grid has at least one tile)
   __syncthreads();
-  for (int i = tid; i < 3 * kWidth; i += NT) unsafeAtomicAdd(a.gW5 + i, dw5s[i]);
+  float* part = a.part5 + (size_t)blockIdx.x * kDx5Partial;
+  for (int i = tid; i < 3 * kWidth; i += NT) part[i] = dw5s[i];
   {
     const float v = wave_sum(db5);
-    if (lane == 0 && w < 3) unsafeAtomicAdd(a.gb5 + w, v);
+    if (lane == 0 && w < 3) part[3 * kWidth + w] = v;
   }
+}
+
+// gW5[i] += sum_g part[g][i] (ascending g), gb5 likewise: the order of the sum is fixed, so dW5 / db5 are bitwise reproducible
+// (until this kernel every workgroup added its share with float atomics, in the order the workgroups happened to finish).
+// ONE atomic per element and launch: launches that share gW5 from different streams stay safe.
+struct Dx5ReduceArgs {
+  const float* part;
+  float* gW5;
+  float* gb5;
+  int G;
+};
+
+__global__ __launch_bounds__(256) void mlp_dx5_reduce_kernel(const Dx5ReduceArgs a) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= 3 * kWidth + 3) return;
+  const float* p = a.part + idx;
+  float s0 = 0.0f, s1 = 0.0f;
+  int g = 0;
+  for (; g + 1 < a.G; g += 2) {
+    s0 += p[(size_t)g * kDx5Partial];
+    s1 += p[(size_t)(g + 1) * kDx5Partial];
+  }
+  if (g < a.G) s0 += p[(size_t)g * kDx5Partial];
+  unsafeAtomicAdd(idx < 3 * kWidth ? a.gW5 + idx : a.gb5 + (idx - 3 * kWidth), s0 + s1);
 }
 
 // ==========================================================================================
@@ -1308,6 +1338,10 @@ int dvd_sf_mlp_bwd_dx(const dvd_mlp_desc* d, const void* packed, const void* sta
   a.gscale = gscale;
   const int nw = g_mlp_nw;
   const int grid = persistent_grid(a.n_tiles, DVD_MLP_DX_OCC, nw);
+  // the workgroups' dW5 / db5 shares: the head of the weight-gradient workspace behind the gradient tiles (dvd_sf_mlp_gstash_bytes;
+  // dvd_sf_mlp_bwd_dw, which runs after this call, overwrites it)
+  DVD_REQUIRE((size_t)grid * kDx5Partial <= (size_t)kHidden * kDwSlices * kDwPartial, "sf_mlp_bwd_dx: grid of %d workgroups", grid);
+  a.part5 = a.gstash + (size_t)a.n_tiles * gstash_floats_per_tile();
   // maxima of G_0 .. G_4 over all tiles, folded in by the kernel: floats [8, 16) behind the stash's tiles
   if (int e = zero_words(const_cast<float*>(a.stash) + (size_t)a.n_tiles * stash_floats_per_tile(a.g.c_in16, a.g.s16 != 0) + 8, 8,
                          static_cast<hipStream_t>(stream)))
@@ -1322,6 +1356,13 @@ int dvd_sf_mlp_bwd_dx(const dvd_mlp_desc* d, const void* packed, const void* sta
   if (a.g.s16) e = nw == 4 ? go(mlp_bwd_dx_kernel<true, 4>) : go(mlp_bwd_dx_kernel<true, 8>);
   else e = nw == 4 ? go(mlp_bwd_dx_kernel<false, 4>) : go(mlp_bwd_dx_kernel<false, 8>);
   if (e) return e;
+  DVD_LAUNCH_OK();
+  Dx5ReduceArgs r;
+  r.part = a.part5;
+  r.gW5 = gW5;
+  r.gb5 = gb5;
+  r.G = grid;
+  hipLaunchKernelGGL(mlp_dx5_reduce_kernel, dim3((3 * kWidth + 3 + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), r);
   DVD_LAUNCH_OK();
   return DVD_OK;
 }

@@ -224,7 +224,9 @@ int dvd_sf_mlp_fwd(const dvd_mlp_desc* d, const void* packed, const float* p, co
  *   g_out = gscale * (scale_ptr ? *scale_ptr : 1) * g_out1 + (g_out2 ? g_out2 : 0)
  *   g_p   = J^T (out_scale * g_out)  + (g_p_add ? g_p_add : 0)
  * writes the pre-activation gradients of layers 0..4 to `gstash` and
- * ACCUMULATES the last layer's dW (gW5 [3,256]) and db (gb5 [3]) with atomics. */
+ * ACCUMULATES the last layer's dW (gW5 [3,256]) and db (gb5 [3]): per-workgroup shares (in the weight-gradient
+ * workspace at the end of `gstash`, which must have dvd_sf_mlp_gstash_bytes(n_pix)) summed in fixed order by a second
+ * kernel, one atomic add per element and call -- bitwise reproducible from call to call. */
 int dvd_sf_mlp_bwd_dx(const dvd_mlp_desc* d, const void* packed, const void* stash, float out_scale,
                       const float* g_out1, float gscale, const float* scale_ptr, const float* g_out2,
                       const float* g_p_add, long long n_pix, int pix_per_img, float* g_p, void* gstash,

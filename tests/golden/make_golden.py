@@ -102,26 +102,39 @@ def case_geometry(name, B, H, W, gap, behind, seed):
     print('wrote', name, {k: v.shape for k, v in out.items() if k.startswith('slack_')})
 
 
-def case_mlp(name, B, H, W, seed):
+def case_mlp(name, B, H, W, seed, n_freq_xyz=16, n_freq_t=16, time_dependent=True, seeded=False):
+    """seeded: the weights come from tests/helpers.py::seeded_fill_(net, seed) and are not stored; of the parameter
+    gradients only those of convs.0 and convs.5 are (and the norm of every one)."""
     *_, Net = ref_modules()
     torch.manual_seed(seed)
-    net = Net(net_width=256, n_layers=4, time_dependent=True, N_freq_xyz=16, N_freq_t=16)
-    for m in net.modules():
-        if isinstance(m, torch.nn.Conv2d):
-            torch.nn.init.kaiming_normal_(m.weight.data, a=0.2, mode='fan_in')
-            torch.nn.init.normal_(m.bias.data, 0.0, 0.05)   # non-zero so bias paths are exercised
+    net = Net(net_width=256, n_layers=4, time_dependent=time_dependent, N_freq_xyz=n_freq_xyz, N_freq_t=n_freq_t)
+    if seeded:
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import helpers
+        helpers.seeded_fill_(net, seed)
+    else:
+        for m in net.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                torch.nn.init.kaiming_normal_(m.weight.data, a=0.2, mode='fan_in')
+                torch.nn.init.normal_(m.bias.data, 0.0, 0.05)   # non-zero so bias paths are exercised
     g = torch.Generator().manual_seed(seed + 1)
     x = (torch.randn(B, 3, H, W, generator=g) * 2.0).requires_grad_(True)
     t = torch.rand(B, 1, 1, 1, generator=g).expand(B, 1, H, W).contiguous()
-    y = net(x, t)
+    y = net(x, t if time_dependent else None)
     up = torch.randn(y.shape, generator=g)
     (y * up).sum().backward()
     out = {'in_x': x.detach().numpy(), 'in_t': t.numpy(), 'out_y': y.detach().numpy(), 'up_y': up.numpy(),
            'g_x': x.grad.numpy()}
-    for k, v in net.state_dict().items():
-        out['sd_' + k] = v.numpy()
+    if seeded:
+        out['geometry'] = np.array([n_freq_xyz, n_freq_t, int(time_dependent), seed])
+        out['param_names'] = np.array([k for k, _ in net.named_parameters()])
+        out['grad_norms'] = np.array([float(p.grad.double().norm()) for _, p in net.named_parameters()])
+    else:
+        for k, v in net.state_dict().items():
+            out['sd_' + k] = v.numpy()
     for k, p in net.named_parameters():
-        out['gsd_' + k] = p.grad.numpy()
+        if not seeded or k.startswith('convs.0.') or k.startswith('convs.5.'):
+            out['gsd_' + k] = p.grad.numpy()
     np.savez_compressed(os.path.join(OUT_DIR, name + '.npz'), **out)
     print('wrote', name)
 
@@ -155,7 +168,7 @@ def case_step(name, B, H, W, gap, behind, seed, warm, **opt_over):
     o.update(opt_over)
     opt = SimpleNamespace(**o)
     torch.manual_seed(seed)
-    net = Net(net_width=256, n_layers=4, time_dependent=True, N_freq_xyz=16, N_freq_t=16)
+    net = Net(net_width=256, n_layers=4, time_dependent=opt.time_dependent, N_freq_xyz=opt.n_freq_xyz, N_freq_t=opt.n_freq_t)
     for mod in net.modules():
         if isinstance(mod, torch.nn.Conv2d):
             torch.nn.init.kaiming_normal_(mod.weight.data, a=0.2, mode='fan_in')
@@ -369,6 +382,10 @@ CASES = {
     'geom_b2_24x32': lambda n: case_geometry(n, B=2, H=24, W=32, gap=1, behind=0, seed=11),
     'geom_b3_16x40_behind': lambda n: case_geometry(n, B=3, H=16, W=40, gap=2, behind=1, seed=23),
     'mlp_b2_8x16': lambda n: case_mlp(n, B=2, H=8, W=16, seed=5),
+    # input layers other than the shipped (16, 16, time dependent): the reference's own default (no --time_dependent) and a
+    # small embedding whose layer 0 is exactly one 32-channel row tile
+    'mlp_b2_8x16_notime': lambda n: case_mlp(n, B=2, H=8, W=16, seed=7, time_dependent=False, seeded=True),
+    'mlp_b2_8x16_f4_2': lambda n: case_mlp(n, B=2, H=8, W=16, seed=9, n_freq_xyz=4, n_freq_t=2, seeded=True),
     'step_b2_24x32_full': lambda n: case_step(n, B=2, H=24, W=32, gap=1, behind=0, seed=31, warm=False),
     'step_b2_24x32_warm': lambda n: case_step(n, B=2, H=24, W=32, gap=2, behind=0, seed=37, warm=True),
     'step_b3_16x40_behind_gap2': lambda n: case_step(n, B=3, H=16, W=40, gap=2, behind=1, seed=41, warm=False),
@@ -385,6 +402,11 @@ CASES = {
     # the U-Net scene-flow network (round 4)
     'fullstep_hourglass_b2_32x48_usecnn_gap2': lambda n: case_full_step(n, midas=False, B=2, H=32, W=48, gap=2, epoch=6, seed=127,
                                                                         over=dict(use_cnn=True)),
+    # the time-independent Euler chain and the shared regulariser evaluation / a small embedding in the real _train_on_batch
+    'fullstep_hourglass_b2_32x48_notime_gap2': lambda n: case_full_step(n, midas=False, B=2, H=32, W=48, gap=2, epoch=6, seed=139,
+                                                                        over=dict(time_dependent=False)),
+    'fullstep_hourglass_b2_32x48_f4_2': lambda n: case_full_step(n, midas=False, B=2, H=32, W=48, gap=1, epoch=6, seed=149,
+                                                                 over=dict(n_freq_xyz=4, n_freq_t=2)),
     'flow_masks': lambda n: case_flow_masks(n),
     # K-step trajectories of the real reference (round 5)
     'traj5_hourglass_b2_32x48': lambda n: case_trajectory(n, midas=False, B=2, H=32, W=48, gap=1, epoch=6, seed=131),
@@ -406,7 +428,8 @@ GROUPS = {
     'small': ('geom_b2_24x32', 'geom_b3_16x40_behind', 'mlp_b2_8x16', 'step_b2_24x32_full', 'step_b2_24x32_warm',
               'step_b3_16x40_behind_gap2', 'step_b2_16x24_sfloss', 'step_b2_16x24_ratio', 'fullstep_hourglass_b2_32x48_train',
               'fullstep_hourglass_b2_32x48_warm', 'fullstep_hourglass_b2_32x48_mseg_gap2', 'flow_masks',
-              'traj5_hourglass_b2_32x48'),
+              'traj5_hourglass_b2_32x48', 'mlp_b2_8x16_notime', 'mlp_b2_8x16_f4_2', 'fullstep_hourglass_b2_32x48_notime_gap2',
+              'fullstep_hourglass_b2_32x48_f4_2'),
 }
 
 

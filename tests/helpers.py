@@ -58,6 +58,28 @@ def log_measured(name, value, bound):
             f.write(json.dumps({'test': name, 'measured': float(value), 'bound': float(bound)}) + '\n')
 
 
+def mlp_oracle_f64(sd, x, t=None, n_freq_xyz=16, n_freq_t=16, pre=None):
+    """oracle.sceneflow_mlp.mlp_forward with the periodic embedding in fp32 (the reference rounds f * v in fp32, and so does the
+    kernel) and the 1x1 convolutions in float64.  An fp32 oracle on the host carries summation-order noise of its own (MKL
+    blocks by thread count) of up to ~0.6 of the forward tolerance on these sizes; against float64 the comparison measures the
+    kernels alone.  t=None: the time-independent network.  x / t may be float64 (an Euler chain): they are embedded as fp32.
+    pre: a list that receives the five hidden pre-activations."""
+    import torch.nn.functional as F
+    from oracle import sceneflow_mlp as M
+    feat = M.periodic_embed(x.float(), n_freq_xyz)
+    if t is not None:
+        feat = torch.cat([M.periodic_embed(t.float(), n_freq_t), feat], 1)
+    h = feat.double()
+    n_layers = len([k for k in sd if k.endswith('conv.weight')])
+    for i in range(n_layers):
+        h = F.conv2d(h, sd['convs.%d.conv.weight' % i], sd['convs.%d.conv.bias' % i])
+        if i < n_layers - 1:
+            if pre is not None:
+                pre.append(h)
+            h = F.leaky_relu(h, M.LRELU_SLOPE)
+    return h
+
+
 def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)

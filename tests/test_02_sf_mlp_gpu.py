@@ -11,33 +11,22 @@ agrees to 2.6e-6 of its largest element, median 2e-7; the values are appended to
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from helpers import golden_mlp_sd, load_golden, t
+from helpers import golden_mlp_sd, load_golden, mlp_oracle_f64, seeded_fill_, t
 from oracle import sceneflow_mlp as M
 
 pytestmark = pytest.mark.gpu
 
 
-def _net_from_sd(sd, time_dependent=True):
+def _net_from_sd(sd, time_dependent=True, n_freq_xyz=16, n_freq_t=16):
     from dvd_hip.networks.sceneflow_field import SceneFlowFieldNet
-    net = SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=time_dependent, N_freq_xyz=16, N_freq_t=16)
+    net = SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=time_dependent, N_freq_xyz=n_freq_xyz, N_freq_t=n_freq_t)
     missing = net.load_state_dict(sd, strict=True)
     assert not missing.missing_keys and not missing.unexpected_keys
     return net.cuda()
 
 
-def _oracle_f64(sd, x, t):
-    """M.mlp_forward with the periodic embedding in fp32 (the reference rounds f * v in fp32, and so does the kernel) and the
-    1x1 convolutions in float64.  An fp32 oracle on the host carries summation-order noise of its own (MKL blocks by thread
-    count) of up to ~0.6 of the forward tolerance on these sizes; against float64 the comparison measures the kernels alone."""
-    h = torch.cat([M.periodic_embed(t, 16), M.periodic_embed(x, 16)], 1).double()
-    n_layers = len([k for k in sd if k.endswith('conv.weight')])
-    for i in range(n_layers):
-        h = F.conv2d(h, sd['convs.%d.conv.weight' % i], sd['convs.%d.conv.bias' % i])
-        if i < n_layers - 1:
-            h = F.leaky_relu(h, M.LRELU_SLOPE)
-    return h
+_oracle_f64 = mlp_oracle_f64       # (tests/helpers.py: shared with tests/test_02b_sf_mlp_geometry_gpu.py)
 
 
 def _close(got, want, rel, name, max_outliers=0):
@@ -72,17 +61,33 @@ def test_state_dict_keys_match_reference():
     assert sorted(net.state_dict().keys()) == sorted(k[3:] for k in gd if k.startswith('sd_'))
 
 
-def test_module_forward_backward_vs_golden():
-    gd = load_golden('mlp_b2_8x16')
-    net = _net_from_sd(golden_mlp_sd(gd))
+@pytest.mark.parametrize('name', ['mlp_b2_8x16', 'mlp_b2_8x16_notime', 'mlp_b2_8x16_f4_2'])
+def test_module_forward_backward_vs_golden(name):
+    """The real reference network's outputs and gradients: the shipped input layer (weights stored in the fixture), the
+    reference's default time-independent one and a (4, 2) embedding (weights from helpers.seeded_fill_; the gradients of
+    convs.0 and convs.5 element by element, of every parameter by its norm)."""
+    gd = load_golden(name)
+    if 'geometry' in gd:
+        nx, nt, td, seed = (int(v) for v in gd['geometry'])
+        from dvd_hip.networks.sceneflow_field import SceneFlowFieldNet
+        net = seeded_fill_(SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=bool(td), N_freq_xyz=nx, N_freq_t=nt),
+                           seed).cuda()
+    else:
+        td, net = 1, _net_from_sd(golden_mlp_sd(gd))
     x = t(gd['in_x']).cuda().requires_grad_(True)
-    tt = t(gd['in_t']).cuda()
-    y = net(x, tt)
+    y = net(x, t(gd['in_t']).cuda() if td else None)
     np.testing.assert_allclose(y.detach().cpu().numpy(), gd['out_y'], rtol=1e-4, atol=2e-6)
     (y * t(gd['up_y']).cuda()).sum().backward()
     _close(x.grad.cpu().numpy(), gd['g_x'], 1e-5, 'g_x')
     for k, p in net.named_parameters():
-        _close(p.grad.cpu().numpy(), gd['gsd_' + k], 1e-5, k)
+        if 'gsd_' + k in gd:
+            _close(p.grad.cpu().numpy(), gd['gsd_' + k], 1e-5, k)
+    if 'grad_norms' in gd:
+        # | ||g|| - ||ref|| | <= ||g - ref|| <= 1e-5 max|g| sqrt(n): what the element-wise tolerance allows a norm
+        params = dict(net.named_parameters())
+        for k, want in zip(gd['param_names'], gd['grad_norms']):
+            g = params[str(k)].grad.double()
+            assert abs(float(g.norm()) - float(want)) <= 1e-5 * float(g.abs().max()) * g.numel() ** 0.5, k
 
 
 @pytest.mark.parametrize('B,H,W', [(1, 8, 8), (2, 24, 40), (3, 17, 23)])
@@ -147,7 +152,8 @@ def test_workgroup_shapes_give_the_same_bits(B, H, W, stash_f16):
     """dvd_sf_mlp_select: two 4-wave workgroups per CU (the default since round 5) against one of 8 waves (rounds 2-4).  Who
     computes a 32-channel row tile changes, the products and their order do not: outputs, both stashes (activations, sign
     words, per-layer maxima) and the input gradient are bit-identical; the weight gradients are computed from identical
-    stashes by the same kernel.  dW5 / db5 are float atomics over workgroups in both shapes: equal to rounding only."""
+    stashes by the same kernel.  dW5 / db5 are per-workgroup shares summed in workgroup order, and the two shapes have
+    different grids: equal to rounding only."""
     from dvd_hip import _lib, ops
     lib = _lib.load()
     sd = M.init_params(seed=11)

@@ -36,9 +36,8 @@ def _build(gd, **over):
     from dvd_hip.models.scene_flow_motion_field import Model
     o = dict(helpers.FULL_STEP_OPT)
     o.update(midas=bool(gd['midas']), full_logdir='/tmp')
-    if 'over_keys' in gd:                     # option overrides the fixture was generated with
-        o.update({str(k): (bool(v) if isinstance(o.get(str(k)), bool) else float(v))
-                  for k, v in zip(gd['over_keys'], gd['over_vals'])})
+    if 'over_keys' in gd:                     # option overrides the fixture was generated with, in the type of the default
+        o.update({str(k): type(o.get(str(k), 0.0))(v) for k, v in zip(gd['over_keys'], gd['over_vals'])})
     o.update(over)
     opt = SimpleNamespace(**o)
     with pytest.warns(UserWarning):          # checkpoints are absent: random weights announced
@@ -58,7 +57,9 @@ def _build(gd, **over):
 @pytest.mark.parametrize('name', ['fullstep_hourglass_b2_32x48_train', 'fullstep_hourglass_b2_32x48_warm',
                                   'fullstep_midas_b1_64x96_train', 'fullstep_hourglass_b2_32x48_mseg_gap2',
                                   'fullstep_midas_b2_192x384_train',       # BASELINE configs[0] shape, 2 pairs
-                                  'fullstep_hourglass_b2_32x48_usecnn_gap2'])   # --use_cnn: the U-Net scene-flow network
+                                  'fullstep_hourglass_b2_32x48_usecnn_gap2',    # --use_cnn: the U-Net scene-flow network
+                                  'fullstep_hourglass_b2_32x48_notime_gap2',    # no --time_dependent: the reference's default
+                                  'fullstep_hourglass_b2_32x48_f4_2'])          # --n_freq_xyz 4 --n_freq_t 2
 def test_train_on_batch_matches_reference(name):
     gd = helpers.load_golden(name)
     model, opt, batch = _build(gd)
@@ -123,7 +124,8 @@ def test_two_steps_run_and_change_the_loss():
     assert model._flat_sf.step_count == 2 and model._flat_depth.step_count == 2
 
 
-@pytest.mark.parametrize('name', ['fullstep_hourglass_b2_32x48_train', 'fullstep_hourglass_b2_32x48_mseg_gap2'])
+@pytest.mark.parametrize('name', ['fullstep_hourglass_b2_32x48_train', 'fullstep_hourglass_b2_32x48_mseg_gap2',
+                                  'fullstep_hourglass_b2_32x48_notime_gap2'])
 @pytest.mark.parametrize('whole_gb,recompute', [(160.0, 1), (0.0, 1), (0.0, 0)])
 def test_pair_chunking_is_invisible(whole_gb, recompute, name):
     """A stash budget that forces one pair per MLP chunk gives the same step: when the
@@ -131,7 +133,7 @@ def test_pair_chunking_is_invisible(whole_gb, recompute, name):
     alive), when the stashes of the whole batch do not fit and the Euler chain is evaluated twice (stash-free over the
     batch, stashed again per chunk: the recompute schedule of round 6), and when warp+loss runs once per chunk with the
     late normaliser (rounds 1-5).  Also at frame gap 2 with --use_motion_seg (two Euler evaluations, the regulariser's
-    second evaluation shared with the chain's)."""
+    second evaluation shared with the chain's), and at gap 2 on the time-independent network (every schedule without t)."""
     gd = helpers.load_golden(name)
     m1, _, batch = _build(gd)
     m2, _, _ = _build(gd, mlp_stash_gb=1e-6, depth_chunk=1, mlp_whole_batch_gb=whole_gb, mlp_recompute=recompute)

@@ -57,6 +57,29 @@ def test_mlp_forward_backward():
         np.testing.assert_allclose(v.grad.numpy(), g, rtol=1e-4, atol=1e-5 * np.abs(g).max(), err_msg=k)
 
 
+@pytest.mark.parametrize('name', ['mlp_b2_8x16_notime', 'mlp_b2_8x16_f4_2'])
+def test_mlp_forward_backward_other_input_layers(name):
+    """The reference's default time-independent network and a (4, 2) embedding; weights from helpers.seeded_fill_."""
+    import helpers
+    from dvd_hip.networks.sceneflow_field import SceneFlowFieldNet
+    from oracle import train_step as T
+    gd = load_golden(name)
+    nx, nt, td, seed = (int(v) for v in gd['geometry'])
+    net = helpers.seeded_fill_(SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=bool(td), N_freq_xyz=nx, N_freq_t=nt), seed)
+    sd = {k: v.clone().requires_grad_(True) for k, v in T.mlp_state_from_module(net).items()}
+    assert sd['convs.0.conv.weight'].shape[1] == M.layer_dims(n_freq_xyz=nx, n_freq_t=nt, time_dependent=bool(td))[0]
+    x = t(gd['in_x']).requires_grad_(True)
+    y = M.mlp_forward(sd, x, t(gd['in_t']) if td else None, n_freq_xyz=nx, n_freq_t=nt)
+    np.testing.assert_allclose(y.detach().numpy(), gd['out_y'], rtol=1e-5, atol=1e-6)
+    (y * t(gd['up_y'])).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), gd['g_x'], rtol=1e-4, atol=1e-6)
+    for k in [k[4:] for k in gd if k.startswith('gsd_')]:
+        g = gd['gsd_' + k]
+        np.testing.assert_allclose(sd[k].grad.numpy(), g, rtol=1e-4, atol=1e-5 * np.abs(g).max(), err_msg=k)
+    for k, want in zip(gd['param_names'], gd['grad_norms']):
+        np.testing.assert_allclose(float(sd[str(k)].grad.double().norm()), float(want), rtol=1e-5, err_msg=str(k))
+
+
 def test_mlp_init_statistics():
     sd = M.init_params(seed=0)
     dims = M.layer_dims()
@@ -95,7 +118,8 @@ def test_step_losses_and_grads(name):
 
 
 @pytest.mark.parametrize('name', ['fullstep_hourglass_b2_32x48_train', 'fullstep_hourglass_b2_32x48_warm',
-                                  'fullstep_hourglass_b2_32x48_mseg_gap2', 'fullstep_hourglass_b2_32x48_usecnn_gap2'])
+                                  'fullstep_hourglass_b2_32x48_mseg_gap2', 'fullstep_hourglass_b2_32x48_usecnn_gap2',
+                                  'fullstep_hourglass_b2_32x48_notime_gap2', 'fullstep_hourglass_b2_32x48_f4_2'])
 def test_full_step_oracle_reproduces_the_reference_logs(name):
     """oracle.train_step (what bench.py times as cpu_baseline) against the batch_log the REAL reference
     Model._train_on_batch produced for the same seeded weights and batch (tests/golden/make_golden.py)."""
@@ -107,8 +131,7 @@ def test_full_step_oracle_reproduces_the_reference_logs(name):
     gd = load_golden(name)
     o = dict(helpers.FULL_STEP_OPT)
     if 'over_keys' in gd:
-        o.update({str(k): (bool(v) if isinstance(o.get(str(k)), bool) else float(v))
-                  for k, v in zip(gd['over_keys'], gd['over_vals'])})
+        o.update({str(k): type(o.get(str(k), 0.0))(v) for k, v in zip(gd['over_keys'], gd['over_vals'])})
     opt = L.default_opt(**{k: o[k] for k in ('midas', 'use_disp', 'use_disp_ratio', 'time_dependent', 'flow_mul', 'disp_mul',
                                              'acc_mul', 'sf_mag_div', 'interp_steps', 'warm_reg', 'weight_steps',
                                              'use_motion_seg', 'n_freq_xyz', 'n_freq_t', 'use_cnn', 'n_down')})
@@ -118,8 +141,8 @@ def test_full_step_oracle_reproduces_the_reference_logs(name):
         from dvd_hip.networks.FCNUnet import FCNUnet
         mlp = helpers.seeded_fill_(FCNUnet(None, n_down=3, feat=32, block_type='double_conv', in_channel=4, out_channel=3), seed + 1)
     else:
-        mlp = helpers.seeded_fill_(SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=True, N_freq_xyz=16,
-                                                     N_freq_t=16), seed + 1)
+        mlp = helpers.seeded_fill_(SceneFlowFieldNet(net_width=256, n_layers=4, time_dependent=opt.time_dependent,
+                                                     N_freq_xyz=opt.n_freq_xyz, N_freq_t=opt.n_freq_t), seed + 1)
     sd = T.mlp_state_from_module(mlp)
     batch = synthetic.make_batch(int(gd['B']), int(gd['H']), int(gd['W']), gap=int(gd['gap']), seed=seed + 2)
     warm = int(gd['epoch']) <= o['warm_sf']
