@@ -1,19 +1,25 @@
-"""Convolutions of the depth networks that run on hand-written HIP kernels.
+"""Host side of the depth networks' layers that run on hand-written HIP kernels: both depth nets (MiDaS, hourglass) and the
+`--use_cnn` U-Net build their convolutions from this file.
 
-`GroupedConv3x3C8` is `nn.Conv2d(C, C, 3, padding=1, groups=C // 8, bias=False)` -- the
-`conv2` of the ResNeXt-101 32x8d stage-1 bottlenecks inside the MiDaS encoder (reference:
-third_party/midas_blocks.py:35-50; torchvision resnet.py Bottleneck with groups=32,
-width_per_group=8).  Same parameter name and shape (`weight [C, 8, 3, 3]`), so
-state_dicts interchange.  Forward, backward-data and backward-weight go through
-`dvd_gconv3x3_c8_*` (csrc/gconv.hip); MIOpen's immediate mode serves the backward of this
-shape at 0.3 TFLOP/s (profiles/r01_depthnet_profile.txt), which made three small
-convolutions 38 % of the depth net's time.
+  * the DVD_AB measurement switches and the fp16 activation storage's loss-scale state (`AB`, `GRAD_SCALE`);
+  * element-wise and pooling layers: `bn_eval_relu`, `to_half`, `add_f16`, `upsample_bilinear2x`, `maxpool3s2`, `AvgPool2d`,
+    the depth heads (`head1x1`, `head3x3`, `depth_tail`);
+  * grouped 3x3 convolutions: `GroupedConv3x3C8` (`nn.Conv2d(C, C, 3, padding=1, groups=C // 8, bias=False)`, the `conv2` of
+    the ResNeXt-101 32x8d stage-1 bottlenecks, third_party/midas_blocks.py:35-50; csrc/gconv.hip), `GroupedConv3x3C16` and
+    `GroupedConv3x3C32` (on the grouped xconv path);
+  * the ResNeXt stem as a stride-1 5x5 convolution over the space-to-depth image (`stem_conv_bn_relu`);
+  * dense and grouped 'same' convolutions on the split-operand MFMA kernels (csrc/xconv.hip, csrc/xwgrad3.hip): the packed
+    weight cache and its per-step plan (`xconv_packed`, `xconv_packed_scaled`, `PACK_PLAN`), the launch (`_xconv_run`), the
+    weight gradient (`xconv_wgrad`), the autograd Functions `_XConv`, `_XConvS2`, `_XConvBn` with their fused gradient
+    joins and ReLU-mask hand-over (`_Site`), and the entry points the networks call: `xconv2d`, `conv_bn_act`, `XConv2d`.
 
-Tensors that the kernels do not cover (CPU tensors of the oracle/tests, other dtypes)
-take `F.conv2d`; on a GPU in fp32 the HIP path is the one that runs.
+Every module keeps the parameter names and shapes of the `nn.Conv2d` it replaces, so state_dicts interchange.  Tensors that
+the kernels do not cover (CPU tensors of the oracle / tests, other dtypes) take the ATen ops; on a GPU in fp32 or fp16 the HIP
+path is the one that runs.
 """
 import ctypes
 import os as _os
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -23,23 +29,16 @@ from . import _lib
 from .ops import _p, _stream, _workspace, amax_of, chansum, known_amax, new_scalar, set_amax
 
 # Same-box A/B measurement switches (previous-generation kernels / MIOpen against the kernels in use), read ONCE at
-# import from DVD_AB="gconv32,no_bnfuse,...".  Not product configuration: every default is the fastest measured path.
+# import from DVD_AB="gconv32,no_alias,...".  Not product configuration: every default is the fastest measured path.
 #   gconv32     32-per-group 3x3 on round 1's fp32-MFMA kernels (csrc/gconv32.hip) instead of the grouped xconv path
-#   no_c16      16-per-group 3x3 on MIOpen instead of paired groups on the 32-per-group kernels
-#   no_xwgrad3  weight gradients on the exact-fp32 MFMA kernel (csrc/xwgrad.hip);  no_xwgrad: on MIOpen
-#   no_bnfuse   BatchNorm (+ residual, ReLU) as a separate pass after the convolution
-#   no_xconv    dense convolutions on MIOpen
+#   no_xwgrad3  dense weight gradients on the exact-fp32 MFMA kernel (csrc/xwgrad.hip)
 #   no_alias    gradient joins of residual blocks by autograd's accumulation (ATen add) instead of the backward-data epilogue
 #   no_maskfuse the ReLU mask of a BatchNorm+ReLU site always in the site's own mask pass (never in its consumer's epilogue)
-#   no_packplan every captured graph packs its weights itself (two launches per weight tensor and graph)
-#   no_chansum  bias gradients by an ATen sum (and max|gy| by dvd_amax) instead of one dvd_chansum read
 #   no_s2       stride-2 3x3 convolutions as rounds 2-5 ran them: the stride-1 kernel's output sub-sampled, the gradient
 #               zero-interleaved in HBM (csrc/pool.hip) in front of the stride-1 backward-data kernel
 #   rowsum      (opt-in experiment) a pre-masked site takes its per-channel sums from dvd_xwgrad1s_rowsum and max|g| from the
 #               consumer's epilogue instead of running its sum pass
-AB = {k: False for k in ('gconv32', 'no_c16', 'no_xwgrad3', 'no_xwgrad', 'no_bnfuse', 'no_xconv', 'no_alias', 'no_maskfuse',
-                         'no_chansum', 'no_packplan', 'no_s2',
-                         'rowsum')}
+AB = {k: False for k in ('gconv32', 'no_xwgrad3', 'no_alias', 'no_maskfuse', 'no_s2', 'rowsum')}
 for _k in filter(None, _os.environ.get('DVD_AB', '').split(',')):
     if _k not in AB:
         raise RuntimeError('DVD_AB: unknown switch %r (known: %s)' % (_k, ', '.join(sorted(AB))))
@@ -455,8 +454,8 @@ class GroupedConv3x3C32(nn.Conv2d):
 # STRIDE-1 convolution over the 2x2 space-to-depth image: with x'[4c + 2py + px][Y][X] = x[c][2Y + py][2X + px] and
 # ky - 3 = 2a + py (a in -2..1), out[y][x] = sum w[c][ky][kx] x'[4c + 2py + px][y + a][x + b] -- a 4x4 kernel, embedded in a
 # 5x5 "same" one (zero taps at a = 2 / b = 2).  That runs on the kernels this package already has: xconv (csrc/xconv.hip) with
-# the eval-mode BatchNorm + ReLU in its epilogue, and the exact-fp32 weight gradient (csrc/xwgrad.hip, KS = 5); the image needs
-# no gradient.  The rearranged weight is a gather of the module's [64,3,7,7] parameter, so its gradient flows back through
+# the eval-mode BatchNorm + ReLU in its epilogue, and the k x k weight gradient (xwgradk in csrc/xwgrad3.hip, KS = 5); the image
+# needs no gradient.  The rearranged weight is a gather of the module's [64,3,7,7] parameter, so its gradient flows back through
 # autograd's index backward and the state_dict keeps the reference's key and shape.
 _S2D_IDX = {}
 
@@ -650,7 +649,7 @@ class GroupedConv3x3C16(nn.Conv2d):
 
     def forward(self, x):
         st = self.stride[0]
-        if x.is_cuda and x.dtype in ACT_DTYPES and not AB['no_c16'] and (st == 1 or not AB['gconv32']):
+        if x.is_cuda and x.dtype in ACT_DTYPES and (st == 1 or not AB['gconv32']):
             if not AB['gconv32']:
                 w32 = _pair_groups_of_16(self.weight)
                 if st == 2 and xconv_s2_supported(x, w32, self.groups // 2):
@@ -717,13 +716,11 @@ class _PackPlan(object):
             weight._dvd_pack_req = req
         req[kind] = (int(groups), gamma, var, float(eps))
         if id(weight) not in self.requests:
-            import weakref
             key = id(weight)
             self.requests[key] = weakref.ref(weight, lambda _r, key=key, reqs=self.requests: reqs.pop(key, None))
 
     @staticmethod
     def _ref(t):
-        import weakref
         return weakref.ref(t) if t is not None else (lambda: None)
 
     def extend(self):
@@ -731,8 +728,7 @@ class _PackPlan(object):
         if torch.cuda.is_current_stream_capturing():
             return
         lib = _lib.load()
-        import weakref
-        live = [e for e in self.entries if e['w']() is not None]
+        live =[e for e in self.entries if e['w']() is not None]
         if len(live) != len(self.entries):
             self.entries, self.dirty = live, True
         for ref in list(self.requests.values()):
@@ -821,9 +817,10 @@ class _PackPlan(object):
 PACK_PLAN = _PackPlan()
 
 
-def xconv_packed_scaled(weight, groups, gamma, var, eps):
-    """Transposed packing with row co scaled by gamma[co] / sqrt(var[co] + eps): backward-data through a fused BatchNorm.
-    Cached on the weight like xconv_packed; the key also follows gamma (optimiser steps) and the running variance."""
+def _xconv_packed(weight, kind, groups, gamma=None, var=None, eps=0.0):
+    """The packed copy of `weight` of one of the plan's kinds: 'F' forward, 'T' transposed (backward-data), 'Ts' transposed with
+    row co scaled by gamma[co] / sqrt(var[co] + eps).  Eager calls are served from a cache that hangs on the weight tensor
+    OBJECT (not on its address: allocators reuse addresses), one buffer per kind, re-packed in place when the key changed."""
     from . import ops
     w = weight.detach()
     if not w.is_contiguous():
@@ -831,74 +828,49 @@ def xconv_packed_scaled(weight, groups, gamma, var, eps):
     Cout, Cin, KS, _ = w.shape
     Cin *= groups
     lib = _lib.load()
-    nbytes = lib.dvd_xconv_packed_bytes(Cout, Cin, KS, groups, 1)
     capturing = torch.cuda.is_current_stream_capturing()
-    if not AB['no_packplan']:
-        if capturing:
-            planned = PACK_PLAN.lookup(weight, 'Ts', gamma, var, eps)
-            if planned is not None:
-                return planned
-        else:
-            PACK_PLAN.request(weight, 'Ts', groups, gamma, var, eps)
-    key = (w.data_ptr(), weight._version, ops.WEIGHT_EPOCH[0], tuple(w.shape),
-           None if gamma is None else (gamma.data_ptr(), gamma._version), var.data_ptr(), var._version, float(eps))
-    cache = getattr(weight, '_dvd_xpack', None)
-    if cache is None and not capturing:
-        cache = {}
-        weight._dvd_xpack = cache
-    hit = cache.get('Ts') if cache is not None else None
-    if not capturing and hit is not None and hit[0] == key:
-        return hit[1]
-    packed = hit[1] if (not capturing and hit is not None and hit[1].numel() == nbytes) else \
-        torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-    _lib.check(lib.dvd_xconv_pack_scaled(_p(w), _p(packed), Cout, Cin, KS, groups, 1, _p(gamma), _p(var), float(eps), _stream()),
-               'dvd_xconv_pack_scaled')
+    if capturing:
+        planned = PACK_PLAN.lookup(weight, kind, gamma, var, eps)
+        if planned is not None:             # kept current by the graph's owner (PACK_PLAN.ensure_current before a replay)
+            return planned
+    else:
+        PACK_PLAN.request(weight, kind, groups, gamma, var, eps)
+    # HIP-graph capture without a plan entry: the pack launch must be PART of the graph (a replay runs no Python, and the
+    # weights change between replays), into a buffer of the graph's own pool -- the cache is neither read nor filled
+    hit = None
     if not capturing:
-        cache['Ts'] = (key, packed)
+        key = (w.data_ptr(), weight._version, ops.WEIGHT_EPOCH[0], tuple(w.shape))
+        if kind == 'Ts':                    # ... also follows gamma (optimiser steps) and the running variance
+            key += (None if gamma is None else (gamma.data_ptr(), gamma._version), var.data_ptr(), var._version, float(eps))
+        cache = getattr(weight, '_dvd_xpack', None)
+        if cache is None:
+            cache = weight._dvd_xpack = {}
+        hit = cache.get(kind)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    nbytes = lib.dvd_xconv_packed_bytes(Cout, Cin, KS, groups, int(kind != 'F'))
+    if nbytes == 0:
+        raise RuntimeError('xconv: unsupported weight shape %s' % (tuple(w.shape),))
+    packed = hit[1] if (hit is not None and hit[1].numel() == nbytes) else torch.empty(nbytes, device=w.device, dtype=torch.uint8)
+    if kind == 'Ts':
+        _lib.check(lib.dvd_xconv_pack_scaled(_p(w), _p(packed), Cout, Cin, KS, groups, 1, _p(gamma), _p(var), float(eps),
+                                             _stream()), 'dvd_xconv_pack_scaled')
+    else:
+        _lib.check(lib.dvd_xconv_pack(_p(w), _p(packed), Cout, Cin, KS, groups, int(kind == 'T'), _stream()), 'dvd_xconv_pack')
+    if not capturing:
+        cache[kind] = (key, packed)
     return packed
 
 
 def xconv_packed(weight, transposed, groups=1):
-    """Fragment-ordered, pre-split copy of a conv weight [Cout,Cin/groups,k,k].  The copy hangs on the weight
-    tensor OBJECT (not on its address: allocators reuse addresses) and is rebuilt when the weight changed:
-    new storage, autograd version counter, or an optimiser step of the fused Adam (ops.WEIGHT_EPOCH)."""
-    from . import ops
-    w = weight.detach()
-    if not w.is_contiguous():
-        w = w.contiguous()
-    Cout, Cin, KS, _ = w.shape
-    Cin *= groups
-    lib = _lib.load()
-    if not AB['no_packplan']:
-        if torch.cuda.is_current_stream_capturing():
-            planned = PACK_PLAN.lookup(weight, 'T' if transposed else 'F')
-            if planned is not None:         # kept current by the graph's owner (PACK_PLAN.ensure_current before a replay)
-                return planned
-        else:
-            PACK_PLAN.request(weight, 'T' if transposed else 'F', groups)
-    if torch.cuda.is_current_stream_capturing():
-        # HIP-graph capture without a plan entry: the pack launch must be PART of the graph (a replay runs no Python, and
-        # the weights change between replays), into a buffer of the graph's own pool -- never served from the cache
-        nbytes = lib.dvd_xconv_packed_bytes(Cout, Cin, KS, groups, int(transposed))
-        packed = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-        _lib.check(lib.dvd_xconv_pack(_p(w), _p(packed), Cout, Cin, KS, groups, int(transposed), _stream()), 'dvd_xconv_pack')
-        return packed
-    key = (w.data_ptr(), weight._version, ops.WEIGHT_EPOCH[0], tuple(w.shape))
-    cache = getattr(weight, '_dvd_xpack', None)
-    if cache is None:
-        cache = {}
-        weight._dvd_xpack = cache
-    hit = cache.get(bool(transposed))
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    nbytes = lib.dvd_xconv_packed_bytes(Cout, Cin, KS, groups, int(transposed))
-    if nbytes == 0:
-        raise RuntimeError('xconv: unsupported weight shape %s' % (tuple(w.shape),))
-    packed = hit[1] if (hit is not None and hit[1].numel() == nbytes) else torch.empty(nbytes, device=w.device,
-                                                                                       dtype=torch.uint8)
-    _lib.check(lib.dvd_xconv_pack(_p(w), _p(packed), Cout, Cin, KS, groups, int(transposed), _stream()), 'dvd_xconv_pack')
-    cache[bool(transposed)] = (key, packed)
-    return packed
+    """Fragment-ordered, pre-split copy of a conv weight [Cout,Cin/groups,k,k], rebuilt when the weight changed: new storage,
+    autograd version counter, or an optimiser step of the fused Adam (ops.WEIGHT_EPOCH)."""
+    return _xconv_packed(weight, 'T' if transposed else 'F', groups)
+
+
+def xconv_packed_scaled(weight, groups, gamma, var, eps):
+    """Transposed packing with row co scaled by gamma[co] / sqrt(var[co] + eps): backward-data through a fused BatchNorm."""
+    return _xconv_packed(weight, 'Ts', groups, gamma, var, eps)
 
 
 def _xconv_run(x, packed, Cout, KS, bias=None, residual=None, mask_src=None, relu_in=False, relu_out=False,
@@ -961,17 +933,60 @@ class _Site(object):
         """amax: the device scalar max|g| the writing kernel's epilogue produced (the site's operand scale).
         The hand-over is by tensor OBJECT (a weak reference), not by address: a sum (gA + gB) + gC that the allocator
         happens to place at a freed gA's address has version 0 like every kernel-written tensor, but it is another object."""
-        import weakref
         self.ref, self.version, self.amax = weakref.ref(g), g._version, amax
 
     def is_exactly(self, g):
         return self.ref is not None and self.ref() is g and self.version == g._version
 
 
+def _fwd_amax(ctx, x):
+    """Where a forward epilogue leaves max|y| -> (the scalar the Function returns beside y | None, the slot the kernel writes).
+    fp32: a fresh scalar, a non-differentiable output; fp16 activations carry no operand scale: their epilogue folds max|y| into
+    the overflow guard's forward monitor."""
+    if _is16(x):
+        return None, _fwd_monitor()
+    y_amax = new_scalar(x.device)
+    ctx.mark_non_differentiable(y_amax)
+    return y_amax, y_amax
+
+
+def _gy_reductions(gy, want_gb, want_amax):
+    """What a backward reads off the output gradient before its gradient kernels run -> (bias gradient | None, max|gy| | None):
+    the bias gradient and (if nobody attached it) max|gy| from ONE read of gy (rounds 1-5: ATen sum + dvd_amax); one max|gy|,
+    shared by both gradient kernels.  No bias gradient from here for fp16 or non-GPU gradients: _bias_grad_sum."""
+    gb = None
+    if want_gb and gy.is_cuda and gy.dtype == torch.float32 and gy.dim() == 4:
+        gb = chansum(gy, want_amax=want_amax and known_amax(gy) is None)
+    return gb, (amax_of(gy) if want_amax else None)
+
+
+def _bias_grad_sum(gy):
+    """The bias gradient where dvd_chansum does not serve (fp16 gradients carry the loss scale: times 1 / S)."""
+    return gy.sum((0, 2, 3), dtype=torch.float32) * _gs(1) if _is16(gy) else gy.sum((0, 2, 3))
+
+
+def _xconv_bwd_data(ctx, g, g_amax, weight, groups, mask_src, g_alias=None, bn_scale=None, **strided):
+    """The backward-data launch of the three xconv Functions and what goes with it: max|gx| comes from the epilogue (fp16: into
+    the loss-scale policy's observed maximum) and is attached to gx (used by the next backward if autograd hands this very
+    tensor on); the BatchNorm+ReLU site x came from is told which tensor carries its mask (see _Site).  g_alias: the gradient of
+    x's other consumers, added in the epilogue; bn_scale = (gamma, var, eps): through a fused BatchNorm; strided: stride=-2 and
+    out_hw of _XConvS2."""
+    h16 = _is16(g)
+    gx_amax = _gs(3) if h16 else new_scalar(g.device)
+    packed = xconv_packed(weight, True, groups) if bn_scale is None else xconv_packed_scaled(weight, groups, *bn_scale)
+    gx = _xconv_run(g, packed, weight.shape[1] * groups, weight.shape[2], mask_src=mask_src, groups=groups, x_amax=g_amax,
+                    y_amax=gx_amax, residual=g_alias.contiguous() if g_alias is not None else None, **strided)
+    if not h16:
+        set_amax(gx, gx_amax)
+    if ctx.in_site is not None:
+        ctx.in_site.wrote(gx, None if h16 else gx_amax)
+    return gx
+
+
 class _XConv(torch.autograd.Function):
     """y = conv2d(act(x), w, stride 1, padding k//2) + bias + res'   with act = ReLU or identity and
     res' = residual or relu(residual).  Forward and backward-data on csrc/xconv.hip; backward-weight on
-    csrc/xwgrad.hip (deterministic).
+    csrc/xwgrad3.hip (deterministic).
 
     Fused gradient joins (round 3).  `alias`: the Function also returns its input as a second differentiable output; the
     OTHER consumers of x (a residual connection, a shortcut convolution) take that alias instead of x, so their gradient
@@ -990,15 +1005,12 @@ class _XConv(torch.autograd.Function):
         if residual is not None:
             residual = residual.contiguous()
         Cout, _, KS, _ = weight.shape
-        # fp16 activations carry no operand scale; their epilogue folds max|y| into the overflow guard's forward monitor
-        y_amax = None if _is16(x) else new_scalar(x.device)
+        y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, KS, bias=bias, residual=residual, relu_in=relu_in,
-                       res_relu=res_relu, groups=groups, x_amax=x_amax, y_amax=_fwd_monitor() if _is16(x) else y_amax)
+                       res_relu=res_relu, groups=groups, x_amax=x_amax, y_amax=amax_slot)
         ctx.save_for_backward(x, residual if (res_relu and not res_unmasked) else None, x_amax)
         ctx.wparam = weight          # the tensor object that carries the packed copies
         ctx.cfg = (bool(relu_in), bool(res_relu), bias is not None, residual is not None, groups, bool(res_unmasked))
-        if y_amax is not None:
-            ctx.mark_non_differentiable(y_amax)
         if alias:
             return y, y_amax, x
         return y, y_amax
@@ -1011,29 +1023,16 @@ class _XConv(torch.autograd.Function):
         if gy is None:                      # only the alias was used downstream
             return g_alias, None, None, None, None, None, None, None, None, None, None
         gy = gy.contiguous()
-        Cout, Cin, KS, _ = weight.shape
         need = ctx.needs_input_grad
-        gx = gw = gb = gr = None
-        h16 = _is16(gy)
-        want_amax = (need[0] or need[2]) and not h16
-        if has_bias and need[3] and gy.is_cuda and gy.dtype == torch.float32 and gy.dim() == 4 and not AB['no_chansum']:
-            # the bias gradient and (if nobody attached it) max|gy| from ONE read of gy (rounds 1-5: ATen sum + dvd_amax)
-            gb = chansum(gy, want_amax=want_amax and known_amax(gy) is None)
-        g_amax = amax_of(gy) if want_amax else None   # one reduction, shared by both gradient kernels
+        gx = gw = gr = None
+        gb, g_amax = _gy_reductions(gy, has_bias and need[3], (need[0] or need[2]) and not _is16(gy))
         if need[0]:
-            gx_amax = _gs(3) if h16 else new_scalar(gy.device)      # fp16: the loss-scale policy's observed maximum
-            gx = _xconv_run(gy, xconv_packed(weight, True, groups), Cin * groups, KS,
-                            mask_src=x if (relu_in or ctx.in_site is not None) else None,
-                            groups=groups, x_amax=g_amax, y_amax=gx_amax,
-                            residual=g_alias.contiguous() if g_alias is not None else None)
-            if not h16:
-                set_amax(gx, gx_amax)     # (used by the next backward if autograd hands this very tensor on)
-            if ctx.in_site is not None:
-                ctx.in_site.wrote(gx, None if h16 else gx_amax)     # x is a BatchNorm+ReLU site's output: [x > 0] is already applied
+            # the mask [x > 0]: of the fused input ReLU, or of the BatchNorm+ReLU site whose output x is (ReLU is already applied)
+            gx = _xconv_bwd_data(ctx, gy, g_amax, weight, groups, x if (relu_in or ctx.in_site is not None) else None, g_alias)
         if need[2]:
             gw = xconv_wgrad(x, gy, weight.shape, relu_in, groups, x_amax=x_amax, g_amax=g_amax)
         if has_bias and need[3] and gb is None:
-            gb = gy.sum((0, 2, 3), dtype=torch.float32) * _gs(1) if h16 else gy.sum((0, 2, 3))
+            gb = _bias_grad_sum(gy)
         if has_res and need[4]:
             gr = gy * (residual > 0).to(gy.dtype) if (res_relu and not res_unmasked) else gy
         return gx, None, gw, gb, gr, None, None, None, None, None, None
@@ -1053,14 +1052,12 @@ class _XConvS2(torch.autograd.Function):
         ctx.in_site = in_site if (in_site is not None and not AB['no_maskfuse']) else None
         x = x.contiguous()
         Cout = weight.shape[0]
-        y_amax = None if _is16(x) else new_scalar(x.device)
+        y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, 3, bias=bias, groups=groups, x_amax=x_amax,
-                       y_amax=_fwd_monitor() if _is16(x) else y_amax, stride=2)
+                       y_amax=amax_slot, stride=2)
         ctx.save_for_backward(x, x_amax)
         ctx.wparam = weight
         ctx.cfg = (bias is not None, groups)
-        if y_amax is not None:
-            ctx.mark_non_differentiable(y_amax)
         return y, y_amax
 
     @staticmethod
@@ -1074,26 +1071,17 @@ class _XConvS2(torch.autograd.Function):
         need = ctx.needs_input_grad
         N, Cin, H, W = x.shape
         h16 = _is16(gy)
-        gx = gw = gb = None
-        want_amax = (need[0] or need[2]) and not h16
-        if has_bias and need[3] and gy.dtype == torch.float32 and not AB['no_chansum']:
-            gb = chansum(gy, want_amax=want_amax and known_amax(gy) is None)
-        g_amax = amax_of(gy) if want_amax else None
+        gx = gw = None
+        gb, g_amax = _gy_reductions(gy, has_bias and need[3], (need[0] or need[2]) and not h16)
         if need[0]:
-            gx_amax = _gs(3) if h16 else new_scalar(gy.device)
-            gx = _xconv_run(gy, xconv_packed(weight, True, groups), Cin, 3, mask_src=x if ctx.in_site is not None else None,
-                            groups=groups, x_amax=g_amax, y_amax=gx_amax, stride=-2, out_hw=(H, W))
-            if not h16:
-                set_amax(gx, gx_amax)
-            if ctx.in_site is not None:
-                ctx.in_site.wrote(gx, None if h16 else gx_amax)
+            gx = _xconv_bwd_data(ctx, gy, g_amax, weight, groups, x if ctx.in_site is not None else None, stride=-2, out_hw=(H, W))
         if need[2]:
             gyf = torch.empty(N, gy.shape[1], H, W, device=gy.device, dtype=gy.dtype)       # zero-interleaved gradient
             _lib.check(_lib.load().dvd_subsample2_bwd(_p(gy), _p(gyf), int(h16), N * gy.shape[1], H, W, _stream()),
                        'dvd_subsample2_bwd')
             gw = xconv_wgrad(x, gyf, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax)
         if has_bias and need[3] and gb is None:
-            gb = gy.sum((0, 2, 3), dtype=torch.float32) * _gs(1) if h16 else gy.sum((0, 2, 3))
+            gb = _bias_grad_sum(gy)
         return gx, None, gw, gb, None, None
 
 
@@ -1102,8 +1090,7 @@ def xconv_s2_supported(x, weight, groups):
     buffer-addressed main loop), grouped layers with at least 32 channels per group."""
     cpg = weight.shape[1]
     return (x.is_cuda and x.dtype in ACT_DTYPES and weight.dtype == torch.float32 and tuple(weight.shape[2:]) == (3, 3) and
-            cpg % 16 == 0 and (weight.shape[0] // groups) % 16 == 0 and (groups == 1 or cpg >= 32) and
-            not AB['no_xconv'] and not AB['no_s2'])
+            cpg % 16 == 0 and (weight.shape[0] // groups) % 16 == 0 and (groups == 1 or cpg >= 32) and not AB['no_s2'])
 
 
 def _xconv_s2(x, weight, bias, groups=1):
@@ -1116,12 +1103,10 @@ def _xconv(x, weight, bias, residual, relu_in, res_relu, groups=1, alias=False, 
     """_XConv with the max|.| scalars threaded through: the input's is looked up (or computed), the output's attached.
     alias=True returns (y, alias of x), see _XConv."""
     x_amax = None if _is16(x) else amax_of(x)
-    in_site = getattr(x, '_dvd_site', None)
-    if alias:
-        y, y_amax, xa = _XConv.apply(x, x_amax, weight, bias, residual, relu_in, res_relu, groups, True, res_unmasked, in_site)
-        return set_amax(y, y_amax), set_amax(xa, x_amax)
-    y, y_amax = _XConv.apply(x, x_amax, weight, bias, residual, relu_in, res_relu, groups, False, res_unmasked, in_site)
-    return set_amax(y, y_amax)
+    out = _XConv.apply(x, x_amax, weight, bias, residual, relu_in, res_relu, groups, bool(alias), res_unmasked,
+                       getattr(x, '_dvd_site', None))
+    y = set_amax(out[0], out[1])
+    return (y, set_amax(out[2], x_amax)) if len(out) == 3 else y
 
 
 def wgrad_reports_rowsum(wshape, groups):
@@ -1130,84 +1115,49 @@ def wgrad_reports_rowsum(wshape, groups):
 
 
 def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rowsum=None):
-    """dW[co][ci][tap] = sum_{n,p} gy[n][co][p] * act(x)[n][ci][p + tap]."""
+    """dW[co][ci][tap] = sum_{n,p} gy[n][co][p] * act(x)[n][ci][p + tap] on the split-operand MFMA kernels of csrc/xwgrad3.hip:
+    1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 (xwgradk: the hourglass's inception branches and the stem's
+    space-to-depth form).  fp16 operands take one MFMA per product and the result times 1 / (loss scale) (H16).
+    rowsum: [Cout] tensor that receives sum_{n,p} gy[n][co][p] from the dense fp32 1x1 kernel (it sums the rows it stages
+    anyway, see wgrad_reports_rowsum)."""
+    Cout, KS = wshape[0], wshape[2]
+    h16 = _is16(gy)
+    if h16 and not _is16(x):
+        raise RuntimeError('xconv_wgrad: fp16 gradient with an fp32 activation')
+    if KS not in (1, 3, 5, 7, 11) or (groups > 1 and KS != 3):
+        raise RuntimeError('xconv: the weight gradient exists for 1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 kernels '
+                           '(got %s, %d groups)' % (tuple(wshape), groups))
+    # the kernel family and the integer that follows N, Cin, Cout, H, W in its argument lists; DVD_AB=no_xwgrad3: the dense fp32
+    # gradients on the exact-fp32 MFMA kernel (csrc/xwgrad.hip) that the split-operand ones replaced
+    if AB['no_xwgrad3'] and groups == 1 and not h16:
+        family, extra = 'dvd_xwgrad', (KS,)
+    elif KS == 1:
+        family, extra = 'dvd_xwgrad1s', ()
+    elif KS == 3:
+        family, extra = 'dvd_xwgrad3', (groups,)
+    else:
+        family, extra = 'dvd_xwgradk', (KS,)
     lib = _lib.load()
-    if _is16(gy):        # fp16 operands: one MFMA per product, result times 1 / (loss scale) (csrc/xwgrad3.hip H16)
-        if not _is16(x):
-            raise RuntimeError('xconv_wgrad: fp16 gradient with an fp32 activation')
-        if wshape[2] not in (1, 3, 5, 7, 11) or (groups > 1 and wshape[2] != 3):
-            raise RuntimeError('xconv: the fp16 weight gradient exists for 1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 '
-                               'kernels (got %s)' % (tuple(wshape),))
-        N, Cin, H, W = x.shape
-        gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        if wshape[2] in (5, 7, 11):      # the hourglass's inception branches (csrc/xwgrad3.hip xwgradk, H16)
-            KS = wshape[2]
-            ws = _workspace(lib.dvd_xwgradk_workspace_bytes(N, Cin, wshape[0], H, W, KS), x.device)
-            _lib.check(lib.dvd_xwgradk_h(_p(x), _p(gy), _p(_gs(1)), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, wshape[0],
-                                         H, W, KS, int(bool(relu_in)), _stream()), 'dvd_xwgradk_h')
-        elif wshape[2] == 3:
-            ws = _workspace(lib.dvd_xwgrad3_workspace_bytes(N, Cin, wshape[0], H, W, groups), x.device)
-            _lib.check(lib.dvd_xwgrad3_h(_p(x), _p(gy), _p(_gs(1)), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, wshape[0],
-                                         H, W, groups, int(bool(relu_in)), _stream()), 'dvd_xwgrad3_h')
-        else:
-            ws = _workspace(lib.dvd_xwgrad1s_workspace_bytes(N, Cin, wshape[0], H, W), x.device)
-            _lib.check(lib.dvd_xwgrad1s_h(_p(x), _p(gy), _p(_gs(1)), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, wshape[0],
-                                          H, W, int(bool(relu_in)), _stream()), 'dvd_xwgrad1s_h')
-        return gw
-    if x_amax is None:
-        x_amax = amax_of(x)
-    if g_amax is None:
-        g_amax = amax_of(gy)
-    if groups > 1:                                                          # grouped: 3x3 only (ResNeXt stage 4)
-        if wshape[2] != 3:
-            raise RuntimeError('xconv: grouped weight gradient exists for 3x3 kernels only')
-        N, Cin, H, W = x.shape
-        gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        ws = _workspace(lib.dvd_xwgrad3_workspace_bytes(N, Cin, wshape[0], H, W, groups), x.device)
-        _lib.check(lib.dvd_xwgrad3(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin,
-                                   wshape[0], H, W, groups, int(bool(relu_in)), _stream()), 'dvd_xwgrad3')
-        return gw
-    if wshape[2] in (1, 3) and not AB['no_xwgrad3']:      # split-operand MFMA (csrc/xwgrad3.hip)
-        N, Cin, H, W = x.shape
-        Cout = wshape[0]
-        gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        ws_bytes = (lib.dvd_xwgrad3_workspace_bytes(N, Cin, Cout, H, W, 1) if wshape[2] == 3 else
-                    lib.dvd_xwgrad1s_workspace_bytes(N, Cin, Cout, H, W))
-        ws = _workspace(ws_bytes, x.device)
-        if wshape[2] == 3:
-            _lib.check(lib.dvd_xwgrad3(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N,
-                                       Cin, Cout, H, W, 1, int(bool(relu_in)), _stream()), 'dvd_xwgrad3')
-        else:
-            # rowsum: [Cout] tensor that receives sum_{n,p} gy[n][co][p] (the wide kernel sums the rows it stages anyway)
-            _lib.check(lib.dvd_xwgrad1s_rowsum(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(rowsum), _p(ws),
-                                               ctypes.c_size_t(ws.numel()), N, Cin, Cout, H, W, int(bool(relu_in)), _stream()),
-                       'dvd_xwgrad1s_rowsum')
-        return gw
-    if wshape[2] in (5, 7, 11) and not AB['no_xwgrad3']:      # split-operand MFMA with KS kernel rows (csrc/xwgrad3.hip xwgradk)
-        N, Cin, H, W = x.shape
-        Cout, _, KS, _ = wshape
-        gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        ws = _workspace(lib.dvd_xwgradk_workspace_bytes(N, Cin, Cout, H, W, KS), x.device)
-        _lib.check(lib.dvd_xwgradk(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, Cout,
-                                   H, W, KS, int(bool(relu_in)), _stream()), 'dvd_xwgradk')
-        return gw
-    if (wshape[2] in (1, 3) and not AB['no_xwgrad']) or wshape[2] in (5, 7, 11):
-        # exact-fp32 MFMA kernel (csrc/xwgrad.hip): the A/B fall-back of the small kernels, and -- round 4 -- THE weight gradient
-        # of the hourglass's 5x5 / 7x7 / 11x11 inception branches and of the stem's 5x5 space-to-depth form (round 3: MIOpen)
-        N, Cin, H, W = x.shape
-        Cout, _, KS, _ = wshape
-        gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-        nws = lib.dvd_xwgrad_workspace_bytes(N, Cin, Cout, H, W, KS)
-        ws = _workspace(nws, x.device)
-        _lib.check(lib.dvd_xwgrad(_p(x), _p(gy), _p(gw), _p(ws), ctypes.c_size_t(ws.numel()), N, Cin, Cout, H, W, KS,
-                                  int(bool(relu_in)), _stream()), 'dvd_xwgrad')
-        return gw
-    if AB['no_xwgrad'] and wshape[2] in (1, 3):            # A/B only: MIOpen's weight-gradient kernels
-        xin = torch.relu(x) if relu_in else x
-        KS = wshape[2]
-        return torch.ops.aten.convolution_backward(gy, xin, torch.empty(wshape, device=x.device), None, [1, 1],
-                                                   [KS // 2, KS // 2], [1, 1], False, [0, 0], 1, [False, True, False])[1]
-    raise RuntimeError('xconv: no weight-gradient kernel for a %dx%d convolution (1, 3, 5, 7, 11 are covered)' % (wshape[2], wshape[3]))
+    N, Cin, H, W = x.shape
+    dims = (N, Cin, Cout, H, W) + extra
+    if not h16:                                 # the operands' scales (fp16 operands carry none)
+        if x_amax is None:
+            x_amax = amax_of(x)
+        if g_amax is None:
+            g_amax = amax_of(gy)
+    gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
+    ws = _workspace(getattr(lib, family + '_workspace_bytes')(*dims), x.device)
+    tail = (_p(gw), _p(ws), ctypes.c_size_t(ws.numel())) + dims + (int(bool(relu_in)), _stream())
+    if h16:
+        _lib.check(getattr(lib, family + '_h')(_p(x), _p(gy), _p(_gs(1)), *tail), family + '_h')
+    elif family == 'dvd_xwgrad':
+        _lib.check(lib.dvd_xwgrad(_p(x), _p(gy), *tail), family)
+    elif family == 'dvd_xwgrad1s':
+        _lib.check(lib.dvd_xwgrad1s_rowsum(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(rowsum), *tail[1:]),
+                   'dvd_xwgrad1s_rowsum')
+    else:
+        _lib.check(getattr(lib, family)(_p(x), _p(x_amax), _p(gy), _p(g_amax), *tail), family)
+    return gw
 
 
 class _XConvBn(torch.autograd.Function):
@@ -1226,15 +1176,12 @@ class _XConvBn(torch.autograd.Function):
         if residual is not None:
             residual = residual.contiguous()
         Cout, _, KS, _ = weight.shape
-        y_amax = None if _is16(x) else new_scalar(x.device)
+        y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, KS, bias=cbias, residual=residual, relu_out=relu,
-                       groups=groups, bn=(gamma, beta, mean, var, eps), x_amax=x_amax,
-                       y_amax=_fwd_monitor() if _is16(x) else y_amax)
+                       groups=groups, bn=(gamma, beta, mean, var, eps), x_amax=x_amax, y_amax=amax_slot)
         ctx.save_for_backward(x, y if relu else None, gamma, mean, var, cbias, x_amax)
         ctx.wparam = weight
         ctx.cfg = (float(eps), bool(relu), residual is not None, groups)
-        if y_amax is not None:
-            ctx.mark_non_differentiable(y_amax)
         if alias:
             return y, y_amax, x
         return y, y_amax
@@ -1276,16 +1223,9 @@ class _XConvBn(torch.autograd.Function):
                                             int(h16), _p(_gs(1)) if h16 else None, N, Cout, H * W, int(mask), _p(g_amax),
                                             _stream()), 'dvd_bnrelu_bwd')
         gx = gw = gcb = gg = None
-        if need[0]:
-            gx_amax = _gs(3) if h16 else new_scalar(gy.device)
-            gx = _xconv_run(g, xconv_packed_scaled(weight, groups, gamma, var, eps), Cing * groups, KS, groups=groups,
-                            x_amax=g_amax, y_amax=gx_amax,
-                            residual=g_alias.contiguous() if g_alias is not None else None,   # + the other consumers' gradient
-                            mask_src=x if ctx.in_site is not None else None)                  # ... * [x > 0] for the site x came from
-            if not h16:
-                set_amax(gx, gx_amax)
-            if ctx.in_site is not None:
-                ctx.in_site.wrote(gx, None if h16 else gx_amax)
+        if need[0]:                 # (+ the other consumers' gradient) * [x > 0] for the site x came from
+            gx = _xconv_bwd_data(ctx, g, g_amax, weight, groups, x if ctx.in_site is not None else None, g_alias,
+                                 bn_scale=(gamma, var, eps))
         elif g_alias is not None:
             gx = g_alias
         if need_w:
@@ -1307,29 +1247,24 @@ def conv_bn_act(conv, bn, x, residual=None, relu=True, alias=False):
     alias=True returns (y, x'): x' carries x's values and must be used by every OTHER consumer of x (the block's shortcut);
     on the fused path their gradient is then added inside this convolution's backward-data kernel instead of by autograd's
     accumulation pass (see _XConv); on the other paths x' is x itself."""
-    if (x.is_cuda and x.dtype in ACT_DTYPES and not bn.training and bn.track_running_stats and
-            isinstance(conv, nn.Conv2d) and not AB['no_bnfuse']):
+    if x.is_cuda and x.dtype in ACT_DTYPES and not bn.training and bn.track_running_stats and isinstance(conv, nn.Conv2d):
         xin = None
         if xconv_supported(conv, x):
             xin = x
-        elif (conv.kernel_size == (1, 1) and conv.groups == 1 and tuple(conv.padding) == (0, 0) and
-              conv.stride[0] == conv.stride[1] and conv.stride[0] > 1 and conv.weight.dtype == torch.float32 and
-              not AB['no_xconv']):
+        elif xconv_strided_1x1_supported(conv, x):
             xin = _subsample(x, conv.stride[0])
         if xin is not None:
             gamma, beta = (bn.weight, bn.bias) if bn.affine else (None, None)
             x_amax = None if _is16(xin) else amax_of(xin)
             in_site = getattr(xin, '_dvd_site', None)           # xin is a BatchNorm+ReLU site's output (see _Site)
             out_site = _Site() if relu else None
-            if alias and xin is x and not AB['no_alias']:
-                y, y_amax, xa = _XConvBn.apply(xin, x_amax, conv.weight, conv.bias, gamma, beta, bn.running_mean,
-                                               bn.running_var, bn.eps, residual, relu, conv.groups, True, in_site, out_site)
-                y._dvd_site = out_site
-                return set_amax(y, y_amax), set_amax(xa, x_amax)
-            y, y_amax = _XConvBn.apply(xin, x_amax, conv.weight, conv.bias, gamma, beta, bn.running_mean,
-                                       bn.running_var, bn.eps, residual, relu, conv.groups, False, in_site, out_site)
-            y._dvd_site = out_site
-            return (set_amax(y, y_amax), x) if alias else set_amax(y, y_amax)
+            out = _XConvBn.apply(xin, x_amax, conv.weight, conv.bias, gamma, beta, bn.running_mean, bn.running_var, bn.eps,
+                                 residual, relu, conv.groups, bool(alias and xin is x and not AB['no_alias']), in_site, out_site)
+            out[0]._dvd_site = out_site
+            y = set_amax(out[0], out[1])
+            if len(out) == 3:
+                return y, set_amax(out[2], x_amax)
+            return (y, x) if alias else y
     y = bn_eval_relu(bn, conv(x), residual=residual, relu=relu)
     return (y, x) if alias else y
 
@@ -1340,7 +1275,14 @@ def xconv_supported(conv, x):
             (conv.groups == 1 or (k[0] == 3 and conv.in_channels // conv.groups >= 32)) and
             k[0] == k[1] and k[0] % 2 == 1 and k[0] <= 11 and tuple(conv.stride) == (1, 1) and
             tuple(conv.dilation) == (1, 1) and tuple(conv.padding) == (k[0] // 2, k[0] // 2) and
-            conv.padding_mode == 'zeros' and not AB['no_xconv'])
+            conv.padding_mode == 'zeros')
+
+
+def xconv_strided_1x1_supported(conv, x):
+    """A dense strided 1x1 convolution without padding (the ResNeXt down-sampling shortcut): the 1x1 kernel on the sub-sampled
+    input, `_subsample(x, conv.stride[0])`."""
+    return (x.is_cuda and x.dtype in ACT_DTYPES and conv.weight.dtype == torch.float32 and conv.kernel_size == (1, 1) and
+            conv.groups == 1 and tuple(conv.padding) == (0, 0) and conv.stride[0] == conv.stride[1] and conv.stride[0] > 1)
 
 
 def xconv2d(conv, x, relu_in=False, residual=None, res_relu=False, alias=False, res_unmasked=False):
@@ -1352,8 +1294,7 @@ def xconv2d(conv, x, relu_in=False, residual=None, res_relu=False, alias=False, 
             y = _xconv(x, conv.weight, conv.bias, residual, relu_in, res_relu, conv.groups)
             return (y, x) if alias else y
         return _xconv(x, conv.weight, conv.bias, residual, relu_in, res_relu, conv.groups, alias, res_unmasked)
-    if x.is_cuda and x.dtype in ACT_DTYPES and conv.groups == 1 and tuple(conv.stride) == (1, 1) and \
-            not AB['no_xconv']:
+    if x.is_cuda and x.dtype in ACT_DTYPES and conv.groups == 1 and tuple(conv.stride) == (1, 1):
         raise RuntimeError('xconv2d: convolution %r is not covered by the HIP kernels' % (conv,))
     y = conv(F.relu(x) if relu_in else x)
     if residual is not None:
@@ -1374,15 +1315,12 @@ class XConv2d(nn.Conv2d):
         k, st = self.kernel_size, self.stride
         if (x.is_cuda and x.dtype in ACT_DTYPES and k == (3, 3) and st[0] == st[1] and st[0] > 1 and
                 tuple(self.padding) == (1, 1) and tuple(self.dilation) == (1, 1) and
-                (self.groups == 1 or self.in_channels // self.groups >= 32) and not AB['no_xconv']):
+                (self.groups == 1 or self.in_channels // self.groups >= 32)):
             if st[0] == 2 and xconv_s2_supported(x, self.weight, self.groups):
                 return _xconv_s2(x, self.weight, self.bias, self.groups)
             # out[i][j] of a stride-s 'same' 3x3 convolution is out1[s*i][s*j] of the stride-1 one
             y = _xconv(x, self.weight, self.bias, None, False, False, self.groups)
             return _subsample(y, st[0])
-        if (x.is_cuda and x.dtype in ACT_DTYPES and self.kernel_size == (1, 1) and self.groups == 1 and
-                tuple(self.padding) == (0, 0) and self.stride[0] == self.stride[1] and self.stride[0] > 1 and
-                not AB['no_xconv']):
-            st = self.stride[0]
-            return _xconv(_subsample(x, st), self.weight, self.bias, None, False, False)
+        if xconv_strided_1x1_supported(self, x):
+            return _xconv(_subsample(x, st[0]), self.weight, self.bias, None, False, False)
         return super().forward(x)

@@ -236,8 +236,7 @@ def test_grouped_conv_modules_on_cpu_are_plain_convolutions():
         x = torch.randn(2, 64, 9, 14)
         assert torch.equal(m(x), ref(x))
     # the A/B switches are exactly these, and none is on by default (DVD_AB is an experimenter's tool, not a configuration)
-    assert set(C.AB) == {'gconv32', 'no_c16', 'no_xwgrad3', 'no_xwgrad', 'no_bnfuse', 'no_xconv', 'no_alias', 'no_maskfuse',
-                         'no_chansum', 'no_packplan', 'no_s2', 'rowsum'} and not any(C.AB.values())
+    assert set(C.AB) == {'gconv32', 'no_xwgrad3', 'no_alias', 'no_maskfuse', 'no_s2', 'rowsum'} and not any(C.AB.values())
 
 
 def test_site_handover_detects_a_modified_or_replaced_gradient():
