@@ -166,6 +166,10 @@ SIGNATURES = {
                                                                              c_int, c_void_p, c_void_p, c_void_p]),
     'dvd_upsample_bilinear_fwd_t': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dvd_upsample_bilinear_bwd_t': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # bicubic resize of a MidasNet with a working resolution (csrc/bicubic.hip; additive in ABI 8)
+    'dvd_bicubic_fwd': (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    'dvd_bicubic_bwd_workspace_bytes': (c_size_t, [c_longlong, c_int, c_int, c_int, c_int]),
+    'dvd_bicubic_bwd': (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     'dvd_gconv3x3_c8_fwd_t': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dvd_gconv3x3_c8_bwd_data_t': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'dvd_gconv3x3_c8_bwd_weight_t': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int,

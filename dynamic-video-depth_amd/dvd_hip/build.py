@@ -31,6 +31,7 @@ SOURCES = [
     ('gconv32.hip', []),
     ('surfaces.hip', ['-ffp-contract=off']),
     ('upsample.hip', ['-ffp-contract=off']),
+    ('bicubic.hip', ['-ffp-contract=off']),
     ('bnrelu.hip', []),
     ('amax.hip', []),
     ('xconv.hip', []),

@@ -62,6 +62,26 @@ def images_per_chunk(opt, auto_chunk=None):
     return max(1, c if c > 0 else int(auto_chunk or 48))
 
 
+def working_size(opt, net=None):
+    """(H, W) at which the depth net works when that is not the frame size -- opt.midas_resize, else the `resize` the net was
+    built with (the dataset-name rule of Model.__init__) -- or None."""
+    size = getattr(opt, 'midas_resize', None)
+    if size is None:
+        size = getattr(net, 'resize', None)
+    return None if size is None else (int(size[0]), int(size[1]))
+
+
+def working_pixels(n_images, H, W, resize=None):
+    """Pixels the depth net works on for n_images frames of H x W: a kept slot's autograd state scales with these."""
+    return n_images * (H * W if resize is None else resize[0] * resize[1])
+
+
+def resize_extra_bytes(n_images, H, W, resize=None):
+    """What a slot holds at FRAME size on top of its working-size state when the net resizes: two fp32 planes per image
+    (the resized depth and its gradient)."""
+    return 0 if resize is None else 2 * 4 * n_images * H * W
+
+
 # What DepthRunner.graphs holds.  _Captured: one graph and the algorithmic work per kernel class counted at its capture
 # (bench.py roofline_mfma: added at every replay).  x / y / gy: the static input, output and output-gradient buffers.
 _Captured = namedtuple('_Captured', 'graph flops')
@@ -88,11 +108,12 @@ class DepthRunner:
         self.opt, self.net, self.flat, self.act_fp16 = opt, net, flat, bool(act_fp16)
         self.graphs = {}             # _graph_key / _slot_key -> _Recompute / _Slot; None: denied, trimmed, or its capture failed
         self.keep_bytes = 0          # HBM held by kept-activation graph slots
-        self.keep_per_px = 0.0       # measured bytes per image pixel of a captured slot
+        self.keep_per_px = 0.0       # measured bytes per pixel the net works on (working_pixels) of a captured slot
         self.auto_chunk = None       # --depth_chunk 0: images per slot, chosen at the first training step that keeps slots
         self.pool_bytes = 0          # HBM reserved by the private pools of all captured graphs
         self.denied = {}             # slot key -> step at which it was last denied / trimmed (retried 16 steps later)
         self.step_no = 0
+        self.resize = working_size(opt, net)     # None: the net works at the frame size
 
     def begin_step(self):
         self.step_no += 1
@@ -222,7 +243,7 @@ class DepthRunner:
 
     # -- planning -------------------------------------------------------------------------------------------------------
     def slot_bytes_per_px(self):
-        """Autograd state a kept slot holds per image pixel: measured on the slots captured so far, else an a-priori figure
+        """Autograd state a kept slot holds per pixel the net works on: measured on the slots captured so far, else an a-priori figure
         (as measured in round 6: MiDaS with fused epilogues 4.8 KB -- 55.8 GB per 48 images at 384x672 --, 2.5 KB with fp16
         activations, the hourglass 6.7 KB; rounds 4-5 assumed 4.4 / 2.4 KB).  The hourglass with fp16 activations: 4.9 KB
         (keep_per_px after two steps of 48 pairs at 384x672 with 16-image slots on MI355X: 4 878 bytes, fp32 6 657)."""
@@ -240,7 +261,7 @@ class DepthRunner:
         free, total = self.free_hbm(device)
         budget = float(getattr(self.opt, 'depth_keep_gb', 150.0)) * 2 ** 30
         avail = min(budget, free - mlp_need - head_room_fraction(parallel.world_size(), total) * total)
-        per_img = HW * self.slot_bytes_per_px()
+        per_img = working_pixels(1, HW, 1, self.resize) * self.slot_bytes_per_px() + resize_extra_bytes(1, HW, 1, self.resize)
         for c in (48, 24, 16):
             cc = min(c, B)
             if 2 * B * per_img + 2 * (-(-B // cc)) * 1.5 * 2 ** 30 <= avail:
@@ -356,8 +377,10 @@ class DepthRunner:
             del self.graphs[k]
         # bytes a slot will hold: measured on the slots captured so far (per image and pixel), a-priori figure (MiDaS with
         # fused epilogues: ~4.1 KB per pixel, ~2.2 KB with fp16 activations) for the first one, + packed weights
-        n_px = chunk.shape[0] * chunk.shape[2] * chunk.shape[3]
-        est = int(n_px * self.slot_bytes_per_px() + 1.5 * 2 ** 30)
+        # (pixels the net works on: with a working resolution the state scales with that, + the frame-size planes of the resize)
+        n_px = working_pixels(chunk.shape[0], chunk.shape[2], chunk.shape[3], self.resize)
+        extra = resize_extra_bytes(chunk.shape[0], chunk.shape[2], chunk.shape[3], self.resize)
+        est = int(n_px * self.slot_bytes_per_px() + extra + 1.5 * 2 ** 30)
         free, total = self.free_hbm(chunk.device)
         budget = float(getattr(self.opt, 'depth_keep_gb', 150.0)) * 2 ** 30
         # room that must stay free: the MLP stashes of phase 2 + 8 % head room + (unless this is the last slot of a step
@@ -380,7 +403,7 @@ class DepthRunner:
         if entry is not None:
             self.keep_bytes += entry.bytes
             self.pool_bytes += entry.bytes
-            self.keep_per_px = max(self.keep_per_px, entry.bytes / float(n_px))
+            self.keep_per_px = max(self.keep_per_px, (entry.bytes - extra) / float(n_px))
         return entry
 
     def _capture_slot(self, chunk, fid):

@@ -346,6 +346,30 @@ class _SfStep:
         return scalars, inv
 
 
+def midas_resize_of(opt):
+    """opt.midas_resize, validated: None (the default), or the (H, W) at which MiDaS works whatever the frame size -- the
+    reference only has its dataset-name rule for [224, 384] (scene_flow_motion_field.py:84-94).  An attribute, not a flag of
+    add_arguments (that flag set is the reference's); checkpointed option dictionaries carry it like any other attribute."""
+    size = getattr(opt, 'midas_resize', None)
+    if size is None:
+        return None
+    try:
+        h, w = size
+        ok = int(h) == h and int(w) == w
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('opt.midas_resize must be an (H, W) pair of integers, got %r' % (size,))
+    h, w = int(h), int(w)
+    if h <= 0 or w <= 0 or h % 32 or w % 32:
+        raise ValueError('opt.midas_resize=%r: both values must be positive multiples of 32 (the total stride of the MiDaS '
+                         'encoder)' % (size,))
+    if not getattr(opt, 'midas', False):
+        raise ValueError('opt.midas_resize=%r needs --midas: the working resolution belongs to the MiDaS depth net, the '
+                         'hourglass has none' % (size,))
+    return h, w
+
+
 class Model(NetInterface):
     @classmethod
     def add_arguments(cls, parser):
@@ -413,8 +437,11 @@ class Model(NetInterface):
                             'time_stamp_1', 'time_stamp_2', 'frame_id_1', 'frame_id_2', 'time_step']
         self.gt_names = []
         self.requires = list(set().union(self.input_names, self.gt_names))
+        explicit = midas_resize_of(opt)
         if opt.midas:
             resize = [224, 384] if any(k in opt.dataset for k in ('real_video', 'korean', 'mctest', 'cube')) else None
+            if explicit is not None:        # opt.midas_resize takes precedence over the reference's dataset-name rule
+                resize = list(explicit)
             path = configs.midas_pretrain_path if os.path.exists(configs.midas_pretrain_path) else None
             if path is None:
                 warnings.warn('MiDaS checkpoint %s not found: random weights' % configs.midas_pretrain_path)

@@ -286,7 +286,8 @@ BYTE_CLASSES = ('bnrelu_fwd', 'bnrelu_bwd', 'upsample_fwd', 'upsample_bwd', 'ama
                 'adam', 'geometry', 'gather')
 BYTE_CLASS_KERNELS = {
     'bnrelu_fwd': ('bnrelu_fwd_kernel',), 'bnrelu_bwd': ('bnrelu_bwd', 'bn_mask', 'bnrelu_sum'),
-    'upsample_fwd': ('upsample_bilinear_fwd',), 'upsample_bwd': ('upsample_bilinear_bwd', 'upsample_bwd'),
+    'upsample_fwd': ('upsample_bilinear_fwd', 'bicubic_fwd_kernel'),
+    'upsample_bwd': ('upsample_bilinear_bwd', 'upsample_bwd', 'bicubic_bwd_'),
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
@@ -392,6 +393,50 @@ def gather_pairs(tensors, perm, out=None):
             it.src, it.dst, it.bytes_per_pair = t.data_ptr(), o.data_ptr(), t.numel() // B * t.element_size()
         _lib.check(lib.dvd_gather_pairs(items, len(part), _p(perm), B, _stream()), 'dvd_gather_pairs')
     return out
+
+
+class _BicubicResize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size, mean, std):
+        N, C, H, W = x.shape
+        Ho, Wo = size
+        y = torch.empty(N, C, Ho, Wo, device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().dvd_bicubic_fwd(_p(x), _p(y), N * C, H, W, Ho, Wo, _p(mean), _p(std), C, _stream()), 'dvd_bicubic_fwd')
+        ctx.shape = (N, C, H, W, Ho, Wo)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        N, C, H, W, Ho, Wo = ctx.shape
+        gy = _dev32(gy, 'gy')
+        lib = _lib.load()
+        gx = torch.empty(N, C, H, W, device=gy.device, dtype=torch.float32)
+        # (a plain allocation, not the cached workspace: its size follows the shape, and inside a graph capture it belongs to
+        #  the graph's pool either way)
+        ws = torch.empty(max(1, lib.dvd_bicubic_bwd_workspace_bytes(N * C, H, W, Ho, Wo)), device=gy.device, dtype=torch.uint8)
+        _lib.check(lib.dvd_bicubic_bwd(_p(gy), _p(gx), N * C, H, W, Ho, Wo, _p(ws), ws.numel(), _stream()), 'dvd_bicubic_bwd')
+        return gx, None, None, None
+
+
+def bicubic_resize(x, size, mean=None, std=None):
+    """F.interpolate(x, size=size, mode='bicubic', align_corners=True) of an fp32 GPU tensor [N,C,H,W] (csrc/bicubic.hip),
+    differentiable in x.  mean / std (GPU fp32 tensors of C values, both or neither): the resize of (x - mean[c]) / std[c] in
+    one pass -- MidasNet's input normalisation fused into its input resize; that form has no gradient (an image needs none)."""
+    x = _dev32(x, 'x')
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError('bicubic_resize: x must be a non-empty [N,C,H,W] tensor, got shape %s' % (tuple(x.shape),))
+    Ho, Wo = (int(v) for v in size)
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError('bicubic_resize: size must be positive, got %s' % ((Ho, Wo),))
+    if (mean is None) != (std is None):
+        raise RuntimeError('bicubic_resize: mean and std go together')
+    if mean is not None:
+        mean, std = _dev32(mean, 'mean'), _dev32(std, 'std')
+        if mean.numel() != x.shape[1] or std.numel() != x.shape[1] or mean.device != x.device or std.device != x.device:
+            raise RuntimeError('bicubic_resize: mean / std must hold one value per channel (%d) on the device of x' % x.shape[1])
+        if x.requires_grad:
+            raise RuntimeError('bicubic_resize: the normalising form has no backward (x must not require a gradient)')
+    return _BicubicResize.apply(x, (Ho, Wo), mean, std)
 
 
 def warp_loss_select(variant='tiled', tile=-1, px=0, strip_rows=0, strip_shape=0):

@@ -73,8 +73,8 @@ int dvd_flop_counters(double* out, int n, int reset);
 enum {
   DVD_BYTES_BNRELU_FWD = 0, /* bnrelu_fwd_kernel: x (+ residual) in, y out                                                       */
   DVD_BYTES_BNRELU_BWD = 1, /* bnrelu_bwd kernels: gy, y / x in, gx (+ g_residual) out, per-channel sums                          */
-  DVD_BYTES_UPSAMPLE_FWD = 2,
-  DVD_BYTES_UPSAMPLE_BWD = 3,
+  DVD_BYTES_UPSAMPLE_FWD = 2, /* bilinear up-sampling and the bicubic resize, forward                                         */
+  DVD_BYTES_UPSAMPLE_BWD = 3, /* ... and their backward                                                                        */
   DVD_BYTES_AMAX = 4,       /* amax_kernel: one read of the tensor                                                                */
   DVD_BYTES_PACK = 5,       /* weight maximum + fragment packing of the convolution weights                                       */
   DVD_BYTES_POOL = 6,       /* max-pool of the stem, forward and backward                                                         */
@@ -358,6 +358,21 @@ int dvd_upsample_bilinear_fwd(const float* x, float* y, long long planes, int H_
                               int align_corners, dvd_stream_t stream);
 int dvd_upsample_bilinear_bwd(const float* gy, float* gx, long long planes, int H_in, int W_in, int H_out,
                               int W_out, int align_corners, dvd_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Bicubic resize of fp32 planes [planes, H_in, W_in] -> [planes, H_out, W_out] with align_corners=True, and its backward
+ * (additive in ABI 8).  Replaces the two F.interpolate(mode='bicubic', align_corners=True) calls of a MidasNet with a working
+ * resolution: third_party/MiDaS.py:221-222 (image -> working size) and :244-245 (depth -> frame size).  ATen's
+ * upsample_bicubic2d arithmetic in fp32 (A = -0.75, taps clamped at the border).  Any sizes, 1 included.
+ * fwd: mean / std are device pointers to `channels` floats, or both NULL; when set every tap is normalised first,
+ * (x - mean[c]) / std[c] with c = plane % channels -- the input normalisation of MiDaS.py:213-218 fused into the resize.
+ * bwd: gx = A^T gy as a gather in a fixed order (no atomics: bit-identical from call to call); the image needs no gradient,
+ * so there is no normalised form.  workspace: dvd_bicubic_bwd_workspace_bytes(...) bytes, written before it is read. */
+int dvd_bicubic_fwd(const float* x, float* y, long long planes, int H_in, int W_in, int H_out, int W_out, const float* mean,
+                    const float* std, int channels, dvd_stream_t stream);
+size_t dvd_bicubic_bwd_workspace_bytes(long long planes, int H_in, int W_in, int H_out, int W_out);
+int dvd_bicubic_bwd(const float* gy, float* gx, long long planes, int H_in, int W_in, int H_out, int W_out, void* workspace,
+                    size_t workspace_bytes, dvd_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * max|x| of a tensor into a device scalar: out[0] = max(out[0], max|x|) (atomic; zero `out` first, or pass a running
