@@ -57,7 +57,14 @@ class GatherItem(ctypes.Structure):         # struct dvd_gather_item
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes_per_pair', c_longlong)]
 
 
+class StoreItem(ctypes.Structure):          # struct dvd_store_item
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes_per_row', c_longlong), ('src_rows', c_int), ('index_row', c_int),
+                ('op', c_int), ('pad', c_int)]
+
+
 GATHER_MAX = 32
+STORE_MAX = 32
+STORE_COPY, STORE_MASK, STORE_FILL = 0, 1, 2
 PtrArr6 = c_void_p * 6
 PtrArr5 = c_void_p * 5
 
@@ -197,6 +204,8 @@ SIGNATURES = {
                                      c_float, c_float, c_int, c_void_p, c_void_p]),
     # mixed frame gaps: the batched pair permutation (addition within ABI 8)
     'dvd_gather_pairs': (c_int, [ctypes.POINTER(GatherItem), c_int, c_void_p, c_int, c_void_p]),
+    # device-resident frame store: the batch assembly of a step (addition within ABI 8)
+    'dvd_store_gather': (c_int, [ctypes.POINTER(StoreItem), c_int, c_void_p, c_longlong, c_int, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -41,6 +41,7 @@ SOURCES = [
     ('a16.hip', []),
     ('pool.hip', []),
     ('gather.hip', []),
+    ('frame_store.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

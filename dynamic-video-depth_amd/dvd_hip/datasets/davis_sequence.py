@@ -30,6 +30,14 @@ DATA_ROOT = './datafiles/davis_processed'
 FRAME_PREFIX, SEQ_PREFIX = 'frames_midas', 'sequences_select_pairs_midas'
 
 
+def epoch_pair_order(n_pairs, manual_seed, epoch):
+    """The permutation of n_pairs pairs that --pairs_per_step draws its steps from in `epoch`: a function of (--manual_seed,
+    epoch) alone, so every rank, `Dataset.pair_order` and datasets/frame_store.py's `Catalogue.order` agree on it."""
+    seed = int(manual_seed or 0)
+    rng = np.random.RandomState((seed * 1000003 + int(epoch)) % (2 ** 32))
+    return [int(i) for i in rng.permutation(int(n_pairs))]
+
+
 class Dataset(data.Dataset):
     @classmethod
     def add_arguments(cls, parser):
@@ -94,9 +102,7 @@ class Dataset(data.Dataset):
         agree, two epochs differ)."""
         epoch = self.epoch if epoch is None else int(epoch)
         if self._order_of is None or self._order_of[0] != epoch:
-            seed = int(getattr(self.opt, 'manual_seed', None) or 0)
-            rng = np.random.RandomState((seed * 1000003 + epoch) % (2 ** 32))
-            self._order_of = (epoch, [int(i) for i in rng.permutation(len(self.pair_list))])
+            self._order_of = (epoch, epoch_pair_order(len(self.pair_list), getattr(self.opt, 'manual_seed', None), epoch))
         return self._order_of[1]
 
     def _samples_per_epoch(self):

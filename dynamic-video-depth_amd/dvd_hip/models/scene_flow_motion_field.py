@@ -869,6 +869,8 @@ class Model(NetInterface):
             img_1, img_2 = batch['img_1'].cpu().numpy(), batch['img_2'].cpu().numpy()
         else:
             img_1 = img_2 = batch['img']
+            if torch.is_tensor(img_1) and img_1.is_cuda:       # a device-resident item (datasets/frame_store.py): np.savez wants host data
+                img_1 = img_2 = img_1.cpu().numpy()
         output = {'batch_size': batch_size, 'img_1': img_1, 'img_2': img_2, **pred_all}
         if 'img' not in batch:
             flows = {'flow_1_2': self._input.flow_1_2, 'flow_2_1': self._input.flow_2_1}

@@ -291,7 +291,7 @@ BYTE_CLASS_KERNELS = {
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel',),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel', 'store_gather_kernel'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 
@@ -393,6 +393,86 @@ def gather_pairs(tensors, perm, out=None):
             it.src, it.dst, it.bytes_per_pair = t.data_ptr(), o.data_ptr(), t.numel() // B * t.element_size()
         _lib.check(lib.dvd_gather_pairs(items, len(part), _p(perm), B, _stream()), 'dvd_gather_pairs')
     return out
+
+
+STORE_OPS = {'copy': _lib.STORE_COPY, 'mask': _lib.STORE_MASK, 'fill': _lib.STORE_FILL}
+
+
+def store_gather(entries, index, host_index=None):
+    """Batch assembly out of a device-resident frame store (dvd_store_gather; datasets/frame_store.py): for every entry
+    (src, dst, op, row), dst[b] = op(src[index[row][b]]) for b < B = dst.shape[0], ONE launch per _lib.STORE_MAX entries.
+      op 'copy'  src [rows, ...] and dst [B, ...] of one dtype and the same bytes per row;
+      op 'mask'  src uint8 [rows, ...], dst fp32 [B, ...] with as many elements per row: dst = 1 - src;
+      op 'fill'  src fp32 [rows], dst fp32 [B, ...]: every element of dst[b] is the scalar src[index[row][b]].
+    index: three rows (first frame, second frame, flow pair) of B ints -- a host array (numpy, CPU tensor, nested lists),
+    uploaded here, or a GPU int32 tensor [3, B] whose rows may be strided (a column slice of an epoch's [3, total]); then
+    host_index, its host copy, saves the read-back that checking the ranges needs otherwise.  Everything is checked on the
+    host -- devices, dtypes, contiguity, sizes, every index against the rows of the tables it selects from -- and a
+    RuntimeError is raised before anything is launched."""
+    import numpy as np
+    entries = list(entries)
+    if not entries:
+        raise RuntimeError('store_gather: no entries')
+    B = int(entries[0][1].shape[0]) if (torch.is_tensor(entries[0][1]) and entries[0][1].dim() > 0) else 0
+    if B <= 0:
+        raise RuntimeError('store_gather: an empty batch')
+    if torch.is_tensor(index) and index.is_cuda:
+        if index.dtype != torch.int32 or index.dim() != 2 or tuple(index.shape) != (3, B) or index.stride(1) != 1 or \
+                index.stride(0) < B:
+            raise RuntimeError('store_gather: index must be a GPU int32 tensor [3, %d] with contiguous rows' % B)
+        host = np.asarray(index.cpu() if host_index is None else host_index)
+    else:
+        host = np.asarray(index.cpu() if torch.is_tensor(index) else index)
+        index = None
+    if host.shape != (3, B) or host.dtype.kind not in 'iu':
+        raise RuntimeError('store_gather: index must hold three rows of %d integers, got %s %s' % (B, host.dtype, host.shape))
+    lo, hi = host.min(axis=1), host.max(axis=1)
+    items = []
+    for i, (src, dst, op, row) in enumerate(entries):
+        if op not in STORE_OPS or row not in (0, 1, 2):
+            raise RuntimeError('store_gather: entry %d: operation %r / index row %r' % (i, op, row))
+        if not (torch.is_tensor(src) and src.is_cuda and torch.is_tensor(dst) and dst.is_cuda):
+            raise RuntimeError('store_gather: entry %d must name GPU tensors (dvd_hip has no CPU path)' % i)
+        if src.device != dst.device:
+            raise RuntimeError('store_gather: entry %d: source and destination on different devices' % i)
+        if not dst.is_contiguous() or not src.is_contiguous():
+            raise RuntimeError('store_gather: entry %d: source and destination must be contiguous' % i)
+        if dst.dim() < 1 or dst.shape[0] != B or dst.numel() == 0 or src.dim() < 1 or src.numel() == 0:
+            raise RuntimeError('store_gather: entry %d: destination %s / source %s for %d pairs' % (
+                i, tuple(dst.shape), tuple(src.shape), B))
+        rows, per_row = int(src.shape[0]), dst.numel() // B
+        if op == 'copy':
+            if src.dtype != dst.dtype:
+                raise RuntimeError('store_gather: entry %d: copy of dtype %s into %s' % (i, src.dtype, dst.dtype))
+            if src.numel() // rows != per_row:
+                raise RuntimeError('store_gather: entry %d: size mismatch, a source row holds %d elements, a destination row %d'
+                                   % (i, src.numel() // rows, per_row))
+        elif op == 'mask':
+            if src.dtype != torch.uint8 or dst.dtype != torch.float32:
+                raise RuntimeError('store_gather: entry %d: mask wants dtype uint8 -> float32, got %s -> %s' % (i, src.dtype, dst.dtype))
+            if src.numel() // rows != per_row:
+                raise RuntimeError('store_gather: entry %d: size mismatch, a source row holds %d elements, a destination row %d'
+                                   % (i, src.numel() // rows, per_row))
+        else:
+            if src.dtype != torch.float32 or dst.dtype != torch.float32:
+                raise RuntimeError('store_gather: entry %d: fill wants dtype float32, got %s -> %s' % (i, src.dtype, dst.dtype))
+            if src.dim() != 1:
+                raise RuntimeError('store_gather: entry %d: size mismatch, fill takes one scalar per table row, got %s' % (
+                    i, tuple(src.shape)))
+        if lo[row] < 0 or hi[row] >= rows:
+            raise RuntimeError('store_gather: entry %d: index row %d spans [%d, %d], outside its table of %d rows' % (
+                i, row, int(lo[row]), int(hi[row]), rows))
+        items.append((src, dst, per_row * dst.element_size(), rows, row, STORE_OPS[op]))
+    if index is None:
+        index = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(entries[0][1].device)
+    lib = _lib.load()
+    stride = int(index.stride(0))
+    for k0 in range(0, len(items), _lib.STORE_MAX):
+        part = items[k0:k0 + _lib.STORE_MAX]
+        arr = (_lib.StoreItem * len(part))()
+        for it, (src, dst, bpr, rows, row, op) in zip(arr, part):
+            it.src, it.dst, it.bytes_per_row, it.src_rows, it.index_row, it.op, it.pad = src.data_ptr(), dst.data_ptr(), bpr, rows, row, op, 0
+        _lib.check(lib.dvd_store_gather(arr, len(part), _p(index), stride, B, _stream()), 'dvd_store_gather')
 
 
 class _BicubicResize(torch.autograd.Function):

@@ -658,6 +658,37 @@ typedef struct dvd_gather_item {
 } dvd_gather_item;
 int dvd_gather_pairs(const dvd_gather_item* items, int n_items, const int* perm, int B, dvd_stream_t stream);
 
+/* Batch assembly out of a device-resident frame store (an addition within ABI 8; csrc/frame_store.hip): ONE launch that writes
+ * row b < B of every tensor k of a table of n_items <= DVD_STORE_MAX tensors from row index[index_row_k * index_stride + b] of
+ * that tensor's source table.  It is the re-arrangement of frames and flow pairs into per-pair tensors that the reference does
+ * on the host -- scripts/preprocess/davis/generate_sequence_midas.py:117-170 when it writes the pair packs, then
+ * datasets/davis_sequence.py:98-115 when it reads them -- done per step on the device (datasets/frame_store.py).
+ * `items` is a HOST array (it travels in the kernel arguments); `index` is a DEVICE array of three rows of ints, index_stride
+ * (>= B) ints apart: by convention row 0 = first frame, 1 = second frame, 2 = flow pair.  src_rows is the number of rows of
+ * the source table: an index outside [0, src_rows) writes nothing for that pair and reads nothing.  Operations, with
+ * bytes_per_row the bytes of one DESTINATION row:
+ *   DVD_STORE_COPY  dst row = src row (bytes_per_row bytes each), any element type; 16-byte accesses where both bases and
+ *                   bytes_per_row are multiples of 16, 4-byte accesses for multiples of 4, bytes otherwise;
+ *   DVD_STORE_MASK  src rows of bytes_per_row / 4 uint8, dst fp32: dst = 1.0f - (float)src, which is the writer's
+ *                   1 - ceil(mask) (:144-147) for every uint8 value;
+ *   DVD_STORE_FILL  src one fp32 per row, dst fp32: every element of the destination row is that value (time-stamp planes).
+ * No arithmetic other than that conversion happens here.  Null pointers, an empty batch, more than DVD_STORE_MAX tensors, an
+ * unknown operation or index row, a misaligned fp32 side or overlapping src / dst return DVD_EINVAL before any HIP call.
+ * The launch's algorithmic bytes are counted under DVD_BYTES_GATHER. */
+#define DVD_STORE_MAX 32
+enum { DVD_STORE_COPY = 0, DVD_STORE_MASK = 1, DVD_STORE_FILL = 2 };
+typedef struct dvd_store_item {
+  const void* src;
+  void* dst;
+  long long bytes_per_row;
+  int src_rows;
+  int index_row;
+  int op;
+  int pad;
+} dvd_store_item;
+int dvd_store_gather(const dvd_store_item* items, int n_items, const int* index, long long index_stride, int B,
+                     dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
