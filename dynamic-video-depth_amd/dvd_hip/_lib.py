@@ -206,6 +206,10 @@ SIGNATURES = {
     'dvd_gather_pairs': (c_int, [ctypes.POINTER(GatherItem), c_int, c_void_p, c_int, c_void_p]),
     # device-resident frame store: the batch assembly of a step (addition within ABI 8)
     'dvd_store_gather': (c_int, [ctypes.POINTER(StoreItem), c_int, c_void_p, c_longlong, c_int, c_void_p]),
+    # opt.share_frames: the depth net once per distinct frame of a step (csrc/frame_union.hip; additions within ABI 8)
+    'dvd_union_gather': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
+    'dvd_union_scatter': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
+    'dvd_union_reduce': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -42,6 +42,7 @@ SOURCES = [
     ('pool.hip', []),
     ('gather.hip', []),
     ('frame_store.hip', ['-ffp-contract=off']),
+    ('frame_union.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

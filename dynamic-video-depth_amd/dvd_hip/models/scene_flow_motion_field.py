@@ -30,6 +30,7 @@ package's HIP kernels (csrc/); the matrix kernels evaluate fp32 products from tw
 lives on the device); `--use_cnn` swaps the MLP for the reference's U-Net scene-flow network (networks/FCNUnet.py) under autograd.
 """
 import contextlib
+import numbers
 import os
 import warnings
 from os import makedirs
@@ -44,6 +45,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
+from . import frame_union
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 
@@ -118,6 +120,7 @@ class _SfStep:
         # warp; the un-masked field still drives the Euler chain and the regulariser
         self.mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
         self.cfg_all = self.warp_cfg(B)
+        self.union = None            # opt.share_frames: (index tables, img_u, fid_u) of phase 1, for phase 3
 
     def warp_cfg(self, n_pairs, mul=None):
         opt = self.opt
@@ -370,6 +373,17 @@ def midas_resize_of(opt):
     return h, w
 
 
+def share_frames_of(opt):
+    """(opt.share_frames, opt.share_quantum), validated: whether a step runs the depth net once per DISTINCT frame
+    (models/frame_union.py), and the multiple its number of union rows is padded to.  Attributes, not flags of add_arguments,
+    like opt.midas_resize; off by default."""
+    share = bool(getattr(opt, 'share_frames', 0))
+    quantum = getattr(opt, 'share_quantum', 8)
+    if share and (isinstance(quantum, bool) or not isinstance(quantum, numbers.Integral) or quantum < 1):
+        raise ValueError('opt.share_quantum must be an integer >= 1, got %r' % (quantum,))
+    return share, (int(quantum) if share else None)
+
+
 class Model(NetInterface):
     @classmethod
     def add_arguments(cls, parser):
@@ -476,6 +490,10 @@ class Model(NetInterface):
         self.warm = False
         self.steps, self.steps_per_pair = 0, []     # Euler steps of the last training batch: largest count / per pair (caller's order)
         self._inv_perm = None        # set while self._input holds a batch in gap-grouped order (mixed frame gaps)
+        share_frames_of(opt)         # (validated here; read again at every step, like the other opt attributes of the step)
+        # statistics of the last training step: images the depth net ran on (2B; the padded number of distinct frames with
+        # opt.share_frames), and that step's union {'U', 'U_pad', 'B'} (None without sharing)
+        self.depth_images_last_step, self.last_union = 0, None
 
     # flat parameter buffers + fused Adam (or SGD, --optim sgd) replace the two torch.optim objects (:113-115)
     def to(self, device):
@@ -568,26 +586,50 @@ class Model(NetInterface):
         gap = torch.mean(ts2.float() - ts1.float())
         return int((gap / time_step).round().long().item()), time_step
 
-    def _steps_per_pair(self, batch):
-        """(steps, steps_per_pair, time_step): the Euler steps of every pair, round((ts2[b] - ts1[b]) / time_step) -- time
+    def _batch_frame_ids(self, batch, B):
+        """opt.share_frames: the frame ids of the batch's two image sets as ONE float tensor [2B] (ids are whole numbers far
+        below 2^24, exact in fp32), from `fid_1` / `fid_2` (frame-store items) or `frame_id_1` / `frame_id_2` (pair packs)."""
+        for k1, k2 in (('fid_1', 'fid_2'), ('frame_id_1', 'frame_id_2')):
+            if k1 in batch and k2 in batch:
+                ids = [torch.as_tensor(batch[k]).reshape(-1) for k in (k1, k2)]
+                if ids[0].numel() != B or ids[1].numel() != B:
+                    raise ValueError('opt.share_frames: %s / %s hold %d / %d ids for %d pairs' % (
+                        k1, k2, ids[0].numel(), ids[1].numel(), B))
+                return ids
+        raise ValueError('opt.share_frames needs the frame id of every image: the batch has neither fid_1 / fid_2 nor '
+                         'frame_id_1 / frame_id_2 (its keys: %s)' % sorted(batch))
+
+    def _steps_per_pair(self, batch, with_ids=False):
+        """(steps, steps_per_pair, time_step, ids): the Euler steps of every pair, round((ts2[b] - ts1[b]) / time_step) -- time
         stamps are constant per pair (datasets/davis_sequence.py) --, in the caller's order, with ONE device-to-host read.
-        steps: for a uniform batch exactly _integer_steps' value (the rounded mean gap, :248-250), else the largest count."""
+        steps: for a uniform batch exactly _integer_steps' value (the rounded mean gap, :248-250), else the largest count.
+        with_ids (opt.share_frames): the same read also brings the frame ids of the two image sets, ids = (f1, f2) as lists of
+        ints in the caller's order; else ids is None."""
         ts1, ts2, step = batch['time_stamp_1'], batch['time_stamp_2'], batch['time_step']
         time_step = float(step.squeeze().item()) if torch.is_tensor(step) else float(step)
         d = ts2.float() - ts1.float()
         B = int(d.shape[0]) if d.dim() > 0 else 1
-        both = torch.cat([(d.reshape(B, -1)[:, 0] / time_step).round(), (torch.mean(d) / time_step).round().reshape(1)]).tolist()
+        parts = [(d.reshape(B, -1)[:, 0] / time_step).round(), (torch.mean(d) / time_step).round().reshape(1)]
+        if with_ids:
+            parts += [t.to(d.device, non_blocking=True).float() for t in self._batch_frame_ids(batch, B)]
+        both = torch.cat(parts).tolist()
+        ids = None
+        if with_ids:
+            raw, both = both[B + 1:], both[:B + 1]
+            if not all(np.isfinite(raw)) or any(v != int(v) or v < 0 or v >= 2 ** 24 for v in raw):
+                raise ValueError('opt.share_frames: frame ids must be whole numbers in [0, 2^24), got %s' % (raw,))
+            ids = ([int(v) for v in raw[:B]], [int(v) for v in raw[B:]])
         if not all(np.isfinite(both)):          # (the uniform path keeps whatever it does with such time stamps)
             steps = self._integer_steps(batch)[0]
-            return steps, [steps] * B, time_step
+            return steps, [steps] * B, time_step, ids
         per_pair, mean = [int(v) for v in both[:B]], int(both[B])
         if all(v == per_pair[0] for v in per_pair):
-            return mean, [mean] * B, time_step
+            return mean, [mean] * B, time_step, ids
         for b, v in enumerate(per_pair):
             if v < 1:
                 raise ValueError('pair %d of a batch that mixes frame gaps has time stamps %g frames apart (%d Euler steps): '
                                  'every pair needs at least one' % (b, float(ts2[b].flatten()[0] - ts1[b].flatten()[0]) / time_step, v))
-        return max(per_pair), per_pair, time_step
+        return max(per_pair), per_pair, time_step, ids
 
     def _group_input(self, perm):
         """Bring the loaded batch (self._input) into gap-grouped order: ONE dvd_gather_pairs launch over every per-pair
@@ -644,7 +686,8 @@ class Model(NetInterface):
         for k, v in batch.items():                   # strip the DataLoader dimension (:177-179)
             if type(v) != list:
                 batch[k] = v.squeeze(0)
-        steps, steps_pp, time_step = self._steps_per_pair(batch)
+        share, share_quantum = share_frames_of(opt)
+        steps, steps_pp, time_step, ids = self._steps_per_pair(batch, with_ids=share)
         self.steps, self.steps_per_pair = steps, steps_pp
         self.load_batch(batch)
         inp = self._input
@@ -664,7 +707,28 @@ class Model(NetInterface):
         if keeping:
             self._depth.choose_chunk(B, HW, plan['reserve'], dev)
         n_slots = -(-B // self._chunk())
-        if not keeping:
+        self.depth_images_last_step, self.last_union, union = 2 * B, None, None
+        if share:
+            # opt.share_frames: the depth net runs once per DISTINCT frame of the step (same id = same image: trusted).  The
+            # union rows (padded to a multiple of opt.share_quantum with copies of row 0) are one image set in slots 0..;
+            # phase 3 sums the depth gradients of every image that shows a frame before the one backward
+            perm = plan['perm']
+            tab = ops.UnionTables(frame_union.plan_union([ids[0][p] for p in perm], [ids[1][p] for p in perm],
+                                                         share_quantum), dev)
+            img_u = ops.union_gather(inp.img_1.contiguous(), inp.img_2.contiguous(), tab)
+            fid_u = None if fid1 is None else ops.union_gather(fid1.contiguous(), fid2.contiguous(), tab)
+            n_slots = -(-tab.U_pad // self._chunk())
+            if not keeping:
+                with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
+                    depth_u = self._depth.forward(img_u, fid_u)
+            else:
+                depth_u = self._depth.forward_keep(img_u, fid_u, 0, plan['reserve'], n_slots)
+                self._depth.trim(dev, plan['reserve'])
+            depth_1, depth_2 = ops.union_scatter(depth_u, tab)
+            union = (tab, img_u, fid_u)
+            self.depth_images_last_step = tab.U_pad
+            self.last_union = {'U': tab.U, 'U_pad': tab.U_pad, 'B': B}
+        elif not keeping:
             # (non-warm steps without kept slots: phase 3 recomputes every chunk's forward; a warm-up step has no depth-net backward)
             with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
                 depth_1 = self._depth.forward(inp.img_1, fid1)
@@ -676,6 +740,7 @@ class Model(NetInterface):
 
         # ---- phase 2: geometry + scene-flow network + losses, forward and backward (_SfStep)
         step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg, plan['groups'])
+        step.union = union
         if opt.use_cnn:
             _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
             step.set_global_batch(n_global)
@@ -693,7 +758,8 @@ class Model(NetInterface):
         # and on the size of the global batch before the first data-dependent collective
         # (also agreed across ranks: does ANY rank still have to capture a depth-net graph in phase 3?  Then every rank keeps
         #  the MLP-gradient all-reduce out of flight until after phase 3, so the order of collectives is the same everywhere)
-        will_capture = not warm and self._depth.backward_will_capture((0, inp.img_1), (n_slots, inp.img_2))
+        will_capture = not warm and self._depth.backward_will_capture(
+            *([(0, union[1])] if union is not None else [(0, inp.img_1), (n_slots, inp.img_2)]))
         late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B, will_capture)
         step.set_global_batch(n_global)
         step.begin_mlp(Bc, plan['chunks'])
@@ -723,8 +789,12 @@ class Model(NetInterface):
             fid1, fid2 = self._frame_ids(inp)
             g_d1 = step.g_d1_main if early_norm else ops.scale_add(step.g_d1_main, step.g_d1_main, scale_ptr=inv, b=step.g_d1_reg)
             g_d2 = ops.scale_add(step.g_d2_main, step.g_d2_main, scale_ptr=inv)
-            self._depth.backward(inp.img_1, fid1, g_d1, slot0=0)
-            self._depth.backward(inp.img_2, fid2, g_d2, slot0=n_slots)
+            if step.union is not None:      # opt.share_frames: ONE backward over the distinct frames, from the summed gradients
+                tab, img_u, fid_u = step.union
+                self._depth.backward(img_u, fid_u, ops.union_reduce(g_d1, g_d2, tab), slot0=0)
+            else:
+                self._depth.backward(inp.img_1, fid1, g_d1, slot0=0)
+                self._depth.backward(inp.img_2, fid2, g_d2, slot0=n_slots)
             # 421 MB (MiDaS) in --grad_buckets large all-reduces, each bucket's Adam launch overlapping the next
             # bucket's reduction
             skip = None

@@ -291,7 +291,7 @@ BYTE_CLASS_KERNELS = {
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel', 'store_gather_kernel'),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 
@@ -473,6 +473,100 @@ def store_gather(entries, index, host_index=None):
         for it, (src, dst, bpr, rows, row, op) in zip(arr, part):
             it.src, it.dst, it.bytes_per_row, it.src_rows, it.index_row, it.op, it.pad = src.data_ptr(), dst.data_ptr(), bpr, rows, row, op, 0
         _lib.check(lib.dvd_store_gather(arr, len(part), _p(index), stride, B, _stream()), 'dvd_store_gather')
+
+
+class UnionTables(object):
+    """The index tables of a step that shares frames (models/frame_union.py: plan_union), as ONE int32 device tensor
+    [set | row | u1 | u2 | offsets | entries] uploaded once, its host copy, and a view per part.  The union_* wrappers check
+    every index of the part they use against the host copy before they launch."""
+
+    def __init__(self, plan, device):
+        from .models import frame_union
+        self.plan, self.B, self.U, self.U_pad = plan, int(plan['B']), int(plan['U']), int(plan['U_pad'])
+        self.host, self.where = frame_union.table(plan)
+        self.dev = torch.from_numpy(self.host).to(device, non_blocking=True)
+
+    def part(self, name):
+        o, n = self.where[name]
+        return self.dev[o:o + n]
+
+    def host_part(self, name):
+        o, n = self.where[name]
+        return self.host[o:o + n]
+
+    def check(self, what, name, lo, hi):
+        v = self.host_part(name)
+        if v.size and (int(v.min()) < lo or int(v.max()) >= hi):
+            raise RuntimeError('%s: table %r spans [%d, %d], outside [%d, %d)' % (what, name, int(v.min()), int(v.max()), lo, hi))
+
+
+def _union_rows(what, t, rows, name, dtype=None):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError('%s: %s must be a GPU tensor (dvd_hip has no CPU path)' % (what, name))
+    if t.dim() < 1 or t.shape[0] != rows or t.numel() == 0 or not t.is_contiguous():
+        raise RuntimeError('%s: %s must be a contiguous tensor of %d rows, got %s' % (what, name, rows, tuple(t.shape)))
+    if dtype is not None and t.dtype != dtype:
+        raise RuntimeError('%s: %s must be %s, got %s' % (what, name, dtype, t.dtype))
+    bpr = t.numel() // rows * t.element_size()
+    if bpr % 4 or t.data_ptr() % 4:
+        raise RuntimeError('%s: %s: rows of %d bytes at a %d-byte offset; rows are moved as dwords' % (
+            what, name, bpr, t.data_ptr() % 4))
+    return bpr
+
+
+def union_gather(img_1, img_2, tab, out=None):
+    """out[u] = (set[u] ? img_2 : img_1)[row[u]] for the U_pad union rows of `tab` (dvd_union_gather): the distinct frames of a
+    step, padding rows being copies of union row 0.  img_1, img_2: contiguous GPU tensors [B, ...] of one shape and dtype."""
+    B, U_pad = tab.B, tab.U_pad
+    bpr = _union_rows('union_gather', img_1, B, 'img_1')
+    if img_2.shape != img_1.shape or img_2.dtype != img_1.dtype or _union_rows('union_gather', img_2, B, 'img_2') != bpr:
+        raise RuntimeError('union_gather: the two image sets differ in shape or dtype')
+    tab.check('union_gather', 'set', 0, 2)
+    tab.check('union_gather', 'row', 0, B)
+    if out is None:
+        out = torch.empty((U_pad,) + tuple(img_1.shape[1:]), device=img_1.device, dtype=img_1.dtype)
+    elif out.dtype != img_1.dtype or _union_rows('union_gather', out, U_pad, 'out') != bpr:
+        raise RuntimeError('union_gather: out must hold %d rows like the sources\'' % U_pad)
+    _lib.check(_lib.load().dvd_union_gather(_p(img_1), _p(img_2), _p(out), _p(tab.part('set')), _p(tab.part('row')), U_pad, B,
+                                            bpr, _stream()), 'dvd_union_gather')
+    return out
+
+
+def union_scatter(D, tab, out=None):
+    """(depth_1, depth_2) with depth_1[b] = D[u1[b]], depth_2[b] = D[u2[b]] in ONE launch (dvd_union_scatter).  D: contiguous
+    GPU tensor [U_pad, ...]; out: optional pair of destinations [B, ...]."""
+    B, U_pad = tab.B, tab.U_pad
+    bpr = _union_rows('union_scatter', D, U_pad, 'D')
+    tab.check('union_scatter', 'u1', 0, U_pad)
+    tab.check('union_scatter', 'u2', 0, U_pad)
+    if out is None:
+        out = tuple(torch.empty((B,) + tuple(D.shape[1:]), device=D.device, dtype=D.dtype) for _ in range(2))
+    elif len(out) != 2 or any(o.dtype != D.dtype or _union_rows('union_scatter', o, B, 'out') != bpr for o in out):
+        raise RuntimeError('union_scatter: out must be two tensors of %d rows like D\'s' % B)
+    _lib.check(_lib.load().dvd_union_scatter(_p(D), _p(out[0]), _p(out[1]), _p(tab.part('u1')), _p(tab.part('u2')), B, U_pad, bpr,
+                                             _stream()), 'dvd_union_scatter')
+    return out[0], out[1]
+
+
+def union_reduce(g_d1, g_d2, tab, out=None):
+    """G[u] = the sum of the depth gradients of every image that shows union row u: 0 + g[e_0] + g[e_1] + ... over the row's CSR
+    entries in list order, plain fp32 adds, no atomics (dvd_union_reduce); padding rows are zero.  g_d1, g_d2: fp32 [B, ...]."""
+    B, U_pad = tab.B, tab.U_pad
+    bpr = _union_rows('union_reduce', g_d1, B, 'g_d1', torch.float32)
+    if g_d2.shape != g_d1.shape or _union_rows('union_reduce', g_d2, B, 'g_d2', torch.float32) != bpr:
+        raise RuntimeError('union_reduce: the two gradient sets differ in shape')
+    tab.check('union_reduce', 'offsets', 0, 2 * B + 1)
+    tab.check('union_reduce', 'entries', 0, 2 * B)
+    off = tab.host_part('offsets')
+    if off[0] != 0 or (off[1:] < off[:-1]).any():
+        raise RuntimeError('union_reduce: offsets must start at 0 and not decrease')
+    if out is None:
+        out = torch.empty((U_pad,) + tuple(g_d1.shape[1:]), device=g_d1.device, dtype=torch.float32)
+    elif _union_rows('union_reduce', out, U_pad, 'out', torch.float32) != bpr:
+        raise RuntimeError('union_reduce: out must hold %d rows like the sources\'' % U_pad)
+    _lib.check(_lib.load().dvd_union_reduce(_p(g_d1), _p(g_d2), _p(out), _p(tab.part('offsets')), _p(tab.part('entries')), U_pad,
+                                            B, bpr // 4, _stream()), 'dvd_union_reduce')
+    return out
 
 
 class _BicubicResize(torch.autograd.Function):

@@ -689,6 +689,28 @@ typedef struct dvd_store_item {
 int dvd_store_gather(const dvd_store_item* items, int n_items, const int* index, long long index_stride, int B,
                      dvd_stream_t stream);
 
+/* The depth net once per DISTINCT frame of a step (additions within ABI 8; csrc/frame_union.hip, models/frame_union.py,
+ * opt.share_frames).  The reference evaluates net_depth(img_1) and net_depth(img_2) with the net in eval() mode, so an image
+ * that several pairs of a step show has one depth map; these three launches move rows between the step's two per-pair sets
+ * (B rows each) and the union of their frames (U_pad rows).  Rows are fp32 (any bytes_per_row that is a multiple of 4); every
+ * index array is a DEVICE array of ints; 16-byte accesses where the row size and every base address are multiples of 16, dwords
+ * otherwise.  Copies and sequential fp32 adds only: no atomics, no scaling, results are bit-reproducible.  Null pointers, empty
+ * sizes, misaligned or overlapping buffers return DVD_EINVAL before any HIP call; bytes are counted under DVD_BYTES_GATHER.
+ *   dvd_union_gather   out[u] = (set[u] ? img_2 : img_1)[row[u]], u < U_pad; a set outside {0, 1} or a row outside [0, B)
+ *                      reads and writes nothing for that union row.
+ *   dvd_union_scatter  ONE launch: depth_1[b] = D[u1[b]], depth_2[b] = D[u2[b]], b < B; an index outside [0, U_pad) writes
+ *                      nothing for that image.
+ *   dvd_union_reduce   G[u] = 0 + g[e_0] + g[e_1] + ... over entries[offsets[u] .. offsets[u + 1]) in list order, left to
+ *                      right, where an entry is set * B + row and g = set ? g_d2 : g_d1 (floats_per_row floats per row); a
+ *                      row without entries is zero; an entry outside [0, 2B) (or the part of a range outside the list) adds
+ *                      nothing.  offsets holds U_pad + 1 ints, entries 2B. */
+int dvd_union_gather(const void* img_1, const void* img_2, void* out, const int* set, const int* row, int U_pad, int B,
+                     long long bytes_per_row, dvd_stream_t stream);
+int dvd_union_scatter(const void* D, void* depth_1, void* depth_2, const int* u1, const int* u2, int B, int U_pad,
+                      long long bytes_per_row, dvd_stream_t stream);
+int dvd_union_reduce(const float* g_d1, const float* g_d2, float* G, const int* offsets, const int* entries, int U_pad, int B,
+                     long long floats_per_row, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
