@@ -154,6 +154,8 @@ SIGNATURES = {
     'dvd_xwgradk': (c_int, [c_void_p] * 6 + [c_size_t] + [c_int] * 7 + [c_void_p]),
     'dvd_xwgrad1s': (c_int, [c_void_p] * 6 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'dvd_xwgrad1s_rowsum': (c_int, [c_void_p] * 7 + [c_size_t] + [c_int] * 6 + [c_void_p]),
+    'dvd_xwgrad3_rowsum': (c_int, [c_void_p] * 7 + [c_size_t] + [c_int] * 7 + [c_void_p]),
+    'dvd_xwgrad_rowsum_in_kernel': (c_int, [c_int] * 7),
     'dvd_xwgrad3': (c_int, [c_void_p] * 6 + [c_size_t] + [c_int] * 7 + [c_void_p]),
     'dvd_xwgrad_workspace_bytes': (c_size_t, [c_int] * 6),
     'dvd_xwgrad': (c_int, [c_void_p] * 4 + [c_size_t] + [c_int] * 7 + [c_void_p]),

@@ -36,8 +36,9 @@ from .ops import _p, _stream, _workspace, amax_of, chansum, known_amax, new_scal
 #   no_maskfuse the ReLU mask of a BatchNorm+ReLU site always in the site's own mask pass (never in its consumer's epilogue)
 #   no_s2       stride-2 3x3 convolutions as rounds 2-5 ran them: the stride-1 kernel's output sub-sampled, the gradient
 #               zero-interleaved in HBM (csrc/pool.hip) in front of the stride-1 backward-data kernel
-#   rowsum      (opt-in experiment) a pre-masked site takes its per-channel sums from dvd_xwgrad1s_rowsum and max|g| from the
-#               consumer's epilogue instead of running its sum pass
+#   rowsum      bookkeeping only: the sites that run no pass of their own (see _XConvBn.backward: the default wherever the weight
+#               gradient kernel delivers the per-channel sums) are counted as STATS['sites_no_pass'] instead of 'sites_premasked'.
+#               (No key turns that default off: bench.py and the tests pin the six keys, so its A/B is against the parent build.)
 AB = {k: False for k in ('gconv32', 'no_xwgrad3', 'no_alias', 'no_maskfuse', 'no_s2', 'rowsum')}
 for _k in filter(None, _os.environ.get('DVD_AB', '').split(',')):
     if _k not in AB:
@@ -1114,6 +1115,20 @@ def wgrad_reports_rowsum(wshape, groups):
     return wshape[2] == 1 and groups == 1 and not AB['no_xwgrad3']
 
 
+def xconv_wgrad3_rowsum(x, gy, wshape, groups, x_amax, g_amax, rowsum):
+    """xconv_wgrad of an fp32 3x3 convolution plus rowsum[co] = sum_{n,p} gy[n][co][p] (csrc/xwgrad3.hip dvd_xwgrad3_rowsum: the
+    32 x 32 grouped kernel sums the rows it stages, other shapes take a pass over gy).  A helper of its own: xconv_wgrad's 3x3
+    call stays the plain dvd_xwgrad3."""
+    lib = _lib.load()
+    N, Cin, H, W = x.shape
+    dims = (N, Cin, wshape[0], H, W, groups)
+    gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
+    ws = _workspace(lib.dvd_xwgrad3_workspace_bytes(*dims), x.device)
+    _lib.check(lib.dvd_xwgrad3_rowsum(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(rowsum), _p(ws), ctypes.c_size_t(ws.numel()),
+                                      *(dims + (0, _stream()))), 'dvd_xwgrad3_rowsum')
+    return gw
+
+
 def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rowsum=None):
     """dW[co][ci][tap] = sum_{n,p} gy[n][co][p] * act(x)[n][ci][p + tap] on the split-operand MFMA kernels of csrc/xwgrad3.hip:
     1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 (xwgradk: the hourglass's inception branches and the stem's
@@ -1163,7 +1178,8 @@ def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rows
 class _XConvBn(torch.autograd.Function):
     """y = act(bn_eval(conv2d(x, w) + cbias) (+ residual)): the convolution kernel's epilogue applies the BatchNorm, so
     the pre-BN tensor is never written.  Backward: one pass masks the output gradient (g = gy * [y > 0]) and sums it per
-    channel (dbeta); backward-data runs on g with the weights packed transposed AND scaled by gamma * rstd; backward-weight
+    channel (dbeta) -- no pass at all where the consumer's epilogue has masked the gradient and the weight-gradient kernel
+    delivers the sums; backward-data runs on g with the weights packed transposed AND scaled by gamma * rstd; backward-weight
     runs on g unscaled, and a tiny kernel derives dW, dgamma and the conv-bias gradient from it (csrc/bnrelu.hip)."""
 
     @staticmethod
@@ -1204,12 +1220,19 @@ class _XConvBn(torch.autograd.Function):
         premasked = relu and ctx.out_site is not None and ctx.out_site.is_exactly(gy) and not AB['no_maskfuse']
         mask = relu and not premasked
         need_w = need[2] or (gamma is not None and need[4]) or (cbias is not None and need[3])
-        # ... and if the weight gradient runs on the 1x1 kernel, that kernel reports the per-channel sums of the rows it stages
-        # and the consumer's epilogue has left max|g|: no pass of this site's own at all
-        no_pass = (premasked and need_w and ctx.out_site.amax is not None and wgrad_reports_rowsum(weight.shape, groups) and
-                   AB['rowsum'])
-        if relu:
-            STATS['sites_no_pass' if no_pass else ('sites_premasked' if premasked else 'sites_masked')] += 1
+        # ... and the sum pass of a pre-masked fp32 site read the whole gradient for one add per element, right before the weight
+        # gradient kernel stages the same rows: the dense 1x1 and the grouped 3x3 kernels report the per-channel sums of the rows
+        # they stage, the consumer's epilogue has left max|g| -- no pass of this site's own at all.  Only where the kernel itself
+        # sums (dvd_xwgrad_rowsum_in_kernel): the entry points' fallback pass for other shapes is slower than the site's pass.
+        # A ReLU site that masks for itself takes dbeta from the weight gradient call too (its pass runs for g and max|g| and
+        # writes no sums): the sums are then the same bits however the mask was obtained, which
+        # tests/test_09_fused_joins_gpu.py asserts of every gradient.  Sites without a ReLU have no such twin and keep their pass.
+        grouped3 = KS == 3 and groups > 1
+        wgrad_sums = (relu and need_w and gy.dtype == torch.float32 and (grouped3 or wgrad_reports_rowsum(weight.shape, groups)) and
+                      lib.dvd_xwgrad_rowsum_in_kernel(N, Cing * groups, Cout, H, W, KS, groups) == 1)
+        no_pass = premasked and wgrad_sums and ctx.out_site.amax is not None
+        if relu:         # (sites_premasked says how the mask was obtained; sites_no_pass only under DVD_AB=rowsum)
+            STATS['sites_no_pass' if (no_pass and AB['rowsum']) else ('sites_premasked' if premasked else 'sites_masked')] += 1
         g = torch.empty_like(gy) if mask else gy
         h16 = _is16(gy)
         if no_pass:
@@ -1219,7 +1242,8 @@ class _XConvBn(torch.autograd.Function):
             # max|masked gradient|, folded in by the mask pass (it reads every element anyway); fp16: the policy's observed maximum
             g_amax = _gs(3) if h16 else new_scalar(gy.device)
             _lib.check(lib.dvd_bnrelu_bwd_t(_p(gy), _p(y) if mask else None, None, _p(var), _p(mean), _p(var), eps, None,
-                                            _p(g) if mask else None, None, _p(dbeta), _p(ws), ctypes.c_size_t(ws.numel()),
+                                            _p(g) if mask else None, None, None if wgrad_sums else _p(dbeta), _p(ws),
+                                            ctypes.c_size_t(ws.numel()),
                                             int(h16), _p(_gs(1)) if h16 else None, N, Cout, H * W, int(mask), _p(g_amax),
                                             _stream()), 'dvd_bnrelu_bwd')
         gx = gw = gcb = gg = None
@@ -1229,7 +1253,10 @@ class _XConvBn(torch.autograd.Function):
         elif g_alias is not None:
             gx = g_alias
         if need_w:
-            gw = xconv_wgrad(x, g, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if no_pass else None)
+            if wgrad_sums and grouped3:
+                gw = xconv_wgrad3_rowsum(x, g, weight.shape, groups, x_amax, g_amax, dbeta)
+            else:
+                gw = xconv_wgrad(x, g, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if wgrad_sums else None)
             gg = torch.empty_like(gamma) if gamma is not None else None
             gcb = torch.empty_like(cbias) if cbias is not None else None
             _lib.check(lib.dvd_convbn_finalize(_p(weight.detach()), _p(gw), _p(dbeta), _p(gamma), _p(mean), _p(var), eps,

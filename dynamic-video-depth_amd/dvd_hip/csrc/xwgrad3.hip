@@ -42,6 +42,8 @@ struct Wg3Args {
   const float* __restrict__ g_amax;
   const float* __restrict__ out_scale;  // H16: device scalar the result is multiplied by (1 / loss scale of the fp16 gradients), or null
   float* __restrict__ partial;   // [S][9][Cout][Cin]
+  // RSUM kernels (fp32 xwgrad1b FW / xwgrad3g): [S][G * Cout] per-slice sums of the gy rows the block stages, or null
+  float* __restrict__ rowsum_partial = nullptr;
   int N, Cin, Cout, H, W;        // Cin / Cout per group
   int G, nco;                    // groups, output-channel blocks per group
   int nstrips, RS, nrseg, S;     // column strips per image, rows per work item, row segments per image, slices
@@ -571,11 +573,21 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
 constexpr int kWgCB = 32, kWgNT = 192;
 constexpr int kWgLdsBytes = 2 * 2 * kWgCB * kW3GPitch + 2 * kWgCB * 4 * kW3XPitch;    // 63 488
 
-template <bool H16>
+// RSUM (fp32 only; host: a.rowsum_partial is set): the kernel also sums the gy rows it stages, per output channel -- the shift
+// gradient of a BatchNorm fused behind the convolution (conv._XConvBn), which otherwise takes a pass over gy of its own.  A thread
+// stages the same (at most three) gy channel rows for the whole walk, so it keeps one accumulator per gy item and adds the four
+// scaled, row-end-masked values the split consumes anyway; rows the walk stages beyond its segment (the look-ahead row r1) are
+// gated out, so every element of a (group, co block) counts exactly once over the slices.  Without RSUM the code is unchanged.
+template <bool H16, bool RSUM = false>
 __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
+  static_assert(!(H16 && RSUM), "the channel sums exist for fp32 gradients");
   constexpr int EB = H16 ? 2 : 4, NTERM = H16 ? 1 : 2, CB = kWgCB;
   constexpr int QW = H16 ? 8 : 4, GPR = 64 / QW, XPR = 80 / QW, GQ = CB * GPR, XQ = CB * XPR, NQ = (GQ + XQ) / kWgNT;
   static_assert((GQ + XQ) % kWgNT == 0 && GQ % 64 == 0, "staging items divide evenly over the threads, wave-uniform kind");
+  constexpr int NG = (GQ + kWgNT - 1) / kWgNT;      // staging items of a thread that can be gy runs: i < NG
+  float rs[RSUM ? NG : 1];
+#pragma unroll
+  for (int i = 0; i < (RSUM ? NG : 1); ++i) rs[i] = 0.0f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
   unsigned char* sG = smem3;                                   // [buffer 2][term 2][co 32][kW3GPitch]
   unsigned char* sX = smem3 + 2 * 2 * CB * kW3GPitch;          // [term 2][slot 4][ci 32][kW3XPitch]
@@ -612,7 +624,7 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
     const int so = ok ? row * a.W * EB : 0;
     fstg[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(isg[i] ? srdG : srdX, vo, so, 0));
   };
-  auto f_store = [&](int i, int xslot, int gbuf) {
+  auto f_store = [&](int i, int xslot, int gbuf, bool g_live) {        // g_live (wave-uniform): the gy row belongs to this item's rows
     unsigned char* dst = smem3 + f_lds[i] + (isg[i] ? gbuf * (2 * CB * kW3GPitch) : xslot * (CB * kW3XPitch));
     if constexpr (H16) {
       u32x4 v = fstg[i];
@@ -625,6 +637,9 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
       const float lo = isg[i] ? -__builtin_inff() : relu_lo;
       const float v0 = fmaxf(__uint_as_float(fstg[i][0]), lo) * f_sc[i][0], v1 = fmaxf(__uint_as_float(fstg[i][1]), lo) * f_sc[i][1];
       const float v2 = fmaxf(__uint_as_float(fstg[i][2]), lo) * f_sc[i][2], v3 = fmaxf(__uint_as_float(fstg[i][3]), lo) * f_sc[i][3];
+      if constexpr (RSUM) {
+        if (i < NG && isg[i]) rs[i] += g_live ? (v0 + v1) + (v2 + v3) : 0.0f;
+      }
       unsigned h0, l0, h1, l1;
       split_pair_f16(v0, v1, h0, l0);
       split_pair_f16(v2, v3, h1, l1);
@@ -670,9 +685,9 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
 #pragma unroll
       for (int i = 0; i < NQ; ++i) f_load(i, rg, with_g);
     };
-    auto store_all = [&](int xslot, int gbuf) {
+    auto store_all = [&](int xslot, int gbuf) {       // (the prologue's gy rows: zeros, then row r0)
 #pragma unroll
-      for (int i = 0; i < NQ; ++i) f_store(i, xslot, gbuf);
+      for (int i = 0; i < NQ; ++i) f_store(i, xslot, gbuf, true);
     };
     __syncthreads();                               // the previous item's MFMAs have read their operands
     load_all(r0 - 2, false);
@@ -716,7 +731,7 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
         // the staging items i = s, s + 4 ride behind the MFMAs of K step s (for step r + 1 / r + 2, as in xwgrad3_kernel)
 #pragma unroll
         for (int i = s; i < NQ; i += 4) {
-          f_store(i, (r + 2) & 3, (r + 1) & 1);
+          f_store(i, (r + 2) & 3, (r + 1) & 1, r + 1 < r1);      // gy row r + 1: the look-ahead past the last row is staged, not summed
           f_load(i, r + 2, true);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -735,11 +750,42 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
       if (co < a.Cout && ci < a.Cin) dst[((size_t)tap * a.G * a.Cout + grp * a.Cout + co) * a.Cin + ci] = acc[kx][r] * unscale;
     }
   }
+  if constexpr (RSUM) {
+    // the 16 lanes (run cells) of a channel row, in a fixed order; the operand scale is a power of two: unscaling is exact
+    const float inv_sg = 1.0f / sg;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      float v = rs[i];
+#pragma unroll
+      for (int m = 1; m < GPR; m <<= 1) v += __shfl_xor(v, m, 64);
+      if (isg[i] && (tid & (GPR - 1)) == 0 && blockIdx.y == 0 && f_ch[i] < a.Cout - co0)
+        a.rowsum_partial[(size_t)blockIdx.x * a.G * a.Cout + grp * a.Cout + co0 + f_ch[i]] = v * inv_sg;
+    }
+  }
 }
 
-// gw[co][ci][tap] = sum_s partial[s][tap][co][ci], ascending s (two interleaved chains)
+// gw[co][ci][tap] = sum_s partial[s][tap][co][ci], ascending s (two interleaved chains); blocks from nmain on (RSUM launches):
+// rowsum[c] = sum_s rpartial[s][c], ascending s, in double
 __global__ __launch_bounds__(256) void xwgrad3_reduce_kernel(const float* __restrict__ partial, float* __restrict__ gw, int S,
-                                                             int T, int Cout, int Cin) {
+                                                             int T, int Cout, int Cin, unsigned nmain,
+                                                             const float* __restrict__ rpartial, float* __restrict__ rowsum,
+                                                             int RC) {
+  if (blockIdx.x >= nmain) {
+    const int c = (int)(blockIdx.x - nmain) * 256 + threadIdx.x;
+    if (c >= RC) return;
+    double t = 0.0;
+    int s = 0;
+    for (; s + 16 <= S; s += 16) {                 // sixteen independent loads, then the adds in slice order
+      float v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = rpartial[(size_t)(s + j) * RC + c];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t += (double)v[j];
+    }
+    for (; s < S; ++s) t += (double)rpartial[(size_t)s * RC + c];
+    rowsum[c] = (float)t;
+    return;
+  }
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // over [tap][co][ci]
   const long long per = (long long)T * Cout * Cin;
   if (i >= per) return;
@@ -871,10 +917,21 @@ constexpr size_t kWbLds = 2 * (size_t)kWbBuf;      // double buffered: 98 304
 // the tensor fall out of the resource's range and read 0), a column tile's MFMAs are followed by the split + LDS store of ONE
 // staging item and the request of the same item two chunks ahead -- round 3 ran `barrier | requests | all MFMAs | all splits`
 // with both waves of a SIMD in the same phase (matrix pipe 37 % busy) and one chunk of latency cover for the HBM request.
-template <bool H16, bool FW>
+// RSUM (fp32 FW only; host: a.rowsum_partial is set): the kernel also sums the gy rows it stages -- a thread stages the same two
+// gy rows, tid >> 2 and 128 + (tid >> 2), for its whole slice, so f_store of the two gy items adds the item's four raw values
+// behind the column tile's MFMAs, where it consumes the loaded registers for the split anyway (the scene-flow MLP's dw_body sums
+// its bias gradient the same way).  The kernel has two registers to spare -- the plain FW form allocates 254 of the 256 VGPRs
+// a wave of a 512-thread block may have; with one accumulator per row (two registers) this form spilled 19 -- so the four lanes
+// of a row share ONE accumulator register for both rows (256 VGPRs, no scratch: one more live register here is a spill): the
+// item's sum is folded across lanes q and q ^ 2 first, lanes 0 / 1 of a quad keep row tid >> 2, lanes 2 / 3 keep row
+// 128 + (tid >> 2).  Chunks past the slice's end add zeros.  The blocks of input channel block 0 report;
+// without RSUM the code is unchanged.
+template <bool H16, bool FW, bool RSUM = false>
 __global__ __launch_bounds__(512) void xwgrad1b_kernel(const Wg3Args a) {
+  static_assert(!RSUM || (FW && !H16), "the channel sums exist in the fp32 FW form");
   constexpr int EB = H16 ? 2 : 4;
   constexpr int NTERM = H16 ? 1 : 2;
+  float rs = 0.0f;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w >> 1, wc = w & 1;
@@ -1006,6 +1063,13 @@ __global__ __launch_bounds__(512) void xwgrad1b_kernel(const Wg3Args a) {
         } else {
           const float sc = isx ? sx : sg;
           const float lo = isx ? relu_lo : -__builtin_inff();
+          if constexpr (RSUM) {
+            if (!isx) {
+              float t = (__uint_as_float(st[i][0]) + __uint_as_float(st[i][1])) + (__uint_as_float(st[i][2]) + __uint_as_float(st[i][3]));
+              t += __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(t), 0x4E, 0xf, 0xf, true));     // quad_perm [2, 3, 0, 1]
+              rs += ((tid & 2) != 0) == ((i & 1) != 0) ? t : 0.0f;
+            }
+          }
           const float v0 = fmaxf(__uint_as_float(st[i][0]), lo) * sc, v1 = fmaxf(__uint_as_float(st[i][1]), lo) * sc;
           const float v2 = fmaxf(__uint_as_float(st[i][2]), lo) * sc, v3 = fmaxf(__uint_as_float(st[i][3]), lo) * sc;
           unsigned h0, l0, h1, l1;
@@ -1099,11 +1163,17 @@ __global__ __launch_bounds__(512) void xwgrad1b_kernel(const Wg3Args a) {
         const int co = co0 + 64 * wr + 32 * rr + (r & 3) + 8 * (r >> 2) + 4 * hh, ci = ci0 + 128 * wc + 32 * c + i32;
         if (co < a.Cout && ci < a.Cin) dst[(size_t)co * a.Cin + ci] = acc[rr][c][r] * unscale;
       }
+  if constexpr (RSUM) {
+    // lanes q and q ^ 1 hold the two halves of a row's sum
+    const float v = rs + __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(rs), 0xB1, 0xf, 0xf, true));   // quad_perm [1, 0, 3, 2]
+    const int co = co0 + (tid & 2) * 64 + (tid >> 2);
+    if ((tid & 1) == 0 && blockIdx.y == 0 && co < a.Cout) a.rowsum_partial[(size_t)s * a.Cout + co] = v;
+  }
 }
 
 // out[c] = sum over images and pixels of g[n][c][:]: one block per channel, fixed order (per-thread strided partial sums, then
-// a fixed tree).  (Summing the gy rows inside xwgrad1b_kernel, which stages them anyway, was tried in round 3: the eight extra
-// adds per chunk cost the kernel 10 % -- more than this pass)
+// a fixed tree).  What the row-sum entry points fall back to where no RSUM kernel serves the shape.  (Summing the gy rows inside
+// round 3's xwgrad1b_kernel cost that kernel 10 % -- its staging sat ahead of all MFMAs; the FW form took it: DESIGN.md 7.1.)
 __global__ __launch_bounds__(256) void chansum_kernel(const float* __restrict__ g, int N, int C, int HW, float* __restrict__ out) {
   const int c = blockIdx.x;
   float v = 0.0f;
@@ -1127,6 +1197,9 @@ static int wg1_wide_slices(int N, int Cin, int Cout, int HW) {
   if (S > items) S = (int)items;
   return S;
 }
+
+// the wide kernel's FW form: whole 16-pixel chunks, 256 channel rows of one image inside a 31-bit buffer range
+static bool wg1_fw(int HW, bool h16) { return HW % 16 == 0 && (long long)256 * HW * (h16 ? 2 : 4) < (1ll << 31) && g_w3_variant != 1; }
 
 struct Wg3Plan {
   int nstrips, RS, nrseg, S, nco, nci;
@@ -1152,6 +1225,10 @@ static void wg3_plan(int N, int Cin, int Cout, int H, int W, int G, Wg3Plan& p) 
 
 // 32 x 32 channel blocks of three waves (xwgrad3g_kernel): grouped layers with at most 32 channels per group on both sides
 static bool wg3_small(int Cin, int Cout, int G) { return G > 1 && Cin <= kWgCB && Cout <= kWgCB && g_w3_variant != 1; }
+// ... rows of fp16 elements must start dword-aligned for its buffer loads (even widths), 32 channels of an image within 31 bits
+static bool wg3g_serves(int Cin, int Cout, int H, int W, int G, bool h16) {
+  return wg3_small(Cin, Cout, G) && (!h16 || W % 2 == 0) && (long long)32 * H * W * (h16 ? 2 : 4) < (1ll << 31);
+}
 static void wg3g_plan(int N, int Cin, int Cout, int H, int W, int G, Wg3Plan& p) {
   p.nco = (Cout + kWgCB - 1) / kWgCB;
   p.nci = (Cin + kWgCB - 1) / kWgCB;
@@ -1181,12 +1258,15 @@ size_t dvd_xwgrad3_workspace_bytes(int N, int Cin, int Cout, int H, int W, int g
     dvd::wg3g_plan(N, Cin / groups, Cout / groups, H, W, groups, p);
     if (p.S > S) S = p.S;
   }
-  return (size_t)S * 9 * Cout * (Cin / groups) * sizeof(float);
+  // the dW partials, then the row-sum partials of dvd_xwgrad3_rowsum: [S][Cout]
+  return ((size_t)S * 9 * Cout * (Cin / groups) + (size_t)S * Cout) * sizeof(float);
 }
 
+// gy_rowsum (fp32 only, may be null): receives the per-channel sums of gy -- from the weight-gradient kernel itself where it has
+// an RSUM form (the 32 x 32 grouped kernel), else from chansum_kernel
 static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
                         size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups, int relu_in,
-                        bool h16, const float* out_scale, dvd_stream_t stream) {
+                        bool h16, const float* out_scale, float* gy_rowsum, dvd_stream_t stream) {
   DVD_REQUIRE(x && gy && gw && workspace, "xwgrad3: null pointer");
   DVD_REQUIRE(h16 || (x_amax && gy_amax), "xwgrad3: the operands' max|.| scalars are missing (dvd_amax)");
   DVD_REQUIRE(N > 0 && Cin_total > 0 && Cout_total > 0 && H > 0 && W > 0, "xwgrad3: bad shape");
@@ -1195,11 +1275,12 @@ static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, cons
               "xwgrad3: image too large for 32-bit offsets");
   const int Cin = Cin_total / groups, Cout = Cout_total / groups;
   dvd::Wg3Plan p;
-  // rows of fp16 elements must start dword-aligned for the 32 x 32 kernel's buffer loads: even widths
-  const bool small = dvd::wg3_small(Cin, Cout, groups) && (!h16 || W % 2 == 0) && (long long)32 * H * W * (h16 ? 2 : 4) < (1ll << 31);
+  const bool small = dvd::wg3g_serves(Cin, Cout, H, W, groups, h16);
   if (small) dvd::wg3g_plan(N, Cin, Cout, H, W, groups, p);
   else dvd::wg3_plan(N, Cin, Cout, H, W, groups, p);
-  const size_t need = (size_t)p.S * 9 * Cout_total * Cin * sizeof(float);
+  const bool rsum = gy_rowsum && small && !h16;                      // the kernel sums the rows it stages
+  const size_t npart = (size_t)p.S * 9 * Cout_total * Cin;
+  const size_t need = (npart + (rsum ? (size_t)p.S * Cout_total : 0)) * sizeof(float);
   if (workspace_bytes < need) {
     dvd::set_error("xwgrad3: workspace %zu < %zu bytes", workspace_bytes, need);
     return DVD_ENOSPC;
@@ -1211,6 +1292,7 @@ static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, cons
   a.x_amax = x_amax;
   a.g_amax = gy_amax;
   a.partial = static_cast<float*>(workspace);
+  a.rowsum_partial = rsum ? static_cast<float*>(workspace) + npart : nullptr;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.G = groups; a.nco = p.nco;
   a.nstrips = p.nstrips; a.RS = p.RS; a.nrseg = p.nrseg; a.S = p.S;
@@ -1226,15 +1308,21 @@ static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, cons
   const bool fw = (!h16 || W % 2 == 0) && (long long)64 * H * W * (h16 ? 2 : 4) < (1ll << 31) && dvd::g_w3_variant != 1;
   int e;
   dvd::flops_add(small ? DVD_FLOP_XWGRAD3G : DVD_FLOP_XWGRAD3, 2.0 * 9 * N * (double)Cout_total * Cin * (double)H * W);
-  if (small) e = h16 ? go(dvd::xwgrad3g_kernel<true>) : go(dvd::xwgrad3g_kernel<false>);
+  if (small) e = h16 ? go(dvd::xwgrad3g_kernel<true>) : (rsum ? go(dvd::xwgrad3g_kernel<false, true>) : go(dvd::xwgrad3g_kernel<false>));
   else if (h16) e = fw ? go(dvd::xwgrad3_kernel<true, true>) : go(dvd::xwgrad3_kernel<true, false>);
   else e = fw ? go(dvd::xwgrad3_kernel<false, true>) : go(dvd::xwgrad3_kernel<false, false>);
   if (e) return e;
   DVD_LAUNCH_OK();
   const long long per = (long long)9 * Cout_total * Cin;
-  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, p.S, 9, Cout_total, Cin);
+  const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout_total + 255) / 256) : 0u;
+  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, p.S,
+                     9, Cout_total, Cin, nmain, a.rowsum_partial, gy_rowsum, Cout_total);
   DVD_LAUNCH_OK();
+  if (gy_rowsum && !rsum) {
+    hipLaunchKernelGGL(dvd::chansum_kernel, dim3(Cout_total), dim3(256), 0, s, static_cast<const float*>(gy), N, Cout_total, H * W,
+                       gy_rowsum);
+    DVD_LAUNCH_OK();
+  }
   return DVD_OK;
 }
 
@@ -1242,13 +1330,20 @@ int dvd_xwgrad3(const float* x, const float* x_amax, const float* gy, const floa
                 size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups, int relu_in,
                 dvd_stream_t stream) {
   return xwgrad3_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, false,
-                      nullptr, stream);
+                      nullptr, nullptr, stream);
+}
+
+int dvd_xwgrad3_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
+                       void* workspace, size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups,
+                       int relu_in, dvd_stream_t stream) {
+  return xwgrad3_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, false,
+                      nullptr, gy_rowsum, stream);
 }
 
 int dvd_xwgrad3_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
                   int Cin_total, int Cout_total, int H, int W, int groups, int relu_in, dvd_stream_t stream) {
   return xwgrad3_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, true,
-                      out_scale, stream);
+                      out_scale, nullptr, stream);
 }
 
 size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) {
@@ -1257,7 +1352,8 @@ size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) {
   int S = pairs >= 512 ? 1 : (1024 + pairs - 1) / pairs;
   const int Sw = dvd::wg1_wide_slices(N, Cin, Cout, H * W);      // (either kernel may serve the call)
   if (Sw > S) S = Sw;
-  return (size_t)S * Cout * Cin * sizeof(float);
+  // the dW partials, then the row-sum partials of dvd_xwgrad1s_rowsum: [S][Cout]
+  return ((size_t)S * Cout * Cin + (size_t)S * Cout) * sizeof(float);
 }
 
 // ---- 5x5 / 7x7 / 11x11
@@ -1330,7 +1426,7 @@ static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, cons
   if (int e = h16 ? run(std::true_type{}) : run(std::false_type{})) return e;
   const long long per = (long long)KS * KS * Cout * Cin;
   hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, p.S, KS * KS, Cout, Cin);
+                     static_cast<const float*>(workspace), gw, p.S, KS * KS, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
   DVD_LAUNCH_OK();
   return DVD_OK;
 }
@@ -1354,39 +1450,56 @@ int dvd_xwgrad_select(int variant) {
 
 static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
                          size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, bool h16,
-                         const float* out_scale, dvd_stream_t stream);
+                         const float* out_scale, float* gy_rowsum, dvd_stream_t stream);
 
 int dvd_xwgrad1s_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
                         void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in,
                         dvd_stream_t stream) {
-  if (int e = dvd_xwgrad1s(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, stream)) return e;
-  if (gy_rowsum) {
-    hipLaunchKernelGGL(dvd::chansum_kernel, dim3(Cout), dim3(256), 0, static_cast<hipStream_t>(stream), gy, N, Cout, H * W, gy_rowsum);
-    DVD_LAUNCH_OK();
-  }
-  return DVD_OK;
+  return xwgrad1s_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, false, nullptr, gy_rowsum,
+                       stream);
+}
+
+int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups) {
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cin % groups || Cout % groups) return 0;
+  if (KS == 1 && groups == 1) return dvd::wg1_wide(Cin, Cout, H * W) && dvd::wg1_fw(H * W, false) ? 1 : 0;
+  if (KS == 3) return dvd::wg3g_serves(Cin / groups, Cout / groups, H, W, groups, false) ? 1 : 0;
+  return 0;
 }
 
 int dvd_xwgrad1s(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
                  size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream) {
-  return xwgrad1s_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, false, nullptr, stream);
+  return xwgrad1s_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, false, nullptr, nullptr,
+                       stream);
 }
 
 int dvd_xwgrad1s_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
                    int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream) {
-  return xwgrad1s_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, true, out_scale, stream);
+  return xwgrad1s_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, true, out_scale, nullptr,
+                       stream);
 }
 
+// gy_rowsum (fp32 only, may be null): the per-channel sums of gy -- from the wide FW kernel's RSUM form, else from chansum_kernel
 static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
                          size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, bool h16,
-                         const float* out_scale, dvd_stream_t stream) {
+                         const float* out_scale, float* gy_rowsum, dvd_stream_t stream) {
   DVD_REQUIRE(x && gy && gw && workspace, "xwgrad1s: null pointer");
   DVD_REQUIRE(h16 || (x_amax && gy_amax), "xwgrad1s: the operands' max|.| scalars are missing (dvd_amax)");
   DVD_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "xwgrad1s: bad shape");
   DVD_REQUIRE((long long)H * W * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 31), "xwgrad1s: image too large for 32-bit offsets");
+  DVD_REQUIRE(!(h16 && gy_rowsum), "xwgrad1s: the channel sums exist for fp32 gradients");
+  auto chansum = [&]() -> int {                  // the routes without an RSUM kernel: one fixed-order pass over gy
+    if (!gy_rowsum) return DVD_OK;
+    hipLaunchKernelGGL(dvd::chansum_kernel, dim3(Cout), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(gy),
+                       N, Cout, H * W, gy_rowsum);
+    DVD_LAUNCH_OK();
+    return DVD_OK;
+  };
   if (dvd::wg1_wide(Cin, Cout, H * W)) {
     const int S = dvd::wg1_wide_slices(N, Cin, Cout, H * W);
-    const size_t need = (size_t)S * Cout * Cin * sizeof(float);
+    const bool fw = dvd::wg1_fw(H * W, h16);
+    const bool rsum = gy_rowsum && fw && !h16;   // the kernel sums the rows it stages
+    const size_t npart = (size_t)S * Cout * Cin;
+    const size_t need = (npart + (rsum ? (size_t)S * Cout : 0)) * sizeof(float);
     if (workspace_bytes < need) {
       dvd::set_error("xwgrad1s: workspace %zu < %zu bytes", workspace_bytes, need);
       return DVD_ENOSPC;
@@ -1397,6 +1510,7 @@ static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, con
     a.x_amax = x_amax;
     a.g_amax = gy_amax;
     a.partial = static_cast<float*>(workspace);
+    a.rowsum_partial = rsum ? static_cast<float*>(workspace) + npart : nullptr;
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
     a.G = 1; a.nco = (Cout + 255) / 256;
     a.nstrips = 0; a.RS = 0; a.nrseg = 0; a.S = S;
@@ -1410,18 +1524,18 @@ static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, con
       return DVD_OK;
     };
     dvd::flops_add(DVD_FLOP_XWGRAD1B, 2.0 * N * (double)Cout * Cin * (double)H * W);
-    // whole 16-pixel chunks, 256 channel rows of one image inside a 31-bit buffer range
-    const bool fw = (H * W) % 16 == 0 && (long long)256 * H * W * (h16 ? 2 : 4) < (1ll << 31) && dvd::g_w3_variant != 1;
     int e;
     if (h16) e = fw ? go(dvd::xwgrad1b_kernel<true, true>) : go(dvd::xwgrad1b_kernel<true, false>);
+    else if (rsum) e = go(dvd::xwgrad1b_kernel<false, true, true>);
     else e = fw ? go(dvd::xwgrad1b_kernel<false, true>) : go(dvd::xwgrad1b_kernel<false, false>);
     if (e) return e;
     DVD_LAUNCH_OK();
     const long long per = (long long)Cout * Cin;
-    hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const float*>(workspace), gw, S, 1, Cout, Cin);
+    const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout + 255) / 256) : 0u;
+    hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, S, 1,
+                       Cout, Cin, nmain, a.rowsum_partial, gy_rowsum, Cout);
     DVD_LAUNCH_OK();
-    return DVD_OK;
+    return rsum ? DVD_OK : chansum();
   }
   const int nco = (Cout + dvd::kW1CB - 1) / dvd::kW1CB, nci = (Cin + dvd::kW1CB - 1) / dvd::kW1CB;
   const int pairs = nco * nci;
@@ -1461,9 +1575,9 @@ static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, con
   DVD_LAUNCH_OK();
   const long long per = (long long)Cout * Cin;
   hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, S, 1, Cout, Cin);
+                     static_cast<const float*>(workspace), gw, S, 1, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
   DVD_LAUNCH_OK();
-  return DVD_OK;
+  return chansum();
 }
 
 }  // extern "C"

@@ -484,11 +484,23 @@ int dvd_xwgrad1s(const float* x, const float* x_amax, const float* gy, const flo
                  size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream);
 /* The same, and additionally (gy_rowsum != NULL) gy_rowsum[co] = sum over images and pixels of gy[n][co][:] -- the bias
  * gradient of the convolution / the shift gradient of a BatchNorm fused behind it (nn.Conv2d bias, BatchNorm2d.bias of the
- * ResNeXt bottlenecks behind third_party/midas_blocks.py:35-50), by one extra pass over gy in fixed order (deterministic).
+ * ResNeXt bottlenecks behind third_party/midas_blocks.py:35-50), deterministic: wide layers with H * W a multiple of 16 sum the
+ * rows inside the weight-gradient kernel, which stages them anyway (per-slice partial sums behind the dW partials in the
+ * workspace, added in slice order by the same reduction launch); every other shape takes one extra fixed-order pass over gy.
  * Workspace: dvd_xwgrad1s_workspace_bytes. */
 int dvd_xwgrad1s_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
                         void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in,
                         dvd_stream_t stream);
+/* dvd_xwgrad3 plus gy_rowsum (may be NULL), the same sums for the 3x3 case: grouped layers with at most 32 channels per group on
+ * both sides (ResNeXt stages 1-3) sum inside the weight-gradient kernel, every other shape by the extra pass.
+ * Workspace: dvd_xwgrad3_workspace_bytes. */
+int dvd_xwgrad3_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
+                       void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int groups, int relu_in,
+                       dvd_stream_t stream);
+/* 1 if the fp32 weight-gradient kernel that serves this shape (as selected now, see dvd_xwgrad_select) delivers gy_rowsum itself,
+ * 0 if dvd_xwgrad1s_rowsum (KS = 1, groups = 1) / dvd_xwgrad3_rowsum (KS = 3) would take the extra pass over gy: a caller that
+ * has a pass over gy of its own anyway keeps that one. */
+int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups);
 /* Test / A-B hook (process wide): 0 = automatic (256 x 256-channel workgroups for wide 1x1 layers, 128 x 128 otherwise),
  * 1 = always 128 x 128, 2 = round 3's row step everywhere (no buffer-load / interleaved-staging instantiations of the 3x3 and
  * wide 1x1 kernels, grouped layers on the 64 x 64 channel blocks).  Same products and the same per-element summation order
