@@ -606,7 +606,10 @@ class _AvgPool(torch.autograd.Function):
         gy = gy.contiguous()
         gx = torch.empty(N, C, H, W, device=gy.device, dtype=gy.dtype)
         _lib.check(_lib.load().dvd_avgpool_bwd(_p(gy), _p(gx), int(_is16(gy)), N * C, H, W, k, st, pad, _stream()), 'dvd_avgpool_bwd')
-        kg = known_amax(gy)                   # at most ceil(k / st)^2 windows of weight 1 / k^2 hold a pixel: |gx| <= max|gy|
+        # at most ceil(k / st)^2 windows of weight 1 / k^2 hold a pixel: |gx| <= ceil(k / st)^2 / k^2 * max|gy| <= max|gy|.  Attained
+        # only for stride 1 (AvgPool2d(2): a quarter, AvgPool2d(3, 2, 1): 4 / 9 of it), there up to the rounding of the summed
+        # quotients gy / k^2 -- ulps, far inside the two bits of headroom pow2_scale leaves (tests/test_41_operand_scales_gpu.py)
+        kg = known_amax(gy)
         return (gx if kg is None else set_amax(gx, kg)), None, None, None
 
 
@@ -622,7 +625,10 @@ class AvgPool2d(nn.AvgPool2d):
         if (x.is_cuda and x.dtype in ACT_DTYPES and x.dim() == 4 and None not in (k, st, pad) and not self.ceil_mode and
                 self.count_include_pad and self.divisor_override is None and 1 <= k <= 7 and 2 * pad <= k):
             y = _AvgPool.apply(x, k, st, pad)
-            kx = known_amax(x)                # an average of inputs (and padding zeros) never exceeds the largest magnitude
+            # an average of inputs (and padding zeros) never exceeds the largest magnitude -- up to the k^2 roundings of the window
+            # sum: a window of equal extremes can come out k^2 ulps above them for k >= 3 (never for the hourglass's k = 2).  The
+            # two bits of headroom pow2_scale leaves absorb that (tests/test_41_operand_scales_gpu.py)
+            kx = known_amax(x)
             return y if kx is None else set_amax(y, kx)
         return super().forward(x)
 

@@ -50,12 +50,13 @@ def golden_mlp_sd(gd, device='cpu', prefix='sd_'):
 
 def log_measured(name, value, bound):
     """Append one measured-vs-bound record to $DVD_PARITY_LOG (json lines) when it is set: the evidence visit keeps the
-    file under profiles/, so every tolerance in the tests sits next to the value it was derived from."""
+    file under profiles/, so every tolerance in the tests sits next to the value it was derived from.  bound=None: a value
+    that is recorded for later comparison and asserted nowhere."""
     import json
     import os
     if os.environ.get('DVD_PARITY_LOG'):
         with open(os.environ['DVD_PARITY_LOG'], 'a') as f:
-            f.write(json.dumps({'test': name, 'measured': float(value), 'bound': float(bound)}) + '\n')
+            f.write(json.dumps({'test': name, 'measured': float(value), 'bound': None if bound is None else float(bound)}) + '\n')
 
 
 def mlp_oracle_f64(sd, x, t=None, n_freq_xyz=16, n_freq_t=16, pre=None):

@@ -13,7 +13,9 @@ pytestmark = pytest.mark.gpu
                                               (2, 16, 24, 42, True, True), (1, 4, 96, 168, False, True),
                                               (2, 6, 5, 5, False, False),
                                               # small planes: several images of a channel per block in the backward pass
-                                              (8, 512, 12, 21, True, True), (6, 700, 7, 9, False, True)])
+                                              (8, 512, 12, 21, True, True), (6, 700, 7, 9, False, True),
+                                              # several chunks per plane: with H * W % 4 != 0 (the scalar loop), with N > 1
+                                              (1, 3, 65, 67, True, True), (3, 4, 96, 168, False, True)])
 def test_matches_aten(N, C, H, W, res, relu):
     from dvd_hip.conv import bn_eval_relu
     g = torch.Generator().manual_seed(C * 100 + H)
