@@ -212,6 +212,12 @@ SIGNATURES = {
     'dvd_union_gather': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
     'dvd_union_scatter': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
     'dvd_union_reduce': (c_int, [c_void_p] * 5 + [c_int, c_int, c_longlong, c_void_p]),
+    # the 8-per-group convolution with its BatchNorm+ReLU site in the kernels (csrc/gconv.hip; additions within ABI 8)
+    'dvd_gconv3x3_c8_bn_fwd': (c_int, [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    'dvd_gconv3x3_c8_bn_bwd_data': (c_int, [c_void_p] * 4 + [c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                            c_void_p]),
+    'dvd_gconv3x3_c8_bn_wgrad_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'dvd_gconv3x3_c8_bn_bwd_weight': (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1190,7 +1190,8 @@ class _XConvBn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x_amax, weight, cbias, gamma, beta, mean, var, eps, residual, relu, groups, alias=False, in_site=None,
-                out_site=None):
+                out_site=None, stride=1):
+        """stride 2: the 3x3 / stride 2 / padding 1 forms of the kernels (see _XConvS2), with the same site protocol."""
         ctx.set_materialize_grads(False)    # (alias: see _XConv -- the gradient of the input's other consumers arrives in backward)
         ctx.in_site = in_site if (in_site is not None and not AB['no_maskfuse']) else None      # see _Site
         ctx.out_site = out_site if relu else None
@@ -1200,10 +1201,11 @@ class _XConvBn(torch.autograd.Function):
         Cout, _, KS, _ = weight.shape
         y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, KS, bias=cbias, residual=residual, relu_out=relu,
-                       groups=groups, bn=(gamma, beta, mean, var, eps), x_amax=x_amax, y_amax=amax_slot)
+                       groups=groups, bn=(gamma, beta, mean, var, eps), x_amax=x_amax, y_amax=amax_slot,
+                       **({'stride': 2} if stride == 2 else {}))
         ctx.save_for_backward(x, y if relu else None, gamma, mean, var, cbias, x_amax)
         ctx.wparam = weight
-        ctx.cfg = (float(eps), bool(relu), residual is not None, groups)
+        ctx.cfg = (float(eps), bool(relu), residual is not None, groups, int(stride))
         if alias:
             return y, y_amax, x
         return y, y_amax
@@ -1212,9 +1214,9 @@ class _XConvBn(torch.autograd.Function):
     def backward(ctx, gy, _g_amax, g_alias=None):
         x, y, gamma, mean, var, cbias, x_amax = ctx.saved_tensors
         weight = ctx.wparam
-        eps, relu, has_res, groups = ctx.cfg
+        eps, relu, has_res, groups, stride = ctx.cfg
         if gy is None:                      # only the alias was used downstream
-            return (g_alias,) + (None,) * 14
+            return (g_alias,) + (None,) * 15
         gy = gy.contiguous()
         Cout, Cing, KS, _ = weight.shape
         N, _, H, W = gy.shape
@@ -1233,9 +1235,12 @@ class _XConvBn(torch.autograd.Function):
         # A ReLU site that masks for itself takes dbeta from the weight gradient call too (its pass runs for g and max|g| and
         # writes no sums): the sums are then the same bits however the mask was obtained, which
         # tests/test_09_fused_joins_gpu.py asserts of every gradient.  Sites without a ReLU have no such twin and keep their pass.
+        # (stride 2: the weight gradient runs at the input's resolution, on the zero-interleaved gradient -- the zeros add nothing
+        # to a sum; where that kernel does not sum, the site's pass below sums the compact gradient)
         grouped3 = KS == 3 and groups > 1
+        wH, wW = (x.shape[2], x.shape[3]) if stride == 2 else (H, W)
         wgrad_sums = (relu and need_w and gy.dtype == torch.float32 and (grouped3 or wgrad_reports_rowsum(weight.shape, groups)) and
-                      lib.dvd_xwgrad_rowsum_in_kernel(N, Cing * groups, Cout, H, W, KS, groups) == 1)
+                      lib.dvd_xwgrad_rowsum_in_kernel(N, Cing * groups, Cout, wH, wW, KS, groups) == 1)
         no_pass = premasked and wgrad_sums and ctx.out_site.amax is not None
         if relu:         # (sites_premasked says how the mask was obtained; sites_no_pass only under DVD_AB=rowsum)
             STATS['sites_no_pass' if (no_pass and AB['rowsum']) else ('sites_premasked' if premasked else 'sites_masked')] += 1
@@ -1254,29 +1259,126 @@ class _XConvBn(torch.autograd.Function):
                                             _stream()), 'dvd_bnrelu_bwd')
         gx = gw = gcb = gg = None
         if need[0]:                 # (+ the other consumers' gradient) * [x > 0] for the site x came from
+            strided = dict(stride=-2, out_hw=(x.shape[2], x.shape[3])) if stride == 2 else {}
             gx = _xconv_bwd_data(ctx, g, g_amax, weight, groups, x if ctx.in_site is not None else None, g_alias,
-                                 bn_scale=(gamma, var, eps))
+                                 bn_scale=(gamma, var, eps), **strided)
         elif g_alias is not None:
             gx = g_alias
         if need_w:
+            gf = g
+            if stride == 2:                 # the zero-interleaved gradient for the stride-1 weight gradient kernels (see _XConvS2)
+                gf = torch.empty(N, Cout, wH, wW, device=g.device, dtype=g.dtype)
+                _lib.check(lib.dvd_subsample2_bwd(_p(g), _p(gf), int(h16), N * Cout, wH, wW, _stream()), 'dvd_subsample2_bwd')
             if wgrad_sums and grouped3:
-                gw = xconv_wgrad3_rowsum(x, g, weight.shape, groups, x_amax, g_amax, dbeta)
+                gw = xconv_wgrad3_rowsum(x, gf, weight.shape, groups, x_amax, g_amax, dbeta)
             else:
-                gw = xconv_wgrad(x, g, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if wgrad_sums else None)
+                gw = xconv_wgrad(x, gf, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if wgrad_sums else None)
             gg = torch.empty_like(gamma) if gamma is not None else None
             gcb = torch.empty_like(cbias) if cbias is not None else None
             _lib.check(lib.dvd_convbn_finalize(_p(weight.detach()), _p(gw), _p(dbeta), _p(gamma), _p(mean), _p(var), eps,
                                                _p(cbias), Cout, Cing * KS * KS, _p(gg), _p(gcb), _stream()),
                        'dvd_convbn_finalize')
         return (gx, None, gw, gcb, gg, (dbeta if need[5] else None), None, None, None, (g if has_res else None), None, None, None,
-                None, None)
+                None, None, None)
+
+
+class _GConvBn(torch.autograd.Function):
+    """y = relu(bn_eval(conv2d(x, w, padding 1, groups C // 8))) for fp32 tensors with the site inside the kernels of
+    csrc/gconv.hip (dvd_gconv3x3_c8_bn_*): `_XConvBn`'s site protocol on the 8-per-group family.  The forward epilogue applies
+    BatchNorm + ReLU and leaves max|y|; backward-data takes the masked, unscaled gradient and scales it while staging, masks its
+    result for the site x came from (`in_site`) and leaves max|gx|; the weight gradient kernel delivers dbeta with dW, whether
+    the mask came pre-applied or from this site's own pass (the same bits either way).  The family takes no operand scales, so
+    a pre-masked site runs no pass at all."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, mean, var, eps, in_site, out_site):
+        ctx.set_materialize_grads(False)
+        ctx.in_site = in_site if (in_site is not None and not AB['no_maskfuse']) else None
+        ctx.out_site = out_site
+        x = x.contiguous()
+        N, C, H, W = x.shape
+        y = torch.empty_like(x)
+        y_amax = new_scalar(x.device)
+        ctx.mark_non_differentiable(y_amax)
+        _lib.check(_lib.load().dvd_gconv3x3_c8_bn_fwd(_p(x), _p(weight), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), _p(y),
+                                                      _p(y_amax), N, C, H, W, _stream()), 'dvd_gconv3x3_c8_bn_fwd')
+        ctx.save_for_backward(x, y, weight, gamma, mean, var)
+        ctx.eps = float(eps)
+        return y, y_amax
+
+    @staticmethod
+    def backward(ctx, gy, _g_amax):
+        x, y, weight, gamma, mean, var = ctx.saved_tensors
+        if gy is None:
+            return (None,) * 9
+        gy = gy.contiguous()
+        N, C, H, W = x.shape
+        eps = ctx.eps
+        need = ctx.needs_input_grad
+        lib = _lib.load()
+        premasked = ctx.out_site is not None and ctx.out_site.is_exactly(gy) and not AB['no_maskfuse']
+        STATS['sites_premasked' if premasked else 'sites_masked'] += 1
+        g = gy
+        if not premasked:                   # g = gy * [y > 0]; no sums, no maximum: the gradient kernels below need neither
+            g = torch.empty_like(gy)
+            ws = _workspace(lib.dvd_bnrelu_bwd_workspace_bytes(N, C, H * W), gy.device)
+            _lib.check(lib.dvd_bnrelu_bwd_t(_p(gy), _p(y), None, _p(var), _p(mean), _p(var), eps, None, _p(g), None, None, _p(ws),
+                                            ctypes.c_size_t(ws.numel()), 0, None, N, C, H * W, 1, None, _stream()), 'dvd_bnrelu_bwd')
+        gx = gw = gg = dbeta = None
+        if need[0]:
+            gx = torch.empty_like(x)
+            gx_amax = new_scalar(gy.device)
+            _lib.check(lib.dvd_gconv3x3_c8_bn_bwd_data(_p(g), _p(weight), _p(gamma), _p(var), eps,
+                                                       _p(x) if ctx.in_site is not None else None, _p(gx), _p(gx_amax), N, C, H, W,
+                                                       _stream()), 'dvd_gconv3x3_c8_bn_bwd_data')
+            set_amax(gx, gx_amax)
+            if ctx.in_site is not None:
+                ctx.in_site.wrote(gx, gx_amax)
+        if need[1] or need[2] or need[3]:
+            gw = torch.empty_like(weight)
+            dbeta = torch.empty(C, device=gy.device, dtype=torch.float32)
+            ws = _workspace(lib.dvd_gconv3x3_c8_bn_wgrad_workspace_bytes(N, C, H, W), gy.device)
+            _lib.check(lib.dvd_gconv3x3_c8_bn_bwd_weight(_p(x), _p(g), _p(gw), _p(dbeta), _p(ws), ctypes.c_size_t(ws.numel()), N, C,
+                                                         H, W, _stream()), 'dvd_gconv3x3_c8_bn_bwd_weight')
+            gg = torch.empty_like(gamma)
+            _lib.check(lib.dvd_convbn_finalize(_p(weight), _p(gw), _p(dbeta), _p(gamma), _p(mean), _p(var), eps, None, C, 72,
+                                               _p(gg), None, _stream()), 'dvd_convbn_finalize')
+        return gx, gw, gg, (dbeta if need[3] else None), None, None, None, None, None
+
+
+def _conv2_site_kind(conv, bn, x, residual, relu):
+    """Which fused site takes a ResNeXt `conv2` + BatchNorm + ReLU that xconv_supported does not cover -> 'c8' (8 per group:
+    csrc/gconv.hip), 'c16' (16 per group, stride 1: groups paired on the grouped xconv kernels), 's2' (3x3 / stride 2 on the
+    strided forms of xconv, stage 2's entry through the pairing) or None: conv(x) followed by bn_eval_relu.
+    fp32 storage only.  fp16 activations keep the composition: their passes move half the bytes, and the loss scale would have
+    to be threaded through dbeta and dvd_convbn_finalize first."""
+    if not (x.dtype == torch.float32 and relu and residual is None and bn.affine and conv.bias is None and
+            conv.weight.dtype == torch.float32 and conv.kernel_size == (3, 3) and tuple(conv.padding) == (1, 1) and
+            tuple(conv.dilation) == (1, 1) and conv.padding_mode == 'zeros' and x.dim() == 4):
+        return None
+    cpg, st = conv.in_channels // conv.groups, tuple(conv.stride)
+    if conv.in_channels != conv.out_channels and conv.groups > 1:
+        return None
+    if st == (1, 1):
+        if cpg == 8 and conv.groups > 1:
+            return 'c8'
+        if cpg == 16 and conv.groups > 1 and conv.in_channels % 32 == 0 and not AB['gconv32']:
+            return 'c16'
+        return None
+    if st == (2, 2) and not AB['no_s2']:
+        if cpg == 16 and conv.groups > 1:
+            return 's2' if (conv.in_channels % 32 == 0 and not AB['gconv32']) else None
+        if xconv_s2_supported(x, conv.weight, conv.groups):
+            return 's2'
+    return None
 
 
 def conv_bn_act(conv, bn, x, residual=None, relu=True, alias=False):
     """relu(bn(conv(x)) (+ residual)) for an nn.Conv2d followed by an eval-mode nn.BatchNorm2d.  Convolutions the xconv
-    kernels cover run as ONE launch (BatchNorm, residual and ReLU in the epilogue); everything else (CPU tensors,
-    training-mode statistics, the 8/16-per-group and strided 3x3 convolutions) is conv(x) followed by the fused
-    BatchNorm+ReLU kernel / the ATen ops.
+    kernels cover run as ONE launch (BatchNorm, residual and ReLU in the epilogue), and so do, for fp32 tensors, the ResNeXt
+    `conv2` layers outside that family: 8 and 16 channels per group and the 3x3 / stride 2 entries (_conv2_site_kind);
+    everything else (CPU tensors, training-mode statistics, those `conv2` layers with fp16 activations) is conv(x) followed by
+    the fused BatchNorm+ReLU kernel / the ATen ops.
     alias=True returns (y, x'): x' carries x's values and must be used by every OTHER consumer of x (the block's shortcut);
     on the fused path their gradient is then added inside this convolution's backward-data kernel instead of by autograd's
     accumulation pass (see _XConv); on the other paths x' is x itself."""
@@ -1297,6 +1399,24 @@ def conv_bn_act(conv, bn, x, residual=None, relu=True, alias=False):
             y = set_amax(out[0], out[1])
             if len(out) == 3:
                 return y, set_amax(out[2], x_amax)
+            return (y, x) if alias else y
+        kind = _conv2_site_kind(conv, bn, x, residual, relu)
+        if kind is not None:
+            in_site, out_site = getattr(x, '_dvd_site', None), _Site()
+            stats = (bn.running_mean, bn.running_var, bn.eps)
+            if kind == 'c8':
+                y, y_amax = _GConvBn.apply(x, conv.weight, bn.weight, bn.bias, *stats, in_site, out_site)
+            else:
+                # 16 per group: two groups share a 32-channel block of the grouped kernels (see GroupedConv3x3C16).  The paired
+                # weight is a tensor derived per call: it has no PACK_PLAN entry, so its packings (the scaled transposed one
+                # included) are launched with the pass, inside a captured graph too, and follow the parameters on every replay
+                w, groups = conv.weight, conv.groups
+                if w.shape[1] == 16:
+                    w, groups = _pair_groups_of_16(w), groups // 2
+                y, y_amax = _XConvBn.apply(x, amax_of(x), w, None, bn.weight, bn.bias, *stats, None, True, groups, False, in_site,
+                                           out_site, 2 if kind == 's2' else 1)
+            y._dvd_site = out_site
+            y = set_amax(y, y_amax)
             return (y, x) if alias else y
     y = bn_eval_relu(bn, conv(x), residual=residual, relu=relu)
     return (y, x) if alias else y

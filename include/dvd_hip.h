@@ -320,6 +320,23 @@ size_t dvd_gconv3x3_c8_wgrad_workspace_bytes(int N, int C, int H, int W);
 int dvd_gconv3x3_c8_bwd_weight(const float* x, const float* gy, float* gw, int accumulate, void* workspace,
                                size_t workspace_bytes, int N, int C, int H, int W, dvd_stream_t stream);
 
+/* The same convolution with the eval-mode BatchNorm + ReLU site behind it inside the kernels (fp32 storage; additions within
+ * ABI 8), so that no pre-BN tensor and no pass of csrc/bnrelu.hip exists for the layer.  s = gamma / sqrt(var + eps).
+ *   bn_fwd:        y = max(0, conv(x, w) * s + (beta - mean * s)); max|y| is folded into y_amax (optional, zeroed by the caller).
+ *   bn_bwd_data:   gx = conv_transpose(g * s, w) for the masked, UNSCALED gradient g = gy * [y > 0]; mask_src (optional, the
+ *                  layer's saved input): gx *= [mask_src > 0]; max|gx| is folded into gx_amax (optional, zeroed by the caller).
+ *   bn_bwd_weight: gw = the weight gradient of the unscaled g (dvd_convbn_finalize derives dW, dgamma from it) and
+ *                  g_chansum[c] = sum_{n,p} g[n][c][p] (dbeta), both summed in a fixed order (deterministic). */
+int dvd_gconv3x3_c8_bn_fwd(const float* x, const float* w, const float* gamma, const float* beta, const float* mean,
+                           const float* var, float eps, float* y, float* y_amax, int N, int C, int H, int W,
+                           dvd_stream_t stream);
+int dvd_gconv3x3_c8_bn_bwd_data(const float* g, const float* w, const float* gamma, const float* var, float eps,
+                                const float* mask_src, float* gx, float* gx_amax, int N, int C, int H, int W,
+                                dvd_stream_t stream);
+size_t dvd_gconv3x3_c8_bn_wgrad_workspace_bytes(int N, int C, int H, int W);
+int dvd_gconv3x3_c8_bn_bwd_weight(const float* x, const float* g, float* gw, float* g_chansum, void* workspace,
+                                  size_t workspace_bytes, int N, int C, int H, int W, dvd_stream_t stream);
+
 /* Same convolution with 32 channels per group (fp32 MFMA): the stride-1 bottlenecks of ResNeXt
  * stage 3 (width 1024 = 32 groups x 32).  w, gw: [C,32,3,3].  All three entry points take a workspace
  * of dvd_gconv3x3_c32_workspace_bytes (fragment-ordered weights for fwd / bwd_data, per-block
