@@ -218,6 +218,10 @@ SIGNATURES = {
                                             c_void_p]),
     'dvd_gconv3x3_c8_bn_wgrad_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'dvd_gconv3x3_c8_bn_bwd_weight': (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    # long-range tracks: projection into a sequence of target cameras (csrc/track.hip; additions within ABI 8)
+    'dvd_track_project': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 +
+                          [c_void_p]),
+    'dvd_project_bwd': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p]),
 }
 
 _lock = threading.Lock()

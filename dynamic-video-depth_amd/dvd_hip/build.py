@@ -43,6 +43,7 @@ SOURCES = [
     ('gather.hip', []),
     ('frame_store.hip', ['-ffp-contract=off']),
     ('frame_union.hip', ['-ffp-contract=off']),
+    ('track.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

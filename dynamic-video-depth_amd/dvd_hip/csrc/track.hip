@@ -1,0 +1,314 @@
+// World points -> pixel positions in a sequence of target cameras, with the target frame's depth sampled there (gfx950).
+//
+// Replaces project_ptcld.forward (/root/reference/losses/scene_flow_projection.py:27-44)
+//     Q = (P - t) @ R_T ;  I = Q @ K ;  (u, v) = I.xy / (I.z + 1e-8)
+// and, for the depth sample, BackwardWarp (:289-297) fed with that module's displacement field (u - x, v - y):
+// F.grid_sample(depth, (x, y) + displacement, bilinear, padding 'border', align_corners=True) -- the coordinate chain
+// (sample_coord) and the tap arithmetic (bilinear) are those of the fused warp+loss kernel (warp_pixel.h), as in
+// dvd_flow_warp_fwd.  The cameras are rows of per-frame tables: image b of step k looks up frame start[b] + k, so ONE launch
+// projects every step of an integrated trajectory (models/tracks.py); a frame past the end of the tables writes zeros and
+// reads nothing.  dvd_project_bwd is the 2x3 Jacobian of (u, v) w.r.t. P, transposed, per point.
+//
+// A pure map plus one 4-tap gather: 12 B read and 17 B written per point, plus the taps; no atomics, every output element
+// is written by exactly one thread with plain vector stores, so results are bitwise reproducible.  One thread per 4
+// horizontally adjacent pixels where the width is a multiple of 4 (16-byte accesses, the four `inside` bytes as one dword),
+// one pixel per thread otherwise.  Same fp32 operation order as torch's CPU matmul (dvd_common.h), built with
+// -ffp-contract=off; the division is the compiler's IEEE division (z is not bounded away from 0 here).
+
+#include "warp_pixel.h"
+
+namespace dvd {
+
+struct TrackArgs {
+  const float* points;        // [T1,B,3,H,W] (planar) or [T1,B,H,W,3]
+  const int* start;           // [B]
+  const float *R, *t, *K;     // [N,3,3], [N,3], [N,3,3]
+  const float* depth_all;     // [N,1,H,W] or null
+  float *uv, *z, *depth_at;   // [T1,B,H,W,2], [T1,B,H,W], [T1,B,H,W]   (z, depth_at may be null)
+  unsigned char* inside;      // [T1,B,H,W] or null
+  const float* g_uv;          // backward: [T1,B,H,W,2]
+  float* g_points;            // backward: the layout of points
+  int B, N, H, W, HW, displacement, accumulate;
+  float half_w, half_h, wmax, hmax;
+};
+
+struct TrackCam {
+  float R[9], K[9], t[3];
+};
+
+// the table row of image b at step k, or -1 where the video has ended (or the start is not a frame at all)
+__device__ __forceinline__ int target_frame(const TrackArgs& a, int b, int k) {
+  const int s = a.start[b];
+  const long long g = (long long)s + k;
+  return (s >= 0 && g < (long long)a.N) ? (int)g : -1;
+}
+
+__device__ __forceinline__ void load_track_cam(const TrackArgs& a, int g, TrackCam& c) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    c.R[i] = a.R[(size_t)g * 9 + i];
+    c.K[i] = a.K[(size_t)g * 9 + i];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) c.t[i] = a.t[(size_t)g * 3 + i];
+}
+
+// I = ((P - t) @ R_T) @ K: the one projection core of the forward and the backward
+__device__ __forceinline__ void project_point(const TrackCam& c, float P0, float P1, float P2, float& I0, float& I1,
+                                              float& I2) {
+  float Q0, Q1, Q2;
+  rowvec_mat3(P0 - c.t[0], P1 - c.t[1], P2 - c.t[2], c.R, Q0, Q1, Q2);
+  rowvec_mat3(Q0, Q1, Q2, c.K, I0, I1, I2);
+}
+
+template <int PX, bool PLANAR>
+__device__ __forceinline__ void load_points(const float* __restrict__ base, size_t img, int p0, int HW, float P[3][PX]) {
+  if (PLANAR) {
+    const float* s = base + img * 3 * HW + p0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (PX == 4)
+        *reinterpret_cast<float4*>(P[c]) = *reinterpret_cast<const float4*>(s + (size_t)c * HW);
+      else
+        P[c][0] = s[(size_t)c * HW];
+    }
+  } else {
+    const float* s = base + (img * HW + p0) * 3;
+    float v[3 * PX];
+    if (PX == 4) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) *reinterpret_cast<float4*>(v + 4 * q) = *reinterpret_cast<const float4*>(s + 4 * q);
+    } else {
+      v[0] = s[0];
+      v[1] = s[1];
+      v[2] = s[2];
+    }
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      P[0][i] = v[3 * i];
+      P[1][i] = v[3 * i + 1];
+      P[2][i] = v[3 * i + 2];
+    }
+  }
+}
+
+template <int PX, bool PLANAR>
+__global__ __launch_bounds__(256) void track_project_kernel(const TrackArgs a) {
+  const int b = blockIdx.y, k = blockIdx.z;
+  const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
+  if (p0 >= a.HW) return;
+  const size_t img = (size_t)k * a.B + b;
+  const size_t pix = img * a.HW + p0;
+  const int g = target_frame(a, b, k);      // uniform over the block
+  float u[PX], v[PX], zz[PX], d[PX];
+  unsigned int in[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    u[i] = v[i] = zz[i] = d[i] = 0.0f;
+    in[i] = 0u;
+  }
+  if (g >= 0) {
+    TrackCam c;
+    load_track_cam(a, g, c);
+    float P[3][PX];
+    load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
+    const int y = p0 / a.W, x = p0 - y * a.W;
+    const float yf = (float)y;
+    const float* dg = a.depth_all ? a.depth_all + (size_t)g * a.HW : nullptr;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      const float xf = (float)(x + i);
+      float I0, I1, I2;
+      project_point(c, P[0][i], P[1][i], P[2][i], I0, I1, I2);
+      const float den = I2 + 1e-8f;
+      const float ui = I0 / den, vi = I1 / den;
+      const float dx = ui - xf, dy = vi - yf;      // the module's displacement field
+      const bool front = I2 > 0.0f;
+      in[i] = (front && ui >= 0.0f && ui <= a.wmax && vi >= 0.0f && vi <= a.hmax) ? 1u : 0u;
+      if (dg && front) {
+        // always inside [0, W-1] x [0, H-1]: sample_coord clamps, and its fmaxf / fminf turn a NaN into 0
+        const float ix = sample_coord(xf, dx, a.half_w, a.wmax);
+        const float iy = sample_coord(yf, dy, a.half_h, a.hmax);
+        const float x0f = floorf(ix), y0f = floorf(iy);
+        const float ww = ix - x0f, we = 1.0f - ww, wn = iy - y0f, ws = 1.0f - wn;
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        const bool in_e = (x0 + 1) < a.W, in_s = (y0 + 1) < a.H;
+        const int o = y0 * a.W + x0;
+        const float dnw = dg[o], dne = in_e ? dg[o + 1] : 0.0f, dsw = in_s ? dg[o + a.W] : 0.0f,
+                    dse = (in_e && in_s) ? dg[o + a.W + 1] : 0.0f;
+        d[i] = bilinear(dnw, dne, dsw, dse, ws * we, ws * ww, wn * we, wn * ww);
+      }
+      u[i] = a.displacement ? dx : ui;
+      v[i] = a.displacement ? dy : vi;
+      zz[i] = I2;
+    }
+  }
+  if (PX == 4) {
+    float4* o = reinterpret_cast<float4*>(a.uv + pix * 2);
+    o[0] = make_float4(u[0], v[0], u[1], v[1]);
+    o[1] = make_float4(u[2], v[2], u[3], v[3]);
+    if (a.z) *reinterpret_cast<float4*>(a.z + pix) = make_float4(zz[0], zz[1], zz[2], zz[3]);
+    if (a.depth_all) *reinterpret_cast<float4*>(a.depth_at + pix) = make_float4(d[0], d[1], d[2], d[3]);
+    if (a.inside) *reinterpret_cast<unsigned int*>(a.inside + pix) = in[0] | (in[1] << 8) | (in[2] << 16) | (in[3] << 24);
+  } else {
+    a.uv[pix * 2] = u[0];
+    a.uv[pix * 2 + 1] = v[0];
+    if (a.z) a.z[pix] = zz[0];
+    if (a.depth_all) a.depth_at[pix] = d[0];
+    if (a.inside) a.inside[pix] = (unsigned char)in[0];
+  }
+}
+
+// g_P (+)= J^T g_uv with u = I0 / den, v = I1 / den, den = I2 + 1e-8:
+//   g_I = (g_u / den, g_v / den, -(g_u u + g_v v) / den) ;  g_P = (g_I @ K^T) @ R_T^T
+template <int PX, bool PLANAR>
+__global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
+  const int b = blockIdx.y, k = blockIdx.z;
+  const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
+  if (p0 >= a.HW) return;
+  const size_t img = (size_t)k * a.B + b;
+  const size_t pix = img * a.HW + p0;
+  const int g = target_frame(a, b, k);
+  float G[3][PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) G[0][i] = G[1][i] = G[2][i] = 0.0f;
+  if (g >= 0) {
+    TrackCam c;
+    load_track_cam(a, g, c);
+    float P[3][PX], gu[PX], gv[PX];
+    load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
+    if (PX == 4) {
+      const float4* s = reinterpret_cast<const float4*>(a.g_uv + pix * 2);
+      const float4 lo = s[0], hi = s[1];
+      gu[0] = lo.x, gv[0] = lo.y, gu[1] = lo.z, gv[1] = lo.w;
+      gu[2] = hi.x, gv[2] = hi.y, gu[3] = hi.z, gv[3] = hi.w;
+    } else {
+      gu[0] = a.g_uv[pix * 2];
+      gv[0] = a.g_uv[pix * 2 + 1];
+    }
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      float I0, I1, I2;
+      project_point(c, P[0][i], P[1][i], P[2][i], I0, I1, I2);
+      const float den = I2 + 1e-8f;
+      const float ui = I0 / den, vi = I1 / den;
+      const float gI0 = gu[i] / den, gI1 = gv[i] / den;
+      const float gI2 = -(gu[i] * ui + gv[i] * vi) / den;
+      float q0, q1, q2;
+      rowvec_mat3_T(gI0, gI1, gI2, c.K, q0, q1, q2);
+      rowvec_mat3_T(q0, q1, q2, c.R, G[0][i], G[1][i], G[2][i]);
+    }
+  }
+  if (PLANAR) {
+    float* o = a.g_points + img * 3 * a.HW + p0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float* dst = o + (size_t)ch * a.HW;
+      if (PX == 4) {
+        float4 w = make_float4(G[ch][0], G[ch][1], G[ch][2], G[ch][3]);
+        if (a.accumulate) {
+          const float4 old = *reinterpret_cast<const float4*>(dst);
+          w.x += old.x, w.y += old.y, w.z += old.z, w.w += old.w;
+        }
+        *reinterpret_cast<float4*>(dst) = w;
+      } else {
+        dst[0] = a.accumulate ? dst[0] + G[ch][0] : G[ch][0];
+      }
+    }
+  } else {
+    float* o = a.g_points + pix * 3;
+    float w[3 * PX];
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      w[3 * i] = G[0][i];
+      w[3 * i + 1] = G[1][i];
+      w[3 * i + 2] = G[2][i];
+    }
+    if (PX == 4) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        float4 n = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+        if (a.accumulate) {
+          const float4 old = *reinterpret_cast<const float4*>(o + 4 * q);
+          n.x += old.x, n.y += old.y, n.z += old.z, n.w += old.w;
+        }
+        *reinterpret_cast<float4*>(o + 4 * q) = n;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) o[q] = a.accumulate ? o[q] + w[q] : w[q];
+    }
+  }
+}
+
+static bool track_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static int track_shape_ok(const char* who, int T1, int B, int N, int H, int W) {
+  DVD_REQUIRE(T1 > 0 && T1 <= 65535 && B > 0 && B <= 65535 && N > 0, "%s: bad sizes T1=%d B=%d N=%d", who, T1, B, N);
+  DVD_REQUIRE(H >= 2 && W >= 2 && (long long)H * W < (1LL << 30), "%s: bad image size H=%d W=%d", who, H, W);
+  return DVD_OK;
+}
+
+}  // namespace dvd
+
+extern "C" {
+
+int dvd_track_project(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                      const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                      float* depth_at, unsigned char* inside, int T1, int B, int H, int W, dvd_stream_t stream) {
+  using namespace dvd;
+  DVD_REQUIRE(points && start && R && t && K_T && uv, "track_project: null pointer");
+  DVD_REQUIRE(!depth_all || depth_at, "track_project: depth_all without depth_at");
+  if (int st = track_shape_ok("track_project", T1, B, N, H, W)) return st;
+  TrackArgs a = {};
+  a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.depth_all = depth_all;
+  a.uv = uv, a.z = z, a.depth_at = depth_all ? depth_at : nullptr, a.inside = inside;
+  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.displacement = displacement;
+  a.half_w = (float)((W - 1) / 2.0), a.half_h = (float)((H - 1) / 2.0), a.wmax = (float)(W - 1), a.hmax = (float)(H - 1);
+  const double pts = (double)T1 * B * a.HW;
+  bytes_add(DVD_BYTES_GEOMETRY, pts * (12.0 + 8.0 + (z ? 4.0 : 0.0) + (inside ? 1.0 : 0.0) + (depth_all ? 4.0 : 0.0)) +
+                                    (depth_all ? 4.0 * (double)(N < T1 + B ? N : T1 + B) * a.HW : 0.0));
+  const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(uv) && track_aligned16(z) &&
+                  track_aligned16(a.depth_at) && track_aligned16(inside);
+  const int px = v4 ? 4 : 1;
+  dim3 grid((a.HW + 256 * px - 1) / (256 * px), B, T1), block(256);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (v4 && points_planar)
+    hipLaunchKernelGGL((track_project_kernel<4, true>), grid, block, 0, s, a);
+  else if (v4)
+    hipLaunchKernelGGL((track_project_kernel<4, false>), grid, block, 0, s, a);
+  else if (points_planar)
+    hipLaunchKernelGGL((track_project_kernel<1, true>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((track_project_kernel<1, false>), grid, block, 0, s, a);
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, const int* start, const float* R,
+                    const float* t, const float* K_T, int N, float* g_points, int accumulate, int T1, int B, int H, int W,
+                    dvd_stream_t stream) {
+  using namespace dvd;
+  DVD_REQUIRE(g_uv && points && start && R && t && K_T && g_points, "project_bwd: null pointer");
+  if (int st = track_shape_ok("project_bwd", T1, B, N, H, W)) return st;
+  TrackArgs a = {};
+  a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.g_uv = g_uv, a.g_points = g_points;
+  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.accumulate = accumulate;
+  bytes_add(DVD_BYTES_GEOMETRY, (double)T1 * B * a.HW * (accumulate ? 44.0 : 32.0));
+  const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(g_uv) && track_aligned16(g_points);
+  const int px = v4 ? 4 : 1;
+  dim3 grid((a.HW + 256 * px - 1) / (256 * px), B, T1), block(256);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (v4 && points_planar)
+    hipLaunchKernelGGL((project_bwd_kernel<4, true>), grid, block, 0, s, a);
+  else if (v4)
+    hipLaunchKernelGGL((project_bwd_kernel<4, false>), grid, block, 0, s, a);
+  else if (points_planar)
+    hipLaunchKernelGGL((project_bwd_kernel<1, true>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((project_bwd_kernel<1, false>), grid, block, 0, s, a);
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 """Geometry modules with the reference's names and forward signatures, on HIP kernels.
 
 Counterparts of /root/reference/losses/scene_flow_projection.py:
+  project_ptcld                :21-44    world points -> displacement of their projection [B,H,W,2]
   unproject_ptcld              :48-67    depth -> world points [B,H,W,1,3]
   flow_by_depth                :95-153   (forward signature kept; see below)
   scene_flow_projection_slack  :204-278  (forward signature kept; see below)
@@ -41,6 +42,62 @@ class unproject_ptcld(nn.Module):
 
     def forward(self, depth_1, R_1, t_1, K_inv):
         return _Unproject.apply(depth_1, R_1, t_1, K_inv)
+
+
+_own = {}
+
+
+def _own_cameras(B, device):
+    """start = (0 .. B-1): image b into camera b, as a device int32 tensor (uploaded once per batch size and device) and
+    its host copy."""
+    key = (B, str(device))
+    if key not in _own:
+        ids = list(range(B))
+        _own[key] = (torch.tensor(ids, dtype=torch.int32).to(device), ids)
+    return _own[key]
+
+
+class _Project(torch.autograd.Function):
+    """project_ptcld on dvd_track_project (one step, image b into camera b) / dvd_project_bwd."""
+
+    @staticmethod
+    def forward(ctx, global_p1, R_1_T, t_1, K):
+        B, H, W = global_p1.shape[:3]
+        points = ops._dev32(global_p1, 'global_p1').view(1, B, H, W, 3)
+        tables = {'R': R_1_T.reshape(B, 3, 3), 't': t_1.reshape(B, 3), 'K_T': K.reshape(B, 3, 3)}
+        start, ids = _own_cameras(B, points.device)
+        out = ops.track_project(points, start, tables, planar=False, displacement=True, host_start=ids, want=())
+        ctx.save_for_backward(points, start, *[tables[k] for k in ops.TRACK_TABLES])
+        return out['uv'].view(B, H, W, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        points, start, R, t, K_T = ctx.saved_tensors
+        _, B, H, W, _ = points.shape
+        g_p = ops.project_backward(g.contiguous().view(1, B, H, W, 2), points, start, {'R': R, 't': t, 'K_T': K_T},
+                                   planar=False, host_start=list(range(B)))
+        return g_p.view(B, H, W, 1, 3), None, None, None
+
+
+class project_ptcld(nn.Module):
+    """losses/scene_flow_projection.py:21-44: the displacement (u - x, v - y) of world points [B,H,W,1,3] projected into camera
+    b, with the reference's trailing .squeeze(); differentiable w.r.t. global_p1 (the cameras are data)."""
+
+    def __init__(self, is_one_way=True):
+        super().__init__()
+
+    def forward(self, global_p1, R_1_T, t_1, K):
+        if not torch.is_tensor(global_p1) or global_p1.dim() != 5 or tuple(global_p1.shape[3:]) != (1, 3):
+            raise ValueError('project_ptcld: global_p1 must be [B,H,W,1,3], got %s' % (
+                tuple(global_p1.shape) if torch.is_tensor(global_p1) else type(global_p1).__name__,))
+        B, H, W = global_p1.shape[:3]
+        if B < 1 or H < 2 or W < 2:
+            raise ValueError('project_ptcld: needs at least one image of at least 2 x 2 pixels, got B=%d H=%d W=%d' % (B, H, W))
+        for name, cam, shape in (('R_1_T', R_1_T, (B, 1, 1, 3, 3)), ('t_1', t_1, (B, 1, 1, 1, 3)), ('K', K, (B, 1, 1, 3, 3))):
+            if not torch.is_tensor(cam) or tuple(cam.shape) != shape:
+                raise ValueError('project_ptcld: %s must be %s, got %s' % (
+                    name, shape, tuple(cam.shape) if torch.is_tensor(cam) else type(cam).__name__))
+        return _Project.apply(global_p1, R_1_T, t_1, K).squeeze()
 
 
 class _WarpSurfaces(torch.autograd.Function):

@@ -45,7 +45,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import frame_union
+from . import frame_union, tracks
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 
@@ -974,6 +974,26 @@ class Model(NetInterface):
         ts = inp.time_stamp_1 if self.opt.time_dependent else None
         self._mlp.forward(P, ts, 0.0, 1.0 / self.opt.sf_mag_div, sf_out=sf)
         return {'depth': depth, 'sf_1_2': sf}
+
+    # -- after the optimisation: whole-video depth and long-range tracks (models/tracks.py) -----------------------------------
+    def video_depth(self, frames):
+        """Refined depth of a whole video -> [N,1,H,W] on the device.  frames: the validation view (FrameStore.frames(b), or
+        any iterable of `vali` items); every batch goes through the depth net exactly as _predict_on_batch(is_train=False)
+        runs it (eval mode, no autograd state), so the result is that path's 'depth', frame by frame, bit for bit."""
+        return tracks.video_depth(self, frames)
+
+    def track(self, store, start, n_steps, depth=None, chunk=None):
+        """Where the pixels of the frames `start` are 1 .. n_steps frames later: the scene-flow MLP integrated by Euler steps
+        (forward_sf_net_multi_step, :360-367) from the un-projected refined depth, and every step projected into the camera of
+        its target frame.  store: the video's FrameStore; depth: [N,1,H,W] refined depth (default: video_depth of the store).
+        Returns device tensors, step-major (T1 = n_steps + 1, B = len(start); step 0 is the start frame itself):
+          points [T1,B,3,H,W]  world positions;  uv [T1,B,H,W,2], z [T1,B,H,W]  pixel position and depth in frame start + k
+          depth_at [T1,B,H,W]  that frame's refined depth at uv (0 behind the camera);  inside uint8 [T1,B,H,W]  in front of
+          the camera and within the image;  steps_valid int32 [B]  steps with a target frame -- rows past it are zero.
+        chunk: start frames per pass of the chain (default: 8 GB of world points); the result does not depend on it.  The
+        un-masked field drives the chain, as in training (--use_motion_seg only masks the flow handed to the warp);
+        --use_cnn raises NotImplementedError."""
+        return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk)
 
     def _train_pred(self):
         """The reference's train-time `pred` dict (:243-264 + `sf_loss_pp` of :308), materialised on demand from the

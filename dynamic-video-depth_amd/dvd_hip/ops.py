@@ -48,12 +48,17 @@ def warp_cfg(B, H, W, midas_mask=True, crit_l2=False, disp_mode=1, loss_on_sf=Fa
                         int(bool(loss_on_sf)), float(flow_mul), float(disp_mul))
 
 
-def unproject(depth, R, t, K_inv, planar=True):
-    """depth [B,1,H,W] -> world points, [B,3,H,W] (planar) or [B,H,W,1,3]."""
+def unproject(depth, R, t, K_inv, planar=True, out=None):
+    """depth [B,1,H,W] -> world points, [B,3,H,W] (planar) or [B,H,W,1,3]; out: optional destination of that shape."""
     depth = _dev32(depth, 'depth')
     R, t, K_inv = _dev32(R, 'R'), _dev32(t, 't'), _dev32(K_inv, 'K_inv')
     B, _, H, W = depth.shape
-    out = torch.empty((B, 3, H, W) if planar else (B, H, W, 1, 3), device=depth.device, dtype=torch.float32)
+    shape = (B, 3, H, W) if planar else (B, H, W, 1, 3)
+    if out is None:
+        out = torch.empty(shape, device=depth.device, dtype=torch.float32)
+    elif not (torch.is_tensor(out) and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
+              and out.is_contiguous()):
+        raise RuntimeError('unproject: out must be a contiguous float32 tensor %s on the device of the depth' % (shape,))
     lib = _lib.load()
     _lib.check(lib.dvd_unproject_fwd(_p(depth), _p(R), _p(t), _p(K_inv), _p(out), int(planar), B, H, W, _stream()),
                'dvd_unproject_fwd')
@@ -76,6 +81,112 @@ def unproject_backward(g_points, planar, R, K_inv, scale=None, out=None, accumul
     lib = _lib.load()
     _lib.check(lib.dvd_unproject_bwd(_p(g_points), int(planar), _p(R), _p(K_inv), _p(scale), _p(out),
                                      int(bool(accumulate)), B, H, W, _stream()), 'dvd_unproject_bwd')
+    return out
+
+
+TRACK_TABLES = ('R', 't', 'K_T')
+
+
+def _track_args(what, points, start, tables, planar, host_start):
+    """Everything track_project and project_backward check before a launch -> (points, start on the device, the three tables,
+    T1, B, H, W, N).  Runs on the host; a CPU tensor is refused before any shape is looked at."""
+    import numpy as np
+    points = _dev32(points, 'points')
+    if points.dim() != 5 or points.shape[2 if planar else 4] != 3 or points.numel() == 0:
+        raise RuntimeError('%s: points must be [T1,B,3,H,W] (planar) or [T1,B,H,W,3], got %s' % (what, tuple(points.shape)))
+    T1, B = int(points.shape[0]), int(points.shape[1])
+    H, W = (int(v) for v in (points.shape[3:5] if planar else points.shape[2:4]))
+    if H < 2 or W < 2:
+        raise RuntimeError('%s: images of %d x %d; the sampling rule needs H, W >= 2' % (what, H, W))
+    if T1 > 65535 or B > 65535:
+        raise RuntimeError('%s: at most 65535 steps and 65535 images per launch, got %d and %d' % (what, T1, B))
+    tabs = []
+    for k in TRACK_TABLES:
+        if k not in tables:
+            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRACK_TABLES)))
+        tab = _dev32(tables[k], 'table ' + k)
+        if tab.device != points.device:
+            raise RuntimeError('%s: table %s and the points are on different devices' % (what, k))
+        tabs.append(tab)
+    N = int(tabs[0].shape[0]) if tabs[0].dim() > 0 else 0
+    for k, tab, per in zip(TRACK_TABLES, tabs, (9, 3, 9)):
+        if N <= 0 or tab.dim() < 2 or tab.shape[0] != N or tab.numel() != N * per:
+            raise RuntimeError('%s: table %s must hold %d values for each of %d frames, got %s' % (what, k, per, N, tuple(tab.shape)))
+    if torch.is_tensor(start) and start.is_cuda:
+        if start.dtype != torch.int32 or start.dim() != 1 or not start.is_contiguous() or start.device != points.device:
+            raise RuntimeError('%s: start must be a contiguous GPU int32 tensor of %d frame ids on the device of the points' % (what, B))
+        host = np.asarray(start.cpu() if host_start is None else host_start)
+    else:
+        host = np.asarray(start.cpu() if torch.is_tensor(start) else start)
+        start = None
+    if host.dtype.kind == 'f' and host.size and np.all(np.isfinite(host)) and np.all(host == np.floor(host)):
+        host = host.astype(np.int64)
+    if host.dtype.kind not in 'iu' or host.shape != (B,):
+        raise RuntimeError('%s: start must hold %d integral frame ids, got %s %s' % (what, B, host.dtype, host.shape))
+    if int(host.min()) < 0 or int(host.max()) >= N:
+        raise RuntimeError('%s: start spans [%d, %d], outside the %d frames of the tables' % (what, int(host.min()), int(host.max()), N))
+    if start is None:
+        start = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(points.device)
+    return points, start, tabs, T1, B, H, W, N
+
+
+def track_project(points, start, tables, depth_all=None, out=None, planar=True, displacement=False, host_start=None,
+                  want=('z', 'inside')):
+    """World points into the cameras of frames start[b] + k (dvd_track_project, csrc/track.hip) -> dict of uv [T1,B,H,W,2], z
+    [T1,B,H,W], inside uint8 [T1,B,H,W] and, with depth_all [N,1,H,W], depth_at [T1,B,H,W].
+      points   [T1,B,3,H,W] (planar: a slab of the scene-flow MLP's p_next rows) or [T1,B,H,W,3]
+      start    B frame ids: a host sequence / array / CPU tensor (uploaded here) or a GPU int32 tensor, then host_start, its
+               host copy, saves the read-back the range check needs otherwise
+      tables   {'R': [N,3,3] world->camera, 't': [N,3], 'K_T': [N,3,3]} -- FrameStore.tables has them under these names
+      out      optional dict of preallocated outputs;  want: which of the optional 'z' / 'inside' to compute
+      displacement  uv minus the pixel's own (x, y): project_ptcld's return value
+    Frames past the end of the tables give zeros.  Everything is checked on the host before the launch."""
+    what = 'track_project'
+    points, start, (R, t, K_T), T1, B, H, W, N = _track_args(what, points, start, tables, planar, host_start)
+    dev = points.device
+    if depth_all is not None:
+        depth_all = _dev32(depth_all, 'depth_all')
+        if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
+            raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
+                what, N, H, W, tuple(depth_all.shape)))
+    shapes = {'uv': ((T1, B, H, W, 2), torch.float32)}
+    if 'z' in want:
+        shapes['z'] = ((T1, B, H, W), torch.float32)
+    if 'inside' in want:
+        shapes['inside'] = ((T1, B, H, W), torch.uint8)
+    if depth_all is not None:
+        shapes['depth_at'] = ((T1, B, H, W), torch.float32)
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        o = out.get(k) if out is not None else None
+        if o is None:
+            o = torch.empty(shape, device=dev, dtype=dtype)
+        elif not (torch.is_tensor(o) and o.device == dev and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
+            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the points' % (what, k, dtype, shape))
+        res[k] = o
+    _lib.check(_lib.load().dvd_track_project(_p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N,
+                                             _p(res['uv']), int(bool(displacement)), _p(res.get('z')), _p(res.get('depth_at')),
+                                             _p(res.get('inside')), T1, B, H, W, _stream()), 'dvd_track_project')
+    return res
+
+
+def project_backward(g_uv, points, start, tables, planar=True, out=None, accumulate=False, host_start=None):
+    """g_points (+)= J^T g_uv for track_project's uv (dvd_project_bwd): g_uv [T1,B,H,W,2], the result in the layout of
+    points.  Cameras get no gradient; a frame past the end of the tables contributes 0."""
+    what = 'project_backward'
+    points, start, (R, t, K_T), T1, B, H, W, N = _track_args(what, points, start, tables, planar, host_start)
+    g_uv = _dev32(g_uv, 'g_uv')
+    if g_uv.device != points.device or tuple(g_uv.shape) != (T1, B, H, W, 2):
+        raise RuntimeError('%s: g_uv must be %s on the device of the points, got %s' % (what, (T1, B, H, W, 2), tuple(g_uv.shape)))
+    if out is None:
+        if accumulate:
+            raise RuntimeError('accumulate=True needs an output tensor')
+        out = torch.empty_like(points)
+    elif not (torch.is_tensor(out) and out.device == points.device and out.dtype == torch.float32 and
+              out.shape == points.shape and out.is_contiguous()):
+        raise RuntimeError('%s: out must be a contiguous float32 tensor shaped like points' % what)
+    _lib.check(_lib.load().dvd_project_bwd(_p(g_uv), _p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), N, _p(out),
+                                           int(bool(accumulate)), T1, B, H, W, _stream()), 'dvd_project_bwd')
     return out
 
 
@@ -291,7 +402,7 @@ BYTE_CLASS_KERNELS = {
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_',), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

@@ -740,6 +740,35 @@ int dvd_union_scatter(const void* D, void* depth_1, void* depth_2, const int* u1
 int dvd_union_reduce(const float* g_d1, const float* g_d2, float* G, const int* offsets, const int* entries, int U_pad, int B,
                      long long floats_per_row, dvd_stream_t stream);
 
+/* Long-range tracks: world points into a sequence of target cameras (additions within ABI 8; csrc/track.hip, models/tracks.py).
+ * dvd_track_project replaces project_ptcld.forward (losses/scene_flow_projection.py:27-44) and, for depth_at, BackwardWarp
+ * (:289-297) applied to that module's displacement field; dvd_project_bwd is what autograd derives from :38-41 for global_p1.
+ *   points     [T1, B, 3, H, W] (points_planar != 0: the layout the scene-flow MLP's p_next writes, one slab row per
+ *              integration step) or [T1, B, H, W, 3]
+ *   start      DEVICE array of B ints: image b of step k is projected into frame g = start[b] + k
+ *   R, t, K_T  the per-frame tables [N, 3, 3], [N, 3], [N, 3, 3]: world->camera rotation (the reference's R_1_T), camera
+ *              centre, transposed intrinsics (the reference's K), as datasets/frame_store.py keeps them
+ *   depth_all  [N, 1, H, W] or NULL
+ * Outputs, per point, with I = ((P - t_g) @ R_g) @ K_T_g in torch's fp32 operation order:
+ *   uv         [T1, B, H, W, 2] = I.xy / (I.z + 1e-8); with displacement != 0 minus the pixel's own (x, y), which is
+ *              project_ptcld's return value
+ *   z          [T1, B, H, W] = I.z (may be NULL)
+ *   depth_at   [T1, B, H, W] = depth_all[g] sampled at uv by grid_sample's rule (bilinear, border, align_corners=True), 0
+ *              where z <= 0; not written when depth_all is NULL
+ *   inside     uint8 [T1, B, H, W] = z > 0 && 0 <= u <= W - 1 && 0 <= v <= H - 1 (may be NULL)
+ * Where g >= N (the video has ended; a negative start counts the same) every output is 0 and no table is read.  No index
+ * derived from the data leaves a table: the sampling position is clamped to the image, NaN included.  No atomics; every
+ * output element has one writer.  16-byte accesses (and the four `inside` bytes of a thread as one dword) where W is a
+ * multiple of 4 and the bases are 16-byte aligned, one pixel per thread otherwise.
+ * dvd_project_bwd: g_points (+)= J^T g_uv, J the 2x3 Jacobian of uv w.r.t. the point (0 where g >= N); g_points has the
+ * layout of points; the cameras get no gradient.  T1, B <= 65535, H, W >= 2; bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_track_project(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                      const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                      float* depth_at, unsigned char* inside, int T1, int B, int H, int W, dvd_stream_t stream);
+int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, const int* start, const float* R,
+                    const float* t, const float* K_T, int N, float* g_points, int accumulate, int T1, int B, int H, int W,
+                    dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
