@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "dvd_split.h"
+#include "wg3_plan.h"
 
 namespace dvd {
 
@@ -34,6 +35,7 @@ typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 
 static int g_w1_variant = 0;      // test / A-B hook (dvd_xwgrad_select): 0 auto, 1 always the 128 x 128 blocks
 static int g_w3_variant = 0;      // 1 (hook value 2): the 3x3 kernel's round-3 row step (staging ahead of the MFMAs) on every shape
+static int g_w3_deal = 0;         // 1 (hook value 3): four K steps per row step and the round-robin deal of whole items (wg3_plan.h)
 
 struct Wg3Args {
   const void* __restrict__ x;         // float, or _Float16 in the H16 kernels (fp16 activation storage, BASELINE configs[4])
@@ -47,6 +49,8 @@ struct Wg3Args {
   int N, Cin, Cout, H, W;        // Cin / Cout per group
   int G, nco;                    // groups, output-channel blocks per group
   int nstrips, RS, nrseg, S;     // column strips per image, rows per work item, row segments per image, slices
+  int strip0, ncols;             // this launch walks the strips [strip0, strip0 + ncols) of every image ...
+  int slice0, deal;              // ... and writes the partial slices [slice0, slice0 + S); deal: whole items, round robin (wg3_plan.h)
   int relu_in;
 };
 
@@ -143,12 +147,28 @@ __device__ __forceinline__ uint4 load_oct_h(const void* row, int px, int n, bool
   return v;
 }
 
-constexpr int kW3Strip = 64;                  // pixels per row step
-constexpr int kW3GPitch = 128 + 16;           // bytes per gy row in LDS (64 fp16 + pad: conflict-free 16-byte reads across rows)
-constexpr int kW3XPitch = 160 + 16;           // bytes per x row in LDS (80 fp16 + pad)
-constexpr int kW3CB = 64;                     // channels per block, both operands
-constexpr int kW3NT = 768;                    // 12 waves: 2 x 2 tile pairs x 3 kernel rows
-constexpr int kW3LdsBytes = 2 * 2 * kW3CB * kW3GPitch + 2 * kW3CB * 4 * kW3XPitch;   // + 16 spare bytes (idle staging items)
+constexpr int kW3NT = 768;                    // 12 waves: 2 x 2 tile pairs x 3 kernel rows (strip, pitches, LDS bytes: wg3_plan.h)
+
+// Live K steps: a row step runs NK = ceil(min(64, W - c0) / 16) K steps, the ones that hold pixels of the row.
+// NK is a template parameter of the three walking kernels -- the staging registers stay indexed by constants, the row step
+// stays one basic block, and a kernel holds ONE row loop (four loops behind a block-uniform switch cost xwgrad3_kernel 40
+// VGPRs and put 112 dwords into scratch) -- and the strips of one NK are a launch of their own (wg3_plan.h).  Every staging
+// item is still loaded and stored (the ones wholly past the row's end as zeros), so no LDS cell a live K step reads -- the
+// neighbour dwords of the first and last live cell included -- ever holds another segment's data; item i rides behind K step
+// i % NK.
+// The walk of a slice is the same in every lane: its state and results are kept in scalar registers.
+#define DVD_WG_WALK_BEGIN(a)                             \
+  int wcur, wend;                                        \
+  wg_walk_begin(a, (int)blockIdx.x, wcur, wend);         \
+  wcur = __builtin_amdgcn_readfirstlane(wcur);           \
+  wend = __builtin_amdgcn_readfirstlane(wend);           \
+  while (wcur < wend)
+#define DVD_WG_WALK_SEGMENT(a)                                               \
+  int wn, wstrip, wr0, wr1, wnext;                                           \
+  wg_walk_segment(a, wcur, wend, wn, wstrip, wr0, wr1, wnext);               \
+  wcur = __builtin_amdgcn_readfirstlane(wnext);                              \
+  const int n = __builtin_amdgcn_readfirstlane(wn), c0 = __builtin_amdgcn_readfirstlane(wstrip) * kW3Strip; \
+  const int r0 = __builtin_amdgcn_readfirstlane(wr0), r1 = __builtin_amdgcn_readfirstlane(wr1);
 
 // FW (host: rows of fp16 elements start dword-aligned, i.e. W even; any W for fp32): every staging item is a 16-byte run of one
 // row (a run crossing the row's end is loaded whole and its tail zeroed on the way to LDS, as in xwgrad3g_kernel) or nothing,
@@ -157,7 +177,7 @@ constexpr int kW3LdsBytes = 2 * 2 * kW3CB * kW3GPitch + 2 * kW3CB * 4 * kW3XPitc
 // basic block, the staging work of item i (split + LDS store of the row loaded a step ago, request of the row two steps ahead)
 // sits between the MFMAs of K step i: round 3 ran `barrier | all staging | all MFMAs` in every wave, the 12 waves in lock step
 // behind the barrier, and the counters showed matrix pipe and VALU taking turns (55 % busy at 5.5 VALU per MFMA).
-template <bool H16, bool FW>
+template <bool H16, bool FW, int NK = 4>
 __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
   constexpr int EB = H16 ? 2 : 4;                // bytes per element in HBM
   constexpr int NTERM = H16 ? 1 : 2;
@@ -172,7 +192,6 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
   const int grp = blockIdx.z / a.nco;                      // group of a grouped convolution (0 for dense)
   const int co0 = (blockIdx.z - grp * a.nco) * kW3CB, ci0 = blockIdx.y * kW3CB;
   const size_t plane = (size_t)a.H * a.W;
-  const int items = a.N * a.nstrips * a.nrseg;
 
   // staging assignment: a thread stages QW consecutive pixels of one channel row (fp32: 4 = 16 bytes; fp16: 8 = 16 bytes).
   //   fp32: gy row 64 channels x 16 items, x row 64 x 20 -> 3 per thread;  fp16: 64 x 8 and 64 x 10 -> 2 per thread
@@ -297,12 +316,8 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
     }
   };
 
-  for (int item = blockIdx.x; item < items; item += a.S) {
-    const int n = item / (a.nstrips * a.nrseg);
-    const int rem = item - n * (a.nstrips * a.nrseg);
-    const int strip = rem / a.nrseg, seg = rem - strip * a.nrseg;
-    const int c0 = strip * kW3Strip, r0 = seg * a.RS;
-    const int r1 = (r0 + a.RS) < a.H ? (r0 + a.RS) : a.H;
+  DVD_WG_WALK_BEGIN(a) {
+    DVD_WG_WALK_SEGMENT(a)
     if constexpr (FW) {
       // this image's 64 channels of either tensor as buffer resources: channels past the tensor are out of range
       const int nci = (a.Cin - ci0) < kW3CB ? (a.Cin - ci0) : kW3CB, nco = (a.Cout - co0) < kW3CB ? (a.Cout - co0) : kW3CB;
@@ -363,7 +378,7 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
       const unsigned char* xr = xa + slot * (kW3CB * kW3XPitch);
       const unsigned char* gr = ga + (r & 1) * (2 * kW3CB * kW3GPitch);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {                // four K steps of 16 pixels
+      for (int s = 0; s < NK; ++s) {               // the live K steps of 16 pixels
         f16x8 A[NTERM], B[3][NTERM];
 #pragma unroll
         for (int t = 0; t < NTERM; ++t) {
@@ -389,11 +404,12 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
         DVD_W3TERM(0, 0)
 #undef DVD_W3TERM
         if constexpr (FW) {
-          // staging item s rides behind the MFMAs of K step s: store the run loaded a step ago (for step r + 1), then
+          // staging item i rides behind the MFMAs of K step i % NK: store the run loaded a step ago (for step r + 1), then
           // request the same run two rows further down (for step r + 2)
-          if (s < NQ) {
-            f_store(s, (r + 2) & 3, (r + 1) & 1);
-            f_load(s, r + 2, true);
+#pragma unroll
+          for (int i = s; i < NQ; i += NK) {
+            f_store(i, (r + 2) & 3, (r + 1) & 1);
+            f_load(i, r + 2, true);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -401,7 +417,7 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
     }
   }
   // partial[s][tap][G * Cout][Cin]
-  float* dst = a.partial + (size_t)blockIdx.x * 9 * a.G * a.Cout * a.Cin;
+  float* dst = a.partial + (size_t)(a.slice0 + blockIdx.x) * 9 * a.G * a.Cout * a.Cin;
   const float unscale = H16 ? (a.out_scale ? a.out_scale[0] : 1.0f) : 1.0f / (sx * sg);          // fp32: exact power of two
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
@@ -425,7 +441,7 @@ __global__ __launch_bounds__(kW3NT) void xwgrad3_kernel(const Wg3Args a) {
 // register selection for even s, v_alignbit for odd s (one shared chain of alignbits serves all odd offsets).
 // H16 (fp16 activation storage): the fp16 tensors themselves are the operands -- one term, no operand scale, the staging a copy,
 // ONE MFMA per product instead of three, the LDS of the second term not allocated; the result is multiplied by *out_scale.
-template <bool H16, int KS, int KX0, int KXN>
+template <bool H16, int KS, int KX0, int KXN, int NK = 4>
 __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
   constexpr int PAD = KS / 2, NS = KS + 1, CB = 32, NT = 64 * KS;
   constexpr int EB = H16 ? 2 : 4, NTERM = H16 ? 1 : 2;
@@ -438,7 +454,6 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
   const int tid = threadIdx.x, lane = tid & 63, ky = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int co0 = blockIdx.z * CB, ci0 = blockIdx.y * CB;
   const size_t plane = (size_t)a.H * a.W;
-  const int items = a.N * a.nstrips * a.nrseg;
   constexpr int GQ = CB * 16, XQ = CB * 20, NQ = (GQ + XQ + NT - 1) / NT;
   typename Quad<H16>::type stg[NQ];
   const bool wvec = (a.W & 3) == 0;
@@ -483,12 +498,8 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
   const unsigned char* ga = sG + (lane & 31) * kW3GPitch + half * 16;
   const unsigned char* xa = sX + (lane & 31) * kW3XPitch + 16 + half * 16;     // cell 1 + half of slot 0
 
-  for (int item = blockIdx.x; item < items; item += a.S) {
-    const int n = item / (a.nstrips * a.nrseg);
-    const int rem = item - n * (a.nstrips * a.nrseg);
-    const int strip = rem / a.nrseg, seg = rem - strip * a.nrseg;
-    const int c0 = strip * kW3Strip, r0 = seg * a.RS;
-    const int r1 = (r0 + a.RS) < a.H ? (r0 + a.RS) : a.H;
+  DVD_WG_WALK_BEGIN(a) {
+    DVD_WG_WALK_SEGMENT(a)
     __syncthreads();                               // the previous item's MFMAs have read their operands
     for (int j = -PAD; j < PAD; ++j) {             // x rows r0 - pad .. r0 + pad - 1 (the gy halves: zeros into the idle buffer)
       stage_load(n, c0, -1, r0 + j);
@@ -504,7 +515,7 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
       const unsigned char* xr = xa + slot_of(r - PAD + ky) * (CB * kW3XPitch);
       const unsigned char* gr = ga + (r & 1) * kGBuf;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {                // four K steps of 16 pixels
+      for (int s = 0; s < NK; ++s) {               // the live K steps of 16 pixels
         f16x8 A[NTERM];
         unsigned d[NTERM][12];                     // per term: previous cell, the lane's cell, next cell (24 pixels)
 #pragma unroll
@@ -546,7 +557,7 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
       }
     }
   }
-  float* dst = a.partial + (size_t)blockIdx.x * (KS * KS) * a.Cout * a.Cin;      // partial[s][tap][Cout][Cin]
+  float* dst = a.partial + (size_t)(a.slice0 + blockIdx.x) * (KS * KS) * a.Cout * a.Cin;      // partial[s][tap][Cout][Cin]
   const float unscale = H16 ? (a.out_scale ? a.out_scale[0] : 1.0f) : 1.0f / (sx * sg);
 #pragma unroll
   for (int kx = 0; kx < KXN; ++kx) {
@@ -570,15 +581,14 @@ __global__ __launch_bounds__(64 * KS) void xwgradk_kernel(const Wg3Args a) {
 // loads) and the elements past the row are zeroed on the way to LDS -- for fp32 by the per-element operand scale the split
 // multiplies by anyway (0 instead of 2^e), for fp16 by a mask -- so the 42- and 21-pixel rows of stages 3 and 4 take the
 // same path as the rest.
-constexpr int kWgCB = 32, kWgNT = 192;
-constexpr int kWgLdsBytes = 2 * 2 * kWgCB * kW3GPitch + 2 * kWgCB * 4 * kW3XPitch;    // 63 488
+constexpr int kWgNT = 192;
 
 // RSUM (fp32 only; host: a.rowsum_partial is set): the kernel also sums the gy rows it stages, per output channel -- the shift
 // gradient of a BatchNorm fused behind the convolution (conv._XConvBn), which otherwise takes a pass over gy of its own.  A thread
 // stages the same (at most three) gy channel rows for the whole walk, so it keeps one accumulator per gy item and adds the four
 // scaled, row-end-masked values the split consumes anyway; rows the walk stages beyond its segment (the look-ahead row r1) are
 // gated out, so every element of a (group, co block) counts exactly once over the slices.  Without RSUM the code is unchanged.
-template <bool H16, bool RSUM = false>
+template <bool H16, bool RSUM = false, int NK = 4>
 __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
   static_assert(!(H16 && RSUM), "the channel sums exist for fp32 gradients");
   constexpr int EB = H16 ? 2 : 4, NTERM = H16 ? 1 : 2, CB = kWgCB;
@@ -596,7 +606,6 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
   const int grp = blockIdx.z / a.nco;
   const int co0 = (blockIdx.z - grp * a.nco) * CB, ci0 = blockIdx.y * CB;
   const size_t plane = (size_t)a.H * a.W;
-  const int items = a.N * a.nstrips * a.nrseg;
 
   bool isg[NQ];
   int f_ch[NQ], f_pq[NQ], f_lds[NQ];
@@ -655,12 +664,8 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
   const unsigned char* ga = sG + (lane & 31) * kW3GPitch + half * 16;
   const unsigned char* xa = sX + (lane & 31) * kW3XPitch + 16 + half * 16;     // cell 1 + half of slot 0
 
-  for (int item = blockIdx.x; item < items; item += a.S) {
-    const int n = item / (a.nstrips * a.nrseg);
-    const int rem = item - n * (a.nstrips * a.nrseg);
-    const int strip = rem / a.nrseg, seg = rem - strip * a.nrseg;
-    const int c0 = strip * kW3Strip, r0 = seg * a.RS;
-    const int r1 = (r0 + a.RS) < a.H ? (r0 + a.RS) : a.H;
+  DVD_WG_WALK_BEGIN(a) {
+    DVD_WG_WALK_SEGMENT(a)
     {
       const int nci = (a.Cin - ci0) < CB ? (a.Cin - ci0) : CB, nco = (a.Cout - co0) < CB ? (a.Cout - co0) : CB;
       const unsigned char* xb = static_cast<const unsigned char*>(a.x) + (((size_t)n * a.G + grp) * a.Cin + ci0) * plane * EB;
@@ -703,7 +708,7 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
       const unsigned char* xr = xa + slot * (CB * kW3XPitch);
       const unsigned char* gr = ga + (r & 1) * (2 * CB * kW3GPitch);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {                // four K steps of 16 pixels
+      for (int s = 0; s < NK; ++s) {               // the live K steps of 16 pixels
         f16x8 A[NTERM], B[3][NTERM];
 #pragma unroll
         for (int t = 0; t < NTERM; ++t) {
@@ -728,9 +733,9 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
         }
         DVD_W3TERM(0, 0)
 #undef DVD_W3TERM
-        // the staging items i = s, s + 4 ride behind the MFMAs of K step s (for step r + 1 / r + 2, as in xwgrad3_kernel)
+        // the staging items i = s, s + NK, .. ride behind the MFMAs of K step s (for step r + 1 / r + 2, as in xwgrad3_kernel)
 #pragma unroll
-        for (int i = s; i < NQ; i += 4) {
+        for (int i = s; i < NQ; i += NK) {
           f_store(i, (r + 2) & 3, (r + 1) & 1, r + 1 < r1);      // gy row r + 1: the look-ahead past the last row is staged, not summed
           f_load(i, r + 2, true);
         }
@@ -738,7 +743,7 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
       }
     }
   }
-  float* dst = a.partial + (size_t)blockIdx.x * 9 * a.G * a.Cout * a.Cin;        // partial[s][tap][G * Cout][Cin]
+  float* dst = a.partial + (size_t)(a.slice0 + blockIdx.x) * 9 * a.G * a.Cout * a.Cin;        // partial[s][tap][G * Cout][Cin]
   const float unscale = H16 ? (a.out_scale ? a.out_scale[0] : 1.0f) : 1.0f / (sx * sg);
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
@@ -759,7 +764,7 @@ __global__ __launch_bounds__(kWgNT) void xwgrad3g_kernel(const Wg3Args a) {
 #pragma unroll
       for (int m = 1; m < GPR; m <<= 1) v += __shfl_xor(v, m, 64);
       if (isg[i] && (tid & (GPR - 1)) == 0 && blockIdx.y == 0 && f_ch[i] < a.Cout - co0)
-        a.rowsum_partial[(size_t)blockIdx.x * a.G * a.Cout + grp * a.Cout + co0 + f_ch[i]] = v * inv_sg;
+        a.rowsum_partial[(size_t)(a.slice0 + blockIdx.x) * a.G * a.Cout + grp * a.Cout + co0 + f_ch[i]] = v * inv_sg;
     }
   }
 }
@@ -1201,50 +1206,39 @@ static int wg1_wide_slices(int N, int Cin, int Cout, int HW) {
 // the wide kernel's FW form: whole 16-pixel chunks, 256 channel rows of one image inside a 31-bit buffer range
 static bool wg1_fw(int HW, bool h16) { return HW % 16 == 0 && (long long)256 * HW * (h16 ? 2 : 4) < (1ll << 31) && g_w3_variant != 1; }
 
-struct Wg3Plan {
-  int nstrips, RS, nrseg, S, nco, nci;
-  size_t lds;
-};
-static void wg3_plan(int N, int Cin, int Cout, int H, int W, int G, Wg3Plan& p) {   // Cin / Cout per group
-  p.nco = (Cout + kW3CB - 1) / kW3CB;
-  p.nci = (Cin + kW3CB - 1) / kW3CB;
-  p.nstrips = (W + kW3Strip - 1) / kW3Strip;
-  const int pairs = p.nco * p.nci * G;
-  // one block per CU is resident: a whole number of rounds over the 256 CUs, each block a few work items long
-  int S = pairs >= 256 ? 1 : (512 + pairs - 1) / pairs;
-  // rows per item: enough items to feed S slices evenly (>= 4 per slice), at least 8 rows (2 warm-up rows per item)
-  int RS = H;
-  while (RS > 8 && (long long)N * p.nstrips * ((H + RS - 1) / RS) < 4LL * S) RS = (RS + 1) / 2;
-  p.RS = RS;
-  p.nrseg = (H + RS - 1) / RS;
-  const long long items = (long long)N * p.nstrips * p.nrseg;
-  if (S > items) S = (int)items;
-  p.S = S;
-  p.lds = (size_t)kW3LdsBytes + 16;
-}
-
 // 32 x 32 channel blocks of three waves (xwgrad3g_kernel): grouped layers with at most 32 channels per group on both sides
 static bool wg3_small(int Cin, int Cout, int G) { return G > 1 && Cin <= kWgCB && Cout <= kWgCB && g_w3_variant != 1; }
 // ... rows of fp16 elements must start dword-aligned for its buffer loads (even widths), 32 channels of an image within 31 bits
 static bool wg3g_serves(int Cin, int Cout, int H, int W, int G, bool h16) {
   return wg3_small(Cin, Cout, G) && (!h16 || W % 2 == 0) && (long long)32 * H * W * (h16 ? 2 : 4) < (1ll << 31);
 }
-static void wg3g_plan(int N, int Cin, int Cout, int H, int W, int G, Wg3Plan& p) {
-  p.nco = (Cout + kWgCB - 1) / kWgCB;
-  p.nci = (Cin + kWgCB - 1) / kWgCB;
-  p.nstrips = (W + kW3Strip - 1) / kW3Strip;
-  const int pairs = p.nco * p.nci * G;
-  int S = pairs >= 512 ? 1 : (512 + pairs - 1) / pairs;        // two blocks per CU are resident
-  int RS = H;
-  while (RS > 8 && (long long)N * p.nstrips * ((H + RS - 1) / RS) < 4LL * S) RS = (RS + 1) / 2;
-  p.RS = RS;
-  p.nrseg = (H + RS - 1) / RS;
-  const long long items = (long long)N * p.nstrips * p.nrseg;
-  if (S > items) S = (int)items;
-  p.S = S;
-  p.lds = (size_t)kWgLdsBytes;
-}
 
+// the launches of a layer: one per cost class of the plan, or the one launch of the round-robin deal (dvd_xwgrad_select(3))
+static int wg_launches(const Wg3Plan& p, WgClass (&L)[2], int& slices) {
+  if (g_w3_deal) {
+    L[0] = WgClass{0, p.nstrips, 4, p.S, 0};
+    slices = p.S;
+    return 1;
+  }
+  for (int c = 0; c < p.ncls; ++c) L[c] = p.cls[c];
+  slices = p.Stot;
+  return p.ncls;
+}
+static void wg_args_class(Wg3Args& a, const Wg3Plan& p, const WgClass& c) {
+  a.nstrips = p.nstrips; a.RS = p.RS; a.nrseg = p.nrseg;
+  a.strip0 = c.strip0; a.ncols = c.ncols; a.S = c.S; a.slice0 = c.slice0;
+  a.deal = g_w3_deal ? 1 : 0;
+}
+// f(std::integral_constant<int, NK>) for the run-time K-step count nk
+template <class F>
+static int wg_with_nk(int nk, F&& f) {
+  switch (nk) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
 }  // namespace dvd
 
 extern "C" {
@@ -1253,13 +1247,14 @@ size_t dvd_xwgrad3_workspace_bytes(int N, int Cin, int Cout, int H, int W, int g
   if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cin % groups || Cout % groups) return 0;
   dvd::Wg3Plan p;
   dvd::wg3_plan(N, Cin / groups, Cout / groups, H, W, groups, p);
-  int S = p.S;
+  // the dW partials, then the row-sum partials of dvd_xwgrad3_rowsum: [S][Cout]
+  size_t n = dvd::wg_partial_floats(p, 9, Cout, Cin / groups, true);
   if (dvd::wg3_small(Cin / groups, Cout / groups, groups)) {      // (the larger of the two plans: the launch may take either)
     dvd::wg3g_plan(N, Cin / groups, Cout / groups, H, W, groups, p);
-    if (p.S > S) S = p.S;
+    const size_t ng = dvd::wg_partial_floats(p, 9, Cout, Cin / groups, true);
+    if (ng > n) n = ng;
   }
-  // the dW partials, then the row-sum partials of dvd_xwgrad3_rowsum: [S][Cout]
-  return ((size_t)S * 9 * Cout * (Cin / groups) + (size_t)S * Cout) * sizeof(float);
+  return n * sizeof(float);
 }
 
 // gy_rowsum (fp32 only, may be null): receives the per-channel sums of gy -- from the weight-gradient kernel itself where it has
@@ -1279,8 +1274,11 @@ static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, cons
   if (small) dvd::wg3g_plan(N, Cin, Cout, H, W, groups, p);
   else dvd::wg3_plan(N, Cin, Cout, H, W, groups, p);
   const bool rsum = gy_rowsum && small && !h16;                      // the kernel sums the rows it stages
-  const size_t npart = (size_t)p.S * 9 * Cout_total * Cin;
-  const size_t need = (npart + (rsum ? (size_t)p.S * Cout_total : 0)) * sizeof(float);
+  dvd::WgClass L[2];
+  int slices;
+  const int nl = dvd::wg_launches(p, L, slices);
+  const size_t npart = (size_t)slices * 9 * Cout_total * Cin;
+  const size_t need = (npart + (rsum ? (size_t)slices * Cout_total : 0)) * sizeof(float);
   if (workspace_bytes < need) {
     dvd::set_error("xwgrad3: workspace %zu < %zu bytes", workspace_bytes, need);
     return DVD_ENOSPC;
@@ -1295,27 +1293,33 @@ static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, cons
   a.rowsum_partial = rsum ? static_cast<float*>(workspace) + npart : nullptr;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.G = groups; a.nco = p.nco;
-  a.nstrips = p.nstrips; a.RS = p.RS; a.nrseg = p.nrseg; a.S = p.S;
   a.relu_in = relu_in ? 1 : 0;
   a.out_scale = out_scale;
   hipStream_t s = static_cast<hipStream_t>(stream);
   auto go = [&](auto kern) -> int {
     DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL(kern, dim3(p.S, p.nci, p.nco * groups), dim3(small ? dvd::kWgNT : dvd::kW3NT), p.lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.S, p.nci, p.nco * groups), dim3(small ? dvd::kWgNT : dvd::kW3NT), p.lds, s, a);
+    DVD_LAUNCH_OK();
     return DVD_OK;
   };
   // whole 16-byte staging items (and 64 channels of one image within a 31-bit buffer range): the branch-free row step
   const bool fw = (!h16 || W % 2 == 0) && (long long)64 * H * W * (h16 ? 2 : 4) < (1ll << 31) && dvd::g_w3_variant != 1;
-  int e;
   dvd::flops_add(small ? DVD_FLOP_XWGRAD3G : DVD_FLOP_XWGRAD3, 2.0 * 9 * N * (double)Cout_total * Cin * (double)H * W);
-  if (small) e = h16 ? go(dvd::xwgrad3g_kernel<true>) : (rsum ? go(dvd::xwgrad3g_kernel<false, true>) : go(dvd::xwgrad3g_kernel<false>));
-  else if (h16) e = fw ? go(dvd::xwgrad3_kernel<true, true>) : go(dvd::xwgrad3_kernel<true, false>);
-  else e = fw ? go(dvd::xwgrad3_kernel<false, true>) : go(dvd::xwgrad3_kernel<false, false>);
-  if (e) return e;
-  DVD_LAUNCH_OK();
+  for (int l = 0; l < nl; ++l) {
+    dvd::wg_args_class(a, p, L[l]);
+    const int e = dvd::wg_with_nk(L[l].nk, [&](auto nkc) -> int {
+      constexpr int NK = decltype(nkc)::value;
+      if (small) return h16 ? go(dvd::xwgrad3g_kernel<true, false, NK>)
+                            : (rsum ? go(dvd::xwgrad3g_kernel<false, true, NK>) : go(dvd::xwgrad3g_kernel<false, false, NK>));
+      // (the guarded row step -- fp16 rows of odd width -- keeps four K steps, the dead ones over zeros)
+      if (h16) return fw ? go(dvd::xwgrad3_kernel<true, true, NK>) : go(dvd::xwgrad3_kernel<true, false>);
+      return fw ? go(dvd::xwgrad3_kernel<false, true, NK>) : go(dvd::xwgrad3_kernel<false, false>);
+    });
+    if (e) return e;
+  }
   const long long per = (long long)9 * Cout_total * Cin;
   const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout_total + 255) / 256) : 0u;
-  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, p.S,
+  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, slices,
                      9, Cout_total, Cin, nmain, a.rowsum_partial, gy_rowsum, Cout_total);
   DVD_LAUNCH_OK();
   if (gy_rowsum && !rsum) {
@@ -1357,29 +1361,10 @@ size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) {
 }
 
 // ---- 5x5 / 7x7 / 11x11
-static bool wgk_plan(int N, int Cin, int Cout, int H, int W, int KS, bool h16, dvd::Wg3Plan& p) {
-  if (KS != 5 && KS != 7 && KS != 11) return false;
-  p.nco = (Cout + 31) / 32;
-  p.nci = (Cin + 31) / 32;
-  p.nstrips = (W + dvd::kW3Strip - 1) / dvd::kW3Strip;
-  const int pairs = p.nco * p.nci;
-  int S = pairs >= 256 ? 1 : (256 + pairs - 1) / pairs;        // one block per CU is resident
-  int RS = H;
-  while (RS > 4 * KS && (long long)N * p.nstrips * ((H + RS - 1) / RS) < 4LL * S) RS = (RS + 1) / 2;   // (KS - 1 warm-up rows per item)
-  p.RS = RS;
-  p.nrseg = (H + RS - 1) / RS;
-  const long long items = (long long)N * p.nstrips * p.nrseg;
-  if (S > items) S = (int)items;
-  p.S = S;
-  const int nterm = h16 ? 1 : 2;                               // fp16 operands: one term, half the LDS
-  p.lds = (size_t)2 * nterm * 32 * dvd::kW3GPitch + (size_t)nterm * (KS + 1) * 32 * dvd::kW3XPitch;
-  return true;
-}
-
 size_t dvd_xwgradk_workspace_bytes(int N, int Cin, int Cout, int H, int W, int KS) {
   dvd::Wg3Plan p;
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !wgk_plan(N, Cin, Cout, H, W, KS, false, p)) return 0;
-  return (size_t)p.S * KS * KS * Cout * Cin * sizeof(float);       // (the slice count does not depend on the storage)
+  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !dvd::wgk_plan(N, Cin, Cout, H, W, KS, false, p)) return 0;
+  return dvd::wg_partial_floats(p, KS * KS, Cout, Cin, false) * sizeof(float);       // (the slice count does not depend on the storage)
 }
 
 static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
@@ -1389,8 +1374,11 @@ static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, cons
   DVD_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "xwgradk: bad shape");
   DVD_REQUIRE((long long)H * W * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 31), "xwgradk: image too large for 32-bit offsets");
   dvd::Wg3Plan p;
-  DVD_REQUIRE(wgk_plan(N, Cin, Cout, H, W, KS, h16, p), "xwgradk: kernel size %d (5, 7 and 11 are covered)", KS);
-  const size_t need = (size_t)p.S * KS * KS * Cout * Cin * sizeof(float);
+  DVD_REQUIRE(dvd::wgk_plan(N, Cin, Cout, H, W, KS, h16, p), "xwgradk: kernel size %d (5, 7 and 11 are covered)", KS);
+  dvd::WgClass L[2];
+  int slices;
+  const int nl = dvd::wg_launches(p, L, slices);
+  const size_t need = (size_t)slices * KS * KS * Cout * Cin * sizeof(float);
   if (workspace_bytes < need) {
     dvd::set_error("xwgradk: workspace %zu < %zu bytes", workspace_bytes, need);
     return DVD_ENOSPC;
@@ -1405,28 +1393,31 @@ static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, cons
   a.partial = static_cast<float*>(workspace);
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.G = 1; a.nco = p.nco;
-  a.nstrips = p.nstrips; a.RS = p.RS; a.nrseg = p.nrseg; a.S = p.S;
   a.relu_in = relu_in ? 1 : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(p.S, p.nci, p.nco);
   auto go = [&](auto kern, int waves) -> int {
     DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), p.lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.S, p.nci, p.nco), dim3(64 * waves), p.lds, s, a);
     DVD_LAUNCH_OK();
     return DVD_OK;
   };
-  auto run = [&](auto h) -> int {
+  auto run = [&](auto h, auto nkc) -> int {
     constexpr bool H16 = decltype(h)::value;
-    if (KS == 5) return go(dvd::xwgradk_kernel<H16, 5, 0, 5>, 5);
-    if (KS == 7) return go(dvd::xwgradk_kernel<H16, 7, 0, 7>, 7);
-    if (int e = go(dvd::xwgradk_kernel<H16, 11, 0, 6>, 11)) return e;     // columns 0 .. 5
-    return go(dvd::xwgradk_kernel<H16, 11, 6, 5>, 11);                    // columns 6 .. 10 (disjoint taps of the same partials)
+    constexpr int NK = decltype(nkc)::value;
+    if (KS == 5) return go(dvd::xwgradk_kernel<H16, 5, 0, 5, NK>, 5);
+    if (KS == 7) return go(dvd::xwgradk_kernel<H16, 7, 0, 7, NK>, 7);
+    if (int e = go(dvd::xwgradk_kernel<H16, 11, 0, 6, NK>, 11)) return e;     // columns 0 .. 5
+    return go(dvd::xwgradk_kernel<H16, 11, 6, 5, NK>, 11);                    // columns 6 .. 10 (disjoint taps of the same partials)
   };
   dvd::flops_add(DVD_FLOP_XWGRADK, 2.0 * KS * KS * N * (double)Cout * Cin * (double)H * W);
-  if (int e = h16 ? run(std::true_type{}) : run(std::false_type{})) return e;
+  for (int l = 0; l < nl; ++l) {
+    dvd::wg_args_class(a, p, L[l]);
+    const int e = dvd::wg_with_nk(L[l].nk, [&](auto nkc) -> int { return h16 ? run(std::true_type{}, nkc) : run(std::false_type{}, nkc); });
+    if (e) return e;
+  }
   const long long per = (long long)KS * KS * Cout * Cin;
   hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, p.S, KS * KS, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
+                     static_cast<const float*>(workspace), gw, slices, KS * KS, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
   DVD_LAUNCH_OK();
   return DVD_OK;
 }
@@ -1442,9 +1433,10 @@ int dvd_xwgradk_h(const void* x, const void* gy, const float* out_scale, float* 
 }
 
 int dvd_xwgrad_select(int variant) {
-  DVD_REQUIRE(variant >= 0 && variant <= 2, "xwgrad_select: variant %d", variant);
+  DVD_REQUIRE(variant >= 0 && variant <= 3, "xwgrad_select: variant %d", variant);
   dvd::g_w1_variant = variant == 1 ? 1 : 0;
   dvd::g_w3_variant = variant == 2 ? 1 : 0;
+  dvd::g_w3_deal = variant == 3 ? 1 : 0;
   return DVD_OK;
 }
 
@@ -1514,6 +1506,7 @@ static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, con
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
     a.G = 1; a.nco = (Cout + 255) / 256;
     a.nstrips = 0; a.RS = 0; a.nrseg = 0; a.S = S;
+  a.strip0 = a.ncols = a.slice0 = a.deal = 0;
     a.relu_in = relu_in ? 1 : 0;
     a.out_scale = out_scale;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1558,6 +1551,7 @@ static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, con
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.G = 1; a.nco = nco;
   a.nstrips = 0; a.RS = 0; a.nrseg = 0; a.S = S;
+  a.strip0 = a.ncols = a.slice0 = a.deal = 0;
   a.relu_in = relu_in ? 1 : 0;
   a.out_scale = out_scale;
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -520,7 +520,9 @@ int dvd_xwgrad3_rowsum(const float* x, const float* x_amax, const float* gy, con
 int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups);
 /* Test / A-B hook (process wide): 0 = automatic (256 x 256-channel workgroups for wide 1x1 layers, 128 x 128 otherwise),
  * 1 = always 128 x 128, 2 = round 3's row step everywhere (no buffer-load / interleaved-staging instantiations of the 3x3 and
- * wide 1x1 kernels, grouped layers on the 64 x 64 channel blocks).  Same products and the same per-element summation order
+ * wide 1x1 kernels, grouped layers on the 64 x 64 channel blocks), 3 = the 3x3 / k x k walks with four K steps per row step
+ * and whole work items dealt round robin to the slices (instead of the live K steps of a strip and one launch per strip class
+ * cut into equal row counts, csrc/wg3_plan.h).  Same products and the same per-element summation order
  * within a slice; the number of slices (partial sums added at the end) differs, so results agree to fp32 rounding, not bitwise. */
 int dvd_xwgrad_select(int variant);
 /* The same for dense 5x5 / 7x7 / 11x11 stride-1 "same" convolutions (round 4: third_party/hourglass.py:21-57, the inception
