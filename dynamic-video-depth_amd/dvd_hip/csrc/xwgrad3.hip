@@ -22,6 +22,13 @@
 // between the MFMAs of K step i; taken whenever rows start dword-aligned) and the round-3 one (per-element guarded loads ahead
 // of the MFMAs; what is left for it: fp16 rows of odd width); xwgrad3g_kernel is the same walk on 32 x 32 channel blocks of
 // three waves for grouped layers with at most 32 channels per group; xwgrad1b_kernel (1x1, wide layers) has an FW form too.
+//
+// Five kernel families live here: xwgrad3_kernel (3x3, 64 x 64 channel blocks), xwgrad3g_kernel (3x3 grouped, 32 x 32),
+// xwgradk_kernel (5x5 / 7x7 / 11x11) -- the three that walk down column strips by the plan of wg3_plan.h -- and the 1x1 pair
+// xwgrad1s_kernel (128 x 128 blocks) and xwgrad1b_kernel (256 x 256, wide layers).  All write per-slice partials that
+// xwgrad3_reduce_kernel adds.  Which family and instantiation serves a shape, with which launches and how much workspace, is
+// decided in ONE place, wg_route() in the host section at the end: the size queries, dvd_xwgrad_rowsum_in_kernel and the launch
+// path of every entry point read its answer.  A new route belongs there and nowhere else.
 #include <type_traits>
 
 #include "dvd_split.h"
@@ -1193,25 +1200,22 @@ __global__ __launch_bounds__(256) void chansum_kernel(const float* __restrict__ 
   if (threadIdx.x == 0) out[c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// which 1x1 kernel: the 256 x 256 blocks when both channel counts fill them reasonably and rows are float4 aligned
-static bool wg1_wide(int Cin, int Cout, int HW) { return Cin >= 192 && Cout >= 192 && (HW & 3) == 0 && g_w1_variant != 1; }
-static int wg1_wide_slices(int N, int Cin, int Cout, int HW) {
-  const int pairs = ((Cout + 255) / 256) * ((Cin + 255) / 256);
-  int S = pairs >= 256 ? 1 : (256 + pairs - 1) / pairs;       // one workgroup per CU: a whole round over the 256 CUs
-  const long long items = (long long)N * ((HW + 15) / 16);
-  if (S > items) S = (int)items;
-  return S;
-}
+// ---- host.  wg_route decides which kernel serves a shape, with which launches and how much workspace; the size queries,
+// dvd_xwgrad_rowsum_in_kernel and the one launch path (xwgrad_impl) read its answer and decide nothing themselves.
+enum WgFamily { kWg3, kWg3g, kWgK, kWg1s, kWg1b };       // xwgrad3_ / xwgrad3g_ / xwgradk_ / xwgrad1s_ / xwgrad1b_kernel
 
-// the wide kernel's FW form: whole 16-pixel chunks, 256 channel rows of one image inside a 31-bit buffer range
-static bool wg1_fw(int HW, bool h16) { return HW % 16 == 0 && (long long)256 * HW * (h16 ? 2 : 4) < (1ll << 31) && g_w3_variant != 1; }
-
-// 32 x 32 channel blocks of three waves (xwgrad3g_kernel): grouped layers with at most 32 channels per group on both sides
-static bool wg3_small(int Cin, int Cout, int G) { return G > 1 && Cin <= kWgCB && Cout <= kWgCB && g_w3_variant != 1; }
-// ... rows of fp16 elements must start dword-aligned for its buffer loads (even widths), 32 channels of an image within 31 bits
-static bool wg3g_serves(int Cin, int Cout, int H, int W, int G, bool h16) {
-  return wg3_small(Cin, Cout, G) && (!h16 || W % 2 == 0) && (long long)32 * H * W * (h16 ? 2 : 4) < (1ll << 31);
-}
+struct WgRoute {
+  WgFamily fam;
+  bool fw;                 // xwgrad3_kernel / xwgrad1b_kernel: the FW instantiation
+  bool rsum;               // the kernel has an RSUM form for this storage: it can deliver the row sums of gy itself
+  int KS, G, Cin, Cout;    // kernel size, groups, channels per group
+  int flop_class, nthreads;
+  Wg3Plan p;               // channel blocks (grid y, z / G) and LDS bytes; the walking kernels: their plan (wg3_plan.h)
+  int nl;                  // launches ...
+  WgClass L[2];            // ... and what each walks (the 1x1 kernels: one launch, only S counts)
+  int S;                   // the partial slices the launches write in all
+  size_t floats[2];        // what a size query answers for the route: workspace floats without / with the per-slice row sums
+};
 
 // the launches of a layer: one per cost class of the plan, or the one launch of the round-robin deal (dvd_xwgrad_select(3))
 static int wg_launches(const Wg3Plan& p, WgClass (&L)[2], int& slices) {
@@ -1224,6 +1228,80 @@ static int wg_launches(const Wg3Plan& p, WgClass (&L)[2], int& slices) {
   slices = p.Stot;
   return p.ncls;
 }
+
+// Channel counts are totals over the G groups; false: no kernel for the shape (KS other than 1, 3, 5, 7, 11; groups only for 3x3).
+// force: the route under dvd_xwgrad_select(1) / (2) whatever is selected now (0: as selected).
+static bool wg_route(int KS, int N, int Cin_total, int Cout_total, int H, int W, int G, bool h16, WgRoute& r, int force = 0) {
+  if (N <= 0 || Cin_total <= 0 || Cout_total <= 0 || H <= 0 || W <= 0 || G <= 0 || Cin_total % G || Cout_total % G) return false;
+  if (G > 1 && KS != 3) return false;
+  const bool narrow1 = force == 1 || g_w1_variant == 1;     // hook value 1: always the 128 x 128 blocks
+  const bool round3 = force == 2 || g_w3_variant == 1;      // hook value 2: no FW instantiation, no 32 x 32 blocks
+  const int Cin = Cin_total / G, Cout = Cout_total / G;
+  const long long HW = (long long)H * W;
+  // a buffer resource spans `rows` channel rows of one image: they must lie within 31 bits
+  auto in_range = [&](int rows) { return rows * HW * (h16 ? 2 : 4) < (1ll << 31); };
+  r = WgRoute{};
+  r.KS = KS; r.G = G; r.Cin = Cin; r.Cout = Cout;
+  if (KS == 1) {
+    // the 256 x 256 blocks when both channel counts fill them reasonably and rows are float4 aligned
+    const bool wide = Cin >= 192 && Cout >= 192 && (HW & 3) == 0 && !narrow1;
+    r.fam = wide ? kWg1b : kWg1s;
+    r.fw = wide && HW % 16 == 0 && in_range(256) && !round3;      // whole 16-pixel chunks
+    r.rsum = r.fw && !h16;
+    const int cb = wide ? 256 : kW1CB, chunk = wide ? 16 : kW1Chunk;
+    r.p.nco = (Cout + cb - 1) / cb;
+    r.p.nci = (Cin + cb - 1) / cb;
+    r.p.lds = wide ? kWbLds : (size_t)2 * 2 * kW1CB * kW1Pitch;
+    r.nthreads = wide ? 512 : kW1NT;
+    r.flop_class = wide ? DVD_FLOP_XWGRAD1B : DVD_FLOP_XWGRAD1S;
+    // whole rounds over the resident blocks: one 256 x 256 block per CU (one round over the 256 CUs), two 128 x 128 blocks
+    // per CU (two rounds over 512 slots)
+    const int pairs = r.p.nco * r.p.nci, slots = wide ? 256 : 512, blocks = wide ? 256 : 1024;
+    const int rounds = pairs >= slots ? 1 : (blocks + pairs - 1) / pairs;
+    const long long items = (long long)N * ((HW + chunk - 1) / chunk);
+    r.S = rounds > items ? (int)items : rounds;
+    r.nl = 1;
+    r.L[0] = WgClass{0, 0, 4, r.S, 0};
+    // (the size query answers for the count before the clamp by the items, as it always has)
+    for (int i = 0; i < 2; ++i) r.floats[i] = (size_t)rounds * Cout * Cin + (i ? (size_t)rounds * Cout : 0);
+    return true;
+  }
+  if (KS == 3) {
+    // 32 x 32 channel blocks of three waves (xwgrad3g_kernel): grouped layers with at most 32 channels per group on both sides;
+    // rows of fp16 elements must start dword-aligned for its buffer loads (even widths)
+    const bool small = G > 1 && Cin <= kWgCB && Cout <= kWgCB && !round3 && (!h16 || W % 2 == 0) && in_range(32);
+    r.fam = small ? kWg3g : kWg3;
+    if (small) wg3g_plan(N, Cin, Cout, H, W, G, r.p);
+    else wg3_plan(N, Cin, Cout, H, W, G, r.p);
+    // whole 16-byte staging items: the branch-free row step
+    r.fw = !small && (!h16 || W % 2 == 0) && in_range(64) && !round3;
+    r.rsum = small && !h16;
+    r.nthreads = small ? kWgNT : kW3NT;
+    r.flop_class = small ? DVD_FLOP_XWGRAD3G : DVD_FLOP_XWGRAD3;
+  } else {
+    if (!wgk_plan(N, Cin, Cout, H, W, KS, h16, r.p)) return false;
+    r.fam = kWgK;
+    r.nthreads = 64 * KS;
+    r.flop_class = DVD_FLOP_XWGRADK;
+  }
+  r.nl = wg_launches(r.p, r.L, r.S);
+  for (int i = 0; i < 2; ++i) r.floats[i] = wg_partial_floats(r.p, KS * KS, Cout_total, Cin, i != 0);
+  return true;
+}
+
+// What a size query answers: the largest workspace over the routes a launch may take -- the query does not know the storage
+// (fp32 or fp16), and the hook may be set between the query and the launch.  0: no kernel for the shape.
+static size_t wg_query_bytes(int KS, int N, int Cin_total, int Cout_total, int H, int W, int G, bool rowsum) {
+  size_t n = 0;
+  for (int force = 0; force < 3; ++force)
+    for (int h16 = 0; h16 < 2; ++h16) {
+      WgRoute r;
+      if (!wg_route(KS, N, Cin_total, Cout_total, H, W, G, h16 != 0, r, force)) return 0;
+      if (r.floats[rowsum] > n) n = r.floats[rowsum];
+    }
+  return n * sizeof(float);
+}
+
 static void wg_args_class(Wg3Args& a, const Wg3Plan& p, const WgClass& c) {
   a.nstrips = p.nstrips; a.RS = p.RS; a.nrseg = p.nrseg;
   a.strip0 = c.strip0; a.ncols = c.ncols; a.S = c.S; a.slice0 = c.slice0;
@@ -1239,197 +1317,137 @@ static int wg_with_nk(int nk, F&& f) {
     default: return f(std::integral_constant<int, 4>{});
   }
 }
+
+typedef void (*WgKernel)(const Wg3Args);
+
+// The instantiation that runs a launch of nk live K steps of a route (rsum: the RSUM form).  11x11 runs two, kernel columns
+// 0 .. 5 and 6 .. 10: disjoint taps of the same partials.
+static void wg_kernels(const WgRoute& r, bool h16, bool rsum, int nk, WgKernel (&k)[2]) {
+  k[1] = nullptr;
+  switch (r.fam) {
+    case kWg3:
+    case kWg3g:
+      wg_with_nk(nk, [&](auto nkc) -> int {
+        constexpr int NK = decltype(nkc)::value;
+        if (r.fam == kWg3g) {
+          if (h16) k[0] = xwgrad3g_kernel<true, false, NK>;
+          else if (rsum) k[0] = xwgrad3g_kernel<false, true, NK>;
+          else k[0] = xwgrad3g_kernel<false, false, NK>;
+        } else if (h16) {        // (the guarded row step -- fp16 rows of odd width -- keeps four K steps, the dead ones over zeros)
+          if (r.fw) k[0] = xwgrad3_kernel<true, true, NK>;
+          else k[0] = xwgrad3_kernel<true, false>;
+        } else {
+          if (r.fw) k[0] = xwgrad3_kernel<false, true, NK>;
+          else k[0] = xwgrad3_kernel<false, false>;
+        }
+        return 0;
+      });
+      break;
+    case kWgK: {
+      auto pick = [&](auto h, auto nkc) -> int {
+        constexpr bool H16 = decltype(h)::value;
+        constexpr int NK = decltype(nkc)::value;
+        if (r.KS == 5) k[0] = xwgradk_kernel<H16, 5, 0, 5, NK>;
+        else if (r.KS == 7) k[0] = xwgradk_kernel<H16, 7, 0, 7, NK>;
+        else k[0] = xwgradk_kernel<H16, 11, 0, 6, NK>, k[1] = xwgradk_kernel<H16, 11, 6, 5, NK>;
+        return 0;
+      };
+      wg_with_nk(nk, [&](auto nkc) -> int { return h16 ? pick(std::true_type{}, nkc) : pick(std::false_type{}, nkc); });
+      break;
+    }
+    case kWg1b:
+      if (h16 && r.fw) k[0] = xwgrad1b_kernel<true, true>;
+      else if (h16) k[0] = xwgrad1b_kernel<true, false>;
+      else if (rsum) k[0] = xwgrad1b_kernel<false, true, true>;
+      else if (r.fw) k[0] = xwgrad1b_kernel<false, true>;
+      else k[0] = xwgrad1b_kernel<false, false>;
+      break;
+    case kWg1s:
+      if (h16) k[0] = xwgrad1s_kernel<true>;
+      else k[0] = xwgrad1s_kernel<false>;
+      break;
+  }
+}
+
+static int wg_launch(WgKernel kern, const WgRoute& r, const Wg3Args& a, hipStream_t s) {
+  DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.p.lds));
+  hipLaunchKernelGGL(kern, dim3(a.S, r.p.nci, r.p.nco * r.G), dim3(r.nthreads), r.p.lds, s, a);
+  DVD_LAUNCH_OK();
+  return DVD_OK;
+}
+
+// Every entry point: the checks, the route, its launches, the reduction over the slices.  kxk: the 5x5 / 7x7 / 11x11 entry points.
+// gy_rowsum (fp32 only, may be null): receives the per-channel sums of gy -- from the weight-gradient kernel itself where the
+// route has an RSUM form, else from chansum_kernel.
+static int xwgrad_impl(int KS, bool kxk, const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw,
+                       void* workspace, size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups,
+                       int relu_in, bool h16, const float* out_scale, float* gy_rowsum, dvd_stream_t stream) {
+  const char* name = kxk ? "xwgradk" : KS == 1 ? "xwgrad1s" : "xwgrad3";
+  DVD_REQUIRE(x && gy && gw && workspace, "%s: null pointer", name);
+  DVD_REQUIRE(h16 || (x_amax && gy_amax), kxk ? "%s: null pointer" : "%s: the operands' max|.| scalars are missing (dvd_amax)", name);
+  DVD_REQUIRE(N > 0 && Cin_total > 0 && Cout_total > 0 && H > 0 && W > 0, "%s: bad shape", name);
+  DVD_REQUIRE(groups > 0 && Cin_total % groups == 0 && Cout_total % groups == 0, "%s: %d groups do not divide the channels", name, groups);
+  DVD_REQUIRE((long long)H * W * (long long)(Cin_total > Cout_total ? Cin_total : Cout_total) < (1ll << 31),
+              "%s: image too large for 32-bit offsets", name);
+  DVD_REQUIRE(!(h16 && gy_rowsum), "%s: the channel sums exist for fp32 gradients", name);
+  WgRoute r;
+  DVD_REQUIRE((!kxk || KS > 3) && wg_route(KS, N, Cin_total, Cout_total, H, W, groups, h16, r),
+              "%s: kernel size %d (5, 7 and 11 are covered)", name, KS);
+  const bool rsum = gy_rowsum && r.rsum;                             // the kernel sums the rows it stages
+  const size_t per = (size_t)KS * KS * Cout_total * r.Cin, npart = (size_t)r.S * per;
+  const size_t need = (npart + (rsum ? (size_t)r.S * Cout_total : 0)) * sizeof(float);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
+    return DVD_ENOSPC;
+  }
+  DVD_REQUIRE((long long)r.p.nco * groups <= 65535 && r.p.nci <= 65535, "%s: too many channel blocks", name);
+  Wg3Args a;
+  a.x = x;
+  a.gy = gy;
+  a.x_amax = x_amax;
+  a.g_amax = gy_amax;
+  a.out_scale = out_scale;
+  a.partial = static_cast<float*>(workspace);
+  a.rowsum_partial = rsum ? a.partial + npart : nullptr;
+  a.N = N; a.Cin = r.Cin; a.Cout = r.Cout; a.H = H; a.W = W;
+  a.G = groups; a.nco = r.p.nco;
+  a.relu_in = relu_in ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  flops_add(r.flop_class, 2.0 * (KS * KS) * N * (double)Cout_total * r.Cin * (double)H * W);
+  for (int l = 0; l < r.nl; ++l) {
+    wg_args_class(a, r.p, r.L[l]);
+    WgKernel k[2];
+    wg_kernels(r, h16, rsum, r.L[l].nk, k);
+    for (int j = 0; j < 2 && k[j]; ++j)
+      if (int e = wg_launch(k[j], r, a, s)) return e;
+  }
+  const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout_total + 255) / 256) : 0u;
+  hipLaunchKernelGGL(xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, a.partial, gw, r.S, KS * KS, Cout_total, r.Cin, nmain,
+                     a.rowsum_partial, gy_rowsum, Cout_total);
+  DVD_LAUNCH_OK();
+  if (gy_rowsum && !rsum) {                      // no RSUM kernel on this route: one fixed-order pass over gy
+    hipLaunchKernelGGL(chansum_kernel, dim3(Cout_total), dim3(256), 0, s, static_cast<const float*>(gy), N, Cout_total, H * W, gy_rowsum);
+    DVD_LAUNCH_OK();
+  }
+  return DVD_OK;
+}
 }  // namespace dvd
 
 extern "C" {
 
+// the dW partials, then the row-sum partials of dvd_xwgrad3_rowsum / dvd_xwgrad1s_rowsum: [S][Cout]
 size_t dvd_xwgrad3_workspace_bytes(int N, int Cin, int Cout, int H, int W, int groups) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cin % groups || Cout % groups) return 0;
-  dvd::Wg3Plan p;
-  dvd::wg3_plan(N, Cin / groups, Cout / groups, H, W, groups, p);
-  // the dW partials, then the row-sum partials of dvd_xwgrad3_rowsum: [S][Cout]
-  size_t n = dvd::wg_partial_floats(p, 9, Cout, Cin / groups, true);
-  if (dvd::wg3_small(Cin / groups, Cout / groups, groups)) {      // (the larger of the two plans: the launch may take either)
-    dvd::wg3g_plan(N, Cin / groups, Cout / groups, H, W, groups, p);
-    const size_t ng = dvd::wg_partial_floats(p, 9, Cout, Cin / groups, true);
-    if (ng > n) n = ng;
-  }
-  return n * sizeof(float);
+  return dvd::wg_query_bytes(3, N, Cin, Cout, H, W, groups, true);
 }
-
-// gy_rowsum (fp32 only, may be null): receives the per-channel sums of gy -- from the weight-gradient kernel itself where it has
-// an RSUM form (the 32 x 32 grouped kernel), else from chansum_kernel
-static int xwgrad3_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
-                        size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups, int relu_in,
-                        bool h16, const float* out_scale, float* gy_rowsum, dvd_stream_t stream) {
-  DVD_REQUIRE(x && gy && gw && workspace, "xwgrad3: null pointer");
-  DVD_REQUIRE(h16 || (x_amax && gy_amax), "xwgrad3: the operands' max|.| scalars are missing (dvd_amax)");
-  DVD_REQUIRE(N > 0 && Cin_total > 0 && Cout_total > 0 && H > 0 && W > 0, "xwgrad3: bad shape");
-  DVD_REQUIRE(groups > 0 && Cin_total % groups == 0 && Cout_total % groups == 0, "xwgrad3: %d groups do not divide the channels", groups);
-  DVD_REQUIRE((long long)H * W * (long long)(Cin_total > Cout_total ? Cin_total : Cout_total) < (1ll << 31),
-              "xwgrad3: image too large for 32-bit offsets");
-  const int Cin = Cin_total / groups, Cout = Cout_total / groups;
-  dvd::Wg3Plan p;
-  const bool small = dvd::wg3g_serves(Cin, Cout, H, W, groups, h16);
-  if (small) dvd::wg3g_plan(N, Cin, Cout, H, W, groups, p);
-  else dvd::wg3_plan(N, Cin, Cout, H, W, groups, p);
-  const bool rsum = gy_rowsum && small && !h16;                      // the kernel sums the rows it stages
-  dvd::WgClass L[2];
-  int slices;
-  const int nl = dvd::wg_launches(p, L, slices);
-  const size_t npart = (size_t)slices * 9 * Cout_total * Cin;
-  const size_t need = (npart + (rsum ? (size_t)slices * Cout_total : 0)) * sizeof(float);
-  if (workspace_bytes < need) {
-    dvd::set_error("xwgrad3: workspace %zu < %zu bytes", workspace_bytes, need);
-    return DVD_ENOSPC;
-  }
-  DVD_REQUIRE((long long)p.nco * groups <= 65535 && p.nci <= 65535, "xwgrad3: too many channel blocks");
-  dvd::Wg3Args a;
-  a.x = x;
-  a.gy = gy;
-  a.x_amax = x_amax;
-  a.g_amax = gy_amax;
-  a.partial = static_cast<float*>(workspace);
-  a.rowsum_partial = rsum ? static_cast<float*>(workspace) + npart : nullptr;
-  a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.G = groups; a.nco = p.nco;
-  a.relu_in = relu_in ? 1 : 0;
-  a.out_scale = out_scale;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto go = [&](auto kern) -> int {
-    DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL(kern, dim3(a.S, p.nci, p.nco * groups), dim3(small ? dvd::kWgNT : dvd::kW3NT), p.lds, s, a);
-    DVD_LAUNCH_OK();
-    return DVD_OK;
-  };
-  // whole 16-byte staging items (and 64 channels of one image within a 31-bit buffer range): the branch-free row step
-  const bool fw = (!h16 || W % 2 == 0) && (long long)64 * H * W * (h16 ? 2 : 4) < (1ll << 31) && dvd::g_w3_variant != 1;
-  dvd::flops_add(small ? DVD_FLOP_XWGRAD3G : DVD_FLOP_XWGRAD3, 2.0 * 9 * N * (double)Cout_total * Cin * (double)H * W);
-  for (int l = 0; l < nl; ++l) {
-    dvd::wg_args_class(a, p, L[l]);
-    const int e = dvd::wg_with_nk(L[l].nk, [&](auto nkc) -> int {
-      constexpr int NK = decltype(nkc)::value;
-      if (small) return h16 ? go(dvd::xwgrad3g_kernel<true, false, NK>)
-                            : (rsum ? go(dvd::xwgrad3g_kernel<false, true, NK>) : go(dvd::xwgrad3g_kernel<false, false, NK>));
-      // (the guarded row step -- fp16 rows of odd width -- keeps four K steps, the dead ones over zeros)
-      if (h16) return fw ? go(dvd::xwgrad3_kernel<true, true, NK>) : go(dvd::xwgrad3_kernel<true, false>);
-      return fw ? go(dvd::xwgrad3_kernel<false, true, NK>) : go(dvd::xwgrad3_kernel<false, false>);
-    });
-    if (e) return e;
-  }
-  const long long per = (long long)9 * Cout_total * Cin;
-  const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout_total + 255) / 256) : 0u;
-  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, slices,
-                     9, Cout_total, Cin, nmain, a.rowsum_partial, gy_rowsum, Cout_total);
-  DVD_LAUNCH_OK();
-  if (gy_rowsum && !rsum) {
-    hipLaunchKernelGGL(dvd::chansum_kernel, dim3(Cout_total), dim3(256), 0, s, static_cast<const float*>(gy), N, Cout_total, H * W,
-                       gy_rowsum);
-    DVD_LAUNCH_OK();
-  }
-  return DVD_OK;
-}
-
-int dvd_xwgrad3(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
-                size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups, int relu_in,
-                dvd_stream_t stream) {
-  return xwgrad3_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, false,
-                      nullptr, nullptr, stream);
-}
-
-int dvd_xwgrad3_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
-                       void* workspace, size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups,
-                       int relu_in, dvd_stream_t stream) {
-  return xwgrad3_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, false,
-                      nullptr, gy_rowsum, stream);
-}
-
-int dvd_xwgrad3_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
-                  int Cin_total, int Cout_total, int H, int W, int groups, int relu_in, dvd_stream_t stream) {
-  return xwgrad3_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups, relu_in, true,
-                      out_scale, nullptr, stream);
-}
-
-size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
-  const int pairs = ((Cout + dvd::kW1CB - 1) / dvd::kW1CB) * ((Cin + dvd::kW1CB - 1) / dvd::kW1CB);
-  int S = pairs >= 512 ? 1 : (1024 + pairs - 1) / pairs;
-  const int Sw = dvd::wg1_wide_slices(N, Cin, Cout, H * W);      // (either kernel may serve the call)
-  if (Sw > S) S = Sw;
-  // the dW partials, then the row-sum partials of dvd_xwgrad1s_rowsum: [S][Cout]
-  return ((size_t)S * Cout * Cin + (size_t)S * Cout) * sizeof(float);
-}
-
-// ---- 5x5 / 7x7 / 11x11
+size_t dvd_xwgrad1s_workspace_bytes(int N, int Cin, int Cout, int H, int W) { return dvd::wg_query_bytes(1, N, Cin, Cout, H, W, 1, true); }
+// 5x5 / 7x7 / 11x11
 size_t dvd_xwgradk_workspace_bytes(int N, int Cin, int Cout, int H, int W, int KS) {
-  dvd::Wg3Plan p;
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !dvd::wgk_plan(N, Cin, Cout, H, W, KS, false, p)) return 0;
-  return dvd::wg_partial_floats(p, KS * KS, Cout, Cin, false) * sizeof(float);       // (the slice count does not depend on the storage)
+  return KS > 3 ? dvd::wg_query_bytes(KS, N, Cin, Cout, H, W, 1, false) : 0;
 }
 
-static int xwgradk_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
-                        size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, bool h16,
-                        const float* out_scale, dvd_stream_t stream) {
-  DVD_REQUIRE(x && gy && gw && workspace && (h16 || (x_amax && gy_amax)), "xwgradk: null pointer");
-  DVD_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "xwgradk: bad shape");
-  DVD_REQUIRE((long long)H * W * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 31), "xwgradk: image too large for 32-bit offsets");
-  dvd::Wg3Plan p;
-  DVD_REQUIRE(dvd::wgk_plan(N, Cin, Cout, H, W, KS, h16, p), "xwgradk: kernel size %d (5, 7 and 11 are covered)", KS);
-  dvd::WgClass L[2];
-  int slices;
-  const int nl = dvd::wg_launches(p, L, slices);
-  const size_t need = (size_t)slices * KS * KS * Cout * Cin * sizeof(float);
-  if (workspace_bytes < need) {
-    dvd::set_error("xwgradk: workspace %zu < %zu bytes", workspace_bytes, need);
-    return DVD_ENOSPC;
-  }
-  DVD_REQUIRE(p.nco <= 65535 && p.nci <= 65535, "xwgradk: too many channel blocks");
-  dvd::Wg3Args a;
-  a.x = x;
-  a.gy = gy;
-  a.x_amax = x_amax;
-  a.g_amax = gy_amax;
-  a.out_scale = out_scale;
-  a.partial = static_cast<float*>(workspace);
-  a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.G = 1; a.nco = p.nco;
-  a.relu_in = relu_in ? 1 : 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  auto go = [&](auto kern, int waves) -> int {
-    DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL(kern, dim3(a.S, p.nci, p.nco), dim3(64 * waves), p.lds, s, a);
-    DVD_LAUNCH_OK();
-    return DVD_OK;
-  };
-  auto run = [&](auto h, auto nkc) -> int {
-    constexpr bool H16 = decltype(h)::value;
-    constexpr int NK = decltype(nkc)::value;
-    if (KS == 5) return go(dvd::xwgradk_kernel<H16, 5, 0, 5, NK>, 5);
-    if (KS == 7) return go(dvd::xwgradk_kernel<H16, 7, 0, 7, NK>, 7);
-    if (int e = go(dvd::xwgradk_kernel<H16, 11, 0, 6, NK>, 11)) return e;     // columns 0 .. 5
-    return go(dvd::xwgradk_kernel<H16, 11, 6, 5, NK>, 11);                    // columns 6 .. 10 (disjoint taps of the same partials)
-  };
-  dvd::flops_add(DVD_FLOP_XWGRADK, 2.0 * KS * KS * N * (double)Cout * Cin * (double)H * W);
-  for (int l = 0; l < nl; ++l) {
-    dvd::wg_args_class(a, p, L[l]);
-    const int e = dvd::wg_with_nk(L[l].nk, [&](auto nkc) -> int { return h16 ? run(std::true_type{}, nkc) : run(std::false_type{}, nkc); });
-    if (e) return e;
-  }
-  const long long per = (long long)KS * KS * Cout * Cin;
-  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, slices, KS * KS, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
-  DVD_LAUNCH_OK();
-  return DVD_OK;
-}
-
-int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
-                size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
-  return xwgradk_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, KS, relu_in, false, nullptr, stream);
-}
-
-int dvd_xwgradk_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
-                  int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
-  return xwgradk_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, KS, relu_in, true, out_scale, stream);
+int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups) {
+  dvd::WgRoute r;
+  return (KS == 1 || KS == 3) && dvd::wg_route(KS, N, Cin, Cout, H, W, groups, false, r) && r.rsum ? 1 : 0;
 }
 
 int dvd_xwgrad_select(int variant) {
@@ -1440,138 +1458,56 @@ int dvd_xwgrad_select(int variant) {
   return DVD_OK;
 }
 
-static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
-                         size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, bool h16,
-                         const float* out_scale, float* gy_rowsum, dvd_stream_t stream);
-
-int dvd_xwgrad1s_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
-                        void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in,
-                        dvd_stream_t stream) {
-  return xwgrad1s_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, false, nullptr, gy_rowsum,
-                       stream);
+int dvd_xwgrad3(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
+                size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups, int relu_in,
+                dvd_stream_t stream) {
+  return dvd::xwgrad_impl(3, false, x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups,
+                          relu_in, false, nullptr, nullptr, stream);
 }
 
-int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups) {
-  if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cin % groups || Cout % groups) return 0;
-  if (KS == 1 && groups == 1) return dvd::wg1_wide(Cin, Cout, H * W) && dvd::wg1_fw(H * W, false) ? 1 : 0;
-  if (KS == 3) return dvd::wg3g_serves(Cin / groups, Cout / groups, H, W, groups, false) ? 1 : 0;
-  return 0;
+int dvd_xwgrad3_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
+                       void* workspace, size_t workspace_bytes, int N, int Cin_total, int Cout_total, int H, int W, int groups,
+                       int relu_in, dvd_stream_t stream) {
+  return dvd::xwgrad_impl(3, false, x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups,
+                          relu_in, false, nullptr, gy_rowsum, stream);
+}
+
+int dvd_xwgrad3_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
+                  int Cin_total, int Cout_total, int H, int W, int groups, int relu_in, dvd_stream_t stream) {
+  return dvd::xwgrad_impl(3, false, x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin_total, Cout_total, H, W, groups,
+                          relu_in, true, out_scale, nullptr, stream);
+}
+
+int dvd_xwgradk(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
+                size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
+  return dvd::xwgrad_impl(KS, true, x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, 1, relu_in, false,
+                          nullptr, nullptr, stream);
+}
+
+int dvd_xwgradk_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
+                  int Cin, int Cout, int H, int W, int KS, int relu_in, dvd_stream_t stream) {
+  return dvd::xwgrad_impl(KS, true, x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, 1, relu_in, true,
+                          out_scale, nullptr, stream);
 }
 
 int dvd_xwgrad1s(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, void* workspace,
                  size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream) {
-  return xwgrad1s_impl(x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, false, nullptr, nullptr,
-                       stream);
+  return dvd::xwgrad_impl(1, false, x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, 1, relu_in, false,
+                          nullptr, nullptr, stream);
+}
+
+int dvd_xwgrad1s_rowsum(const float* x, const float* x_amax, const float* gy, const float* gy_amax, float* gw, float* gy_rowsum,
+                        void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in,
+                        dvd_stream_t stream) {
+  return dvd::xwgrad_impl(1, false, x, x_amax, gy, gy_amax, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, 1, relu_in, false,
+                          nullptr, gy_rowsum, stream);
 }
 
 int dvd_xwgrad1s_h(const void* x, const void* gy, const float* out_scale, float* gw, void* workspace, size_t workspace_bytes, int N,
                    int Cin, int Cout, int H, int W, int relu_in, dvd_stream_t stream) {
-  return xwgrad1s_impl(x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, relu_in, true, out_scale, nullptr,
-                       stream);
-}
-
-// gy_rowsum (fp32 only, may be null): the per-channel sums of gy -- from the wide FW kernel's RSUM form, else from chansum_kernel
-static int xwgrad1s_impl(const void* x, const float* x_amax, const void* gy, const float* gy_amax, float* gw, void* workspace,
-                         size_t workspace_bytes, int N, int Cin, int Cout, int H, int W, int relu_in, bool h16,
-                         const float* out_scale, float* gy_rowsum, dvd_stream_t stream) {
-  DVD_REQUIRE(x && gy && gw && workspace, "xwgrad1s: null pointer");
-  DVD_REQUIRE(h16 || (x_amax && gy_amax), "xwgrad1s: the operands' max|.| scalars are missing (dvd_amax)");
-  DVD_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "xwgrad1s: bad shape");
-  DVD_REQUIRE((long long)H * W * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 31), "xwgrad1s: image too large for 32-bit offsets");
-  DVD_REQUIRE(!(h16 && gy_rowsum), "xwgrad1s: the channel sums exist for fp32 gradients");
-  auto chansum = [&]() -> int {                  // the routes without an RSUM kernel: one fixed-order pass over gy
-    if (!gy_rowsum) return DVD_OK;
-    hipLaunchKernelGGL(dvd::chansum_kernel, dim3(Cout), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(gy),
-                       N, Cout, H * W, gy_rowsum);
-    DVD_LAUNCH_OK();
-    return DVD_OK;
-  };
-  if (dvd::wg1_wide(Cin, Cout, H * W)) {
-    const int S = dvd::wg1_wide_slices(N, Cin, Cout, H * W);
-    const bool fw = dvd::wg1_fw(H * W, h16);
-    const bool rsum = gy_rowsum && fw && !h16;   // the kernel sums the rows it stages
-    const size_t npart = (size_t)S * Cout * Cin;
-    const size_t need = (npart + (rsum ? (size_t)S * Cout : 0)) * sizeof(float);
-    if (workspace_bytes < need) {
-      dvd::set_error("xwgrad1s: workspace %zu < %zu bytes", workspace_bytes, need);
-      return DVD_ENOSPC;
-    }
-    dvd::Wg3Args a;
-    a.x = x;
-    a.gy = gy;
-    a.x_amax = x_amax;
-    a.g_amax = gy_amax;
-    a.partial = static_cast<float*>(workspace);
-    a.rowsum_partial = rsum ? static_cast<float*>(workspace) + npart : nullptr;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.G = 1; a.nco = (Cout + 255) / 256;
-    a.nstrips = 0; a.RS = 0; a.nrseg = 0; a.S = S;
-  a.strip0 = a.ncols = a.slice0 = a.deal = 0;
-    a.relu_in = relu_in ? 1 : 0;
-    a.out_scale = out_scale;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid(S, (Cin + 255) / 256, (Cout + 255) / 256);
-    auto go = [&](auto kern) -> int {
-      DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dvd::kWbLds));
-      hipLaunchKernelGGL(kern, grid, dim3(512), dvd::kWbLds, s, a);
-      return DVD_OK;
-    };
-    dvd::flops_add(DVD_FLOP_XWGRAD1B, 2.0 * N * (double)Cout * Cin * (double)H * W);
-    int e;
-    if (h16) e = fw ? go(dvd::xwgrad1b_kernel<true, true>) : go(dvd::xwgrad1b_kernel<true, false>);
-    else if (rsum) e = go(dvd::xwgrad1b_kernel<false, true, true>);
-    else e = fw ? go(dvd::xwgrad1b_kernel<false, true>) : go(dvd::xwgrad1b_kernel<false, false>);
-    if (e) return e;
-    DVD_LAUNCH_OK();
-    const long long per = (long long)Cout * Cin;
-    const unsigned nmain = (unsigned)((per + 255) / 256), nrs = rsum ? (unsigned)((Cout + 255) / 256) : 0u;
-    hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, static_cast<const float*>(workspace), gw, S, 1,
-                       Cout, Cin, nmain, a.rowsum_partial, gy_rowsum, Cout);
-    DVD_LAUNCH_OK();
-    return rsum ? DVD_OK : chansum();
-  }
-  const int nco = (Cout + dvd::kW1CB - 1) / dvd::kW1CB, nci = (Cin + dvd::kW1CB - 1) / dvd::kW1CB;
-  const int pairs = nco * nci;
-  // two blocks per CU are resident: whole rounds over 512 slots
-  int S = pairs >= 512 ? 1 : (1024 + pairs - 1) / pairs;
-  const long long items = (long long)N * ((H * W + dvd::kW1Chunk - 1) / dvd::kW1Chunk);
-  if (S > items) S = (int)items;
-  const size_t need = (size_t)S * Cout * Cin * sizeof(float);
-  if (workspace_bytes < need) {
-    dvd::set_error("xwgrad1s: workspace %zu < %zu bytes", workspace_bytes, need);
-    return DVD_ENOSPC;
-  }
-  DVD_REQUIRE(nco <= 65535 && nci <= 65535, "xwgrad1s: too many channel blocks");
-  dvd::Wg3Args a;
-  a.x = x;
-  a.gy = gy;
-  a.x_amax = x_amax;
-  a.g_amax = gy_amax;
-  a.partial = static_cast<float*>(workspace);
-  a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.G = 1; a.nco = nco;
-  a.nstrips = 0; a.RS = 0; a.nrseg = 0; a.S = S;
-  a.strip0 = a.ncols = a.slice0 = a.deal = 0;
-  a.relu_in = relu_in ? 1 : 0;
-  a.out_scale = out_scale;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t lds = (size_t)2 * 2 * dvd::kW1CB * dvd::kW1Pitch;
-  dvd::flops_add(DVD_FLOP_XWGRAD1S, 2.0 * N * (double)Cout * Cin * (double)H * W);
-  if (h16) {
-    DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(dvd::xwgrad1s_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(dvd::xwgrad1s_kernel<true>, dim3(S, nci, nco), dim3(dvd::kW1NT), lds, s, a);
-  } else {
-    DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(dvd::xwgrad1s_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(dvd::xwgrad1s_kernel<false>, dim3(S, nci, nco), dim3(dvd::kW1NT), lds, s, a);
-  }
-  DVD_LAUNCH_OK();
-  const long long per = (long long)Cout * Cin;
-  hipLaunchKernelGGL(dvd::xwgrad3_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const float*>(workspace), gw, S, 1, Cout, Cin, (unsigned)((per + 255) / 256), nullptr, nullptr, 0);
-  DVD_LAUNCH_OK();
-  return chansum();
+  return dvd::xwgrad_impl(1, false, x, nullptr, gy, nullptr, gw, workspace, workspace_bytes, N, Cin, Cout, H, W, 1, relu_in, true,
+                          out_scale, nullptr, stream);
 }
 
 }  // extern "C"
+

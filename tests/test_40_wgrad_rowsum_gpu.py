@@ -36,7 +36,7 @@ def _chain_chansum(N, HW):
 
 
 def _chain_1x1(N, Cin, Cout, HW):
-    """-> (L, route).  The wide FW kernel (csrc/xwgrad3.hip wg1_wide, wg1_wide_slices): a slice is n_it consecutive 16-pixel
+    """-> (L, route).  The wide FW kernel (csrc/xwgrad3.hip wg_route, KS = 1): a slice is n_it consecutive 16-pixel
     chunks; a lane adds, per chunk it stores (two in the prologue, two per pair of the loop), the quad's tree (2 adds), the fold
     across lanes (1) and BOTH gy items into its accumulator (its own row's, and a zero for the other row); then one add across
     lanes and the rounding of the double sum over the slices."""
@@ -51,7 +51,7 @@ def _chain_1x1(N, Cin, Cout, HW):
 
 
 def _chain_3x3(N, Cin, Cout, H, W, G):
-    """-> (L, route).  The 32 x 32 grouped kernel (wg3_small, wg3g_plan): a slice walks ceil(items / S) work items of at most RS
+    """-> (L, route).  The 32 x 32 grouped kernel (wg_route, wg3g_plan): a slice walks ceil(items / S) work items of at most RS
     rows; per item a thread's accumulator takes three prologue stores and one store per row (4 values: 2 adds, then 1), then the
     butterfly over the 16 lanes of a row (4) and the rounding of the double sum over the slices."""
     if not (G > 1 and Cin // G <= 32 and Cout // G <= 32):
