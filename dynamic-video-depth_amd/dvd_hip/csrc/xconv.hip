@@ -27,15 +27,25 @@
 //     convolution, the kernel ran at the L1 rate, not the MFMA rate).
 //   * activations: a block owns a TR x TC tile of one image and all input channels in chunks of 16.  The
 //     chunk's haloed tile is read from HBM as fp32 (coalesced along x), split, and written to LDS as
-//     [term][channel group of 8][position][8 fp16]; positions are linear in the PADDED tile,
-//     q = r * (TC + 2 pad) + c, so the B fragment of tap (ky, kx) is the fragment of the centre tap at a
-//     constant LDS offset ky * P + kx -- 32 consecutive 16-byte cells, conflict free -- and an N tile of 32
-//     consecutive q may straddle rows (the 2 pad columns per row are computed and dropped).  The raw fp32
+//     [term][channel group of 8][cell][8 fp16]; cells are linear in the PADDED tile of pitch P = TC + 2 pad.
+//     GEMM column ("position") q is the OUTPUT (q / TC, q % TC) of the tile and reads the cell (q / TC) * P + q % TC
+//     (csrc/xconv_tile.h: only real outputs are computed, TR * TC <= positions of the block), so the B fragment of
+//     tap (ky, kx) is the fragment of the centre tap at a constant LDS offset ky * P + kx, and an N tile of 32
+//     consecutive q may straddle tile rows.  Within a tile row 32 consecutive positions are 32 consecutive 16-byte
+//     cells: ds_read_b128 serves a wave as 4 groups of 16 lanes over 64 banks of 4 bytes, 16 consecutive cells are the
+//     64 banks once, conflict free.  Where a run of 32 lanes crosses a tile-row end the cells behind the seam sit 2 pad
+//     further on: inside a lane group, cells before and behind the seam are each distinct modulo 16, so a bank is
+//     asked for at most two addresses (with several seams in a run, TC < 32: one more per seam) -- a 2-way conflict,
+//     one extra LDS cycle for each of the read's 4 groups at worst (8 instead of 4 cycles for that read).  A K step of
+//     the 512-thread shape issues 8 waves x 12 reads = 384 LDS cycles against ~1 500 matrix-pipe cycles per SIMD, the
+//     seams add at most 8 x 4 x 4 = 128.  (Rounds 2-6 made the position the cell itself, q = r * P + c: no seam, but
+//     the 2 pad halo columns of every tile row were computed and dropped; kept as dvd_xconv_select(8).)  The raw fp32
 //     values of the next chunk are requested before the MFMAs of the current one.
 //   * epilogue: + bias[co], + residual (optionally relu'd), * [mask_src > 0], ReLU; coalesced stores.
 #include <type_traits>
 
 #include "dvd_split.h"
+#include "xconv_tile.h"
 
 namespace dvd {
 
@@ -266,6 +276,7 @@ struct XArgs {
   int G, mbpg, mtiles;      // groups, channel blocks per group, packed 32-row tiles per group
   int KS, pad, T;
   int TR, TC, P, ntr, ntc, NV;
+  int PQ;                 // positions per tile row: TC (dense positions) or P (haloed positions), csrc/xconv_tile.h
   int nkc, npos, nfi;     // nfi: B staging items per thread (FI == 0 kernels loop over them at run time)
   int relu_in, relu_out, res_relu;
   int vec_out;            // 1x1 kernels: positions are pixels in runs of 8 and every pointer is 16-byte aligned (wide epilogue)
@@ -355,9 +366,7 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
     lp = p;
   };
   // LDS offset of tap (ky, kx) relative to the centre-less origin of the tile
-  auto tapoff = [&](int ky, int kx) {
-    return a.S2 ? ((ky & 1) * 2 + (kx & 1)) * a.S2 + (ky >> 1) * P + (kx >> 1) : ky * P + kx;
-  };
+  auto tapoff = [&](int ky, int kx) { return xconv_tapoff(ky, kx, P, a.S2); };
   int goff[FI], lidx[FI], cig8[FI];
   bool gok[FI];
 #pragma unroll
@@ -599,9 +608,44 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = (f32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-  int qb[TN];
+  // position q of the block (the epilogue's output) and the LDS cell its fragment reads come from (xconv_tile.h).  The 1x1
+  // kernels stage one row without a halo: the cell is the position.
+  auto qpos = [&](int tn) { return (wn * TN + tn) * 32 + (lane & 31); };
+  // The cells of a lane's TN positions are no longer 32 apart (one register + immediate offsets).  The wide wave tiles sit at
+  // the 256-VGPR limit: they keep the cells as 16-bit pairs in one register (a stage has < 2^16 cells) and unpack them where
+  // the fragments are read -- behind an empty asm, or the compiler unpacks once in front of the loop and the forced 256 x 128
+  // shape with three staging items spills.  The narrow tiles keep one register per cell (packed, the 32-channel shape with
+  // two staging items needs 98 instead of 96 VGPRs and loses its fifth wave per SIMD).
+  constexpr bool kPackCells = TM >= 4 && !kOne;
+  constexpr int QP = kPackCells ? (TN + 1) / 2 : TN;
+  int qbp[QP];
 #pragma unroll
-  for (int tn = 0; tn < TN; ++tn) qb[tn] = (wn * TN + tn) * 32 + (lane & 31);
+  for (int h = 0; h < QP; ++h) {
+    if constexpr (kPackCells) {
+      const int c0 = xconv_cell(qpos(2 * h), a.PQ, P, a.TR);
+      const int c1 = 2 * h + 1 >= TN ? 0 : xconv_cell(qpos(2 * h + 1), a.PQ, P, a.TR);
+      qbp[h] = c0 | (c1 << 16);
+    } else {
+      qbp[h] = kOne ? 0 : xconv_cell(qpos(h), a.PQ, P, a.TR);
+    }
+  }
+  auto cells = [&](int (&qb)[TN]) {
+    if constexpr (kOne) {
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) qb[tn] = qpos(tn);
+    } else if constexpr (!kPackCells) {
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) qb[tn] = qbp[tn];
+    } else {
+#pragma unroll
+      for (int h = 0; h < QP; ++h) {
+        int pk = qbp[h];
+        asm volatile("" : "+v"(pk));
+        qb[2 * h] = pk & 0xffff;
+        if (2 * h + 1 < TN) qb[2 * h + 1] = (int)((unsigned)pk >> 16);
+      }
+    }
+  };
   const int bl = (lane >> 5) * npos;
   const int al = (wm * TM) * 128 + lane;
 
@@ -616,6 +660,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
   auto read_frags = [&](Frag& f, int abuf, int kc, int off) {
     const u32x4* Ac = sA + abuf * AS + al;
     const u32x4* Bc = sB + (B1 ? 0 : (kc & 1) * 2 * BT * npos) + bl + off;
+    int qb[TN];
+    cells(qb);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -673,6 +719,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
     {
       const u32x4* Ac = sA + al;
       const u32x4* Bc = sB + bl;
+      int qb[TN];
+      cells(qb);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -699,6 +747,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
       load_a(ra, kt + 2 < nkt ? kt + 2 : kt);
       const u32x4* Ac = sA + ((kt + 1) & 1) * AS + al;
       const u32x4* Bc = sB + (nc & 1) * 2 * BT * npos + bl + tapoff(ny, nx);      // (past the last step: in range, never used)
+      int qb[TN];
+      cells(qb);
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -750,6 +800,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
       load_raw_to(ro, kt + 3 < a.nkc ? kt + 3 : a.nkc - 1);
       const u32x4* Ac = sA + ((kt + 1) & 1) * AS + al;
       const u32x4* Bc = sB + ((kt + 1) & 1) * 2 * BT * npos + bl;
+      int qb[TN];
+      cells(qb);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
@@ -990,8 +1042,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
   }
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
-    const int q = qb[tn];
-    const int rr = q / P, cc = q - rr * P;
+    const int q = qpos(tn);
+    const int rr = q / a.PQ, cc = q - rr * a.PQ;
     const bool pok = rr < TRv && cc < TCv;
     const int pix = pok ? (r0 + rr) * a.W + (c0 + cc) : 0;
 #pragma unroll
@@ -1057,118 +1109,8 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-struct XCfg {
-  int TM, TN, WM, WN;
-  bool b1 = false;        // single activation stage, three blocks per CU
-  bool in16 = false;      // fp16 activations: one split term in LDS
-  int blockM() const { return TM * WM * 32; }
-  int NQ() const { return TN * WN * 32; }
-  int NT() const { return 64 * WM * WN; }
-};
-// Block shapes.  Every activation element a block stages is split into its two fp16 terms ONCE per block (VALU work) and
-// read from LDS once per 32-channel tile row, so the split / LDS cost per MFMA falls with the number of output channels a
-// block owns: with >= 256 of them a block takes 256 channels (wave tile 128 channels x 64 positions: 48 MFMAs against 18
-// fragment reads per K step, round 2: 24 against 12) -- 256 x 128 positions at two blocks per CU for 1x1 kernels, 256 x 256
-// positions in ONE 512-thread block per CU for k >= 3 (the haloed tile of 256 positions needs ~120 KB of LDS).
-static int g_xcfg = 0;    // test / A-B hook (dvd_xconv_select): 0 auto, 1 round-2 shapes only, 2 force 256x128, 3 force 256x256,
-                          // 4 round-2 shapes on the generic (pointer-addressed) main loop, 5 128 x 128 blocks with one
-                          // activation stage at three blocks per CU, 6 1x1 kernels without the two-chunk loop (kOne), 7 kOne with the narrow epilogue
-static XCfg pick_cfg(int M, int KS) {
-  if (M <= 32) return {1, 2, 1, 4};     // 32 channels x 256 positions
-  if (M <= 64) return {2, 2, 1, 4};     // 64 x 256
-  if (M > 64 && g_xcfg == 5) return {2, 2, 2, 2, true};
-  if (M >= 256 && g_xcfg != 1 && g_xcfg != 4) {
-    if (g_xcfg == 2) return {4, 2, 2, 2};
-    if (g_xcfg == 3) return {4, 2, 2, 4};
-    return KS == 1 ? XCfg{4, 2, 2, 2} : XCfg{4, 2, 2, 4};
-  }
-  return {2, 2, 2, 2};                  // 128 x 128
-}
-constexpr int kXLdsBudget = 78 * 1024;    // two blocks per CU
-constexpr int kXMaxFI = 3;       // register-prefetched staging; larger halos use the direct-staging kernels
-constexpr int kXMaxFIDirect = 16;
-
-struct XTile {
-  int TR, TC, P, ntr, ntc, NV, npos, FI;
-  size_t lds;
-};
-static size_t xconv_lds(const XCfg& c, int npos) {
-  const int AU = c.WM * c.TM * 128, NT = c.NT();
-  const int AS = (AU + NT - 1) / NT * NT;
-  return ((size_t)2 * AS + (size_t)(c.b1 ? 4 : 8) * npos / (c.in16 ? 2 : 1)) * sizeof(uint4);
-}
-// Tile of the image per block: TR x TC outputs, TR * (TC + 2 pad) <= NQ positions; choose the split of the
-// width that wastes the fewest positions, subject to the LDS budget and the staging-iteration bound.
-static bool pick_tile_budget(int H, int W, int KS, const XCfg& c, XTile& best, int budget) {
-  const int pad = KS / 2, NQ = c.NQ(), NT = c.NT();
-  double best_eff = -1.0;
-  for (int nct = 1; nct <= W; ++nct) {
-    int TC = (W + nct - 1) / nct;
-    if (KS == 1) TC = (TC + 7) & ~7;                     // whole 16-byte runs per lane in the wide epilogue of the 1x1 kernels
-    const int P = TC + 2 * pad;
-    if (P > NQ) continue;
-    const int ntc = (W + TC - 1) / TC;
-    const int npos = NQ + (KS - 1) * (P + 1) + 1;        // + the spare cell of the staging code
-    if (xconv_lds(c, npos) > (size_t)budget) continue;
-    int trmax = NQ / P;
-    if (trmax > H) trmax = H;
-    for (int tr0 = trmax; tr0 >= 1; --tr0) {
-      const int ntr = (H + tr0 - 1) / tr0;
-      const int TR = (H + ntr - 1) / ntr;               // even out the rows
-      const int NV = (TR + 2 * pad) * P;
-      const int FI = (2 * NV + NT - 1) / NT;
-      if (FI > kXMaxFIDirect) continue;
-      // useful positions per computed position, minus what the halo costs in staging work
-      const double eff = (double)H * W / ((double)ntr * ntc * NQ) - 0.02 * (double)NV / (TR * TC) - 1e-6 * nct;
-      if (eff > best_eff) {
-        best_eff = eff;
-        best = {TR, TC, P, ntr, ntc, NV, npos, FI, xconv_lds(c, npos)};
-      }
-      break;                                             // smaller TR only lowers the efficiency
-    }
-    if (TC <= 8) break;
-  }
-  return best_eff > -1.0;
-}
-
-static bool pick_tile(int H, int W, int KS, const XCfg& c, XTile& best) {
-  // two blocks per CU where the haloed tile allows it, one block (big kernels: k >= 7; the 512-thread shape) otherwise
-  if (c.NT() >= 512) return pick_tile_budget(H, W, KS, c, best, 156 * 1024);
-  if (c.b1) return pick_tile_budget(H, W, KS, c, best, 52 * 1024);        // three blocks per CU, or not this shape
-  return pick_tile_budget(H, W, KS, c, best, kXLdsBudget) || pick_tile_budget(H, W, KS, c, best, 156 * 1024);
-}
-
-// Stride-2 forward (XArgs::S2): TR x TC OUTPUTS per block in a pitch of P = TC + 1, four phase planes of (TR + 1) * P cells.
-static bool pick_tile_s2_budget(int Ho, int Wo, const XCfg& c, XTile& best, int& S2, int budget) {
-  const int NQ = c.NQ(), NT = c.NT();
-  double best_eff = -1.0;
-  for (int nct = 1; nct <= Wo; ++nct) {
-    const int TC = (Wo + nct - 1) / nct, P = TC + 1;
-    if (P > NQ) continue;
-    const int ntc = (Wo + TC - 1) / TC;
-    int trmax = NQ / P;
-    if (trmax > Ho) trmax = Ho;
-    const int ntr = (Ho + trmax - 1) / trmax;
-    const int TR = (Ho + ntr - 1) / ntr;
-    const int s2 = (TR + 1) * P;
-    const int npos = 3 * s2 + NQ + 1;                     // + the spare cell of the staging code
-    const int NV = (2 * TR + 1) * (2 * TC + 1);
-    const int FI = (2 * NV + NT - 1) / NT;
-    if (xconv_lds(c, npos) <= (size_t)budget && FI <= 4 * kXMaxFIDirect) {
-      const double eff = (double)Ho * Wo / ((double)ntr * ntc * NQ) - 1e-6 * nct;
-      if (eff > best_eff) {
-        best_eff = eff;
-        best = {TR, TC, P, ntr, ntc, NV, npos, FI, xconv_lds(c, npos)};
-        S2 = s2;
-      }
-    }
-    if (TC <= 4) break;
-  }
-  return best_eff > -1.0;
-}
-static bool pick_tile_s2(int Ho, int Wo, const XCfg& c, XTile& best, int& S2) {
-  return pick_tile_s2_budget(Ho, Wo, c, best, S2, kXLdsBudget) || pick_tile_s2_budget(Ho, Wo, c, best, S2, 156 * 1024);
-}
+// Block shapes, tiles and the launch plan: csrc/xconv_tile.h
+static int g_xcfg = 0;    // test / A-B hook (dvd_xconv_select), see pick_cfg
 
 template <int TM, int TN, int WM, int WN, bool FAST, bool B1 = false, bool IN16 = false, bool OUT16 = false>
 static int launch_fi(const XArgs& a, int FI, dim3 grid, size_t lds, hipStream_t s) {
@@ -1314,7 +1256,7 @@ int dvd_xconv_pack_many(const dvd_xpack_item* items, int n, void* table, size_t 
 }
 
 int dvd_xconv_select(int cfg) {
-  DVD_REQUIRE(cfg >= 0 && cfg <= 7, "xconv_select: cfg %d", cfg);
+  DVD_REQUIRE(cfg >= 0 && cfg <= dvd::kXSelHalo, "xconv_select: cfg %d", cfg);
   dvd::g_xcfg = cfg;
   return DVD_OK;
 }
@@ -1340,33 +1282,16 @@ static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed
   DVD_REQUIRE(!(s2 || zi) || KS == 3, "xconv: the strided forms exist for 3x3 kernels (got %d)", KS);
   const int Hq = (H + 1) / 2, Wq = (W + 1) / 2;
   const int Cin = Cin_total / groups, Cout = Cout_total / groups;
-  // buffer-addressed main loop: whole 16-channel chunks, 31-bit byte offsets inside one image's input channels and
-  // inside the packed weights of one block row
-  const bool fast = (Cin % 16 == 0) && ((long long)Cin * H * W * 4 < (1ll << 31)) &&
-                    ((long long)8 * ((Cin + 15) / 16) * KS * KS * 2048 < (1ll << 31)) && dvd::g_xcfg != 4;
+  // block shape, tile and position mapping of this launch (csrc/xconv_tile.h)
+  dvd::XPlan plan;
+  const bool planned = dvd::xconv_plan(Cin, Cout, H, W, KS, s2 != 0, in16 != 0, dvd::g_xcfg, plan);
+  const bool fast = plan.fast;
   DVD_REQUIRE(fast || !in16, "xconv: fp16 activations need input channels in multiples of 16 (got %d per group)", Cin);
   DVD_REQUIRE(!(s2 || zi) || fast, "xconv: the strided forms need input channels in multiples of 16 (got %d per group)", Cin);
-  // (stride 2: four input cells per output -- blocks of at most 128 channels, fp32 activations on ONE activation stage)
-  dvd::XCfg c = dvd::pick_cfg((fast && !s2) ? Cout : (Cout < 128 ? Cout : 128), KS);
-  if (!fast) c.b1 = false;   // the wide shapes exist as FAST kernels only
-  if (s2) c.b1 = true;
-  if (in16) c.b1 = false;
-  c.in16 = in16 != 0;
-  int Hh = H, Ww = W;
-  if (KS == 1) {           // no spatial structure: one row of H * W positions
-    Hh = 1;
-    Ww = H * W;
-  }
-  dvd::XTile t;
-  int S2 = 0;
-  if (s2) {
-    Hh = Hq;
-    Ww = Wq;
-    DVD_REQUIRE(dvd::pick_tile_s2(Hh, Ww, c, t, S2), "xconv: no stride-2 tile of a %dx%d image fits the LDS", H, W);
-  } else {
-    if (c.b1 && !dvd::pick_tile(Hh, Ww, KS, c, t)) c.b1 = false;     // (large kernels: the haloed tile needs more LDS)
-    DVD_REQUIRE(dvd::pick_tile(Hh, Ww, KS, c, t), "xconv: no tile of a %dx%d image with a %dx%d kernel fits the LDS", H, W, KS, KS);
-  }
+  DVD_REQUIRE(planned, "xconv: no %stile of a %dx%d image with a %dx%d kernel fits the LDS", s2 ? "stride-2 " : "", H, W, KS, KS);
+  const dvd::XCfg& c = plan.c;
+  const dvd::XTile& t = plan.t;
+  const int Hh = plan.Hh, Ww = plan.Ww, S2 = plan.S2;
   dvd::XArgs a;
   a.x = x;
   a.wp = static_cast<const uint4*>(packed);
@@ -1385,11 +1310,11 @@ static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = Hh; a.W = Ww;
   a.G = groups; a.mtiles = dvd::xconv_mtiles(Cout);
   a.KS = KS; a.pad = KS / 2; a.T = KS * KS;
-  a.TR = t.TR; a.TC = t.TC; a.P = t.P; a.ntr = t.ntr; a.ntc = t.ntc; a.NV = t.NV;
+  a.TR = t.TR; a.TC = t.TC; a.P = t.P; a.PQ = t.PQ; a.ntr = t.ntr; a.ntc = t.ntc; a.NV = t.NV;
   a.nkc = (Cin + 15) / 16; a.npos = t.npos; a.nfi = t.FI;
   a.Hi = s2 ? H : (zi ? Hq : Hh); a.Wi = s2 ? W : (zi ? Wq : Ww); a.S2 = S2; a.ZI = zi;
   a.relu_in = flags & 1; a.relu_out = (flags >> 1) & 1; a.res_relu = (flags >> 2) & 1;
-  const int mblocks = (Cout + c.blockM() - 1) / c.blockM();
+  const int mblocks = plan.mblocks;
   a.mbpg = mblocks;
   DVD_REQUIRE((long long)mblocks * groups <= 65535, "xconv: too many channel blocks");
   const dim3 grid(t.ntr * t.ntc, mblocks * groups, N);

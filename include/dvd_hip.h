@@ -454,7 +454,10 @@ int dvd_xconv_fwd(const float* x, const float* x_amax, const void* packed, const
  * 0 = automatic (256 channels x 128 positions for 1x1 kernels, 256 x 256 for k >= 3), 1 = round 2's 128 x 128 blocks,
  * 2 / 3 = force 256 x 128 / 256 x 256, 4 = round 2's blocks on the generic pointer-addressed main loop (the path shapes
  * with Cin % 16 != 0 take), 5 = 128 x 128 blocks with one activation stage at three blocks per CU, 6 = 1x1 kernels without
- * their two-chunk loop, 7 = 1x1 kernels with the narrow (dword) epilogue instead of the LDS-transposed 16-byte one.
+ * their two-chunk loop, 7 = 1x1 kernels with the narrow (dword) epilogue instead of the LDS-transposed 16-byte one,
+ * 8 = automatic block shapes with the GEMM columns of a k x k tile on the cells of the HALOED tile and the tile choice that
+ * goes with it (rounds 2-6; 0-7 compute the tile's outputs only, csrc/xconv_tile.h, which also names the one launch that
+ * stays on haloed positions in every setting).
  * Results are identical in every setting (same products, same K order). */
 int dvd_xconv_select(int cfg);
 /* Transposed / forward packing with every weight of output channel co scaled by gamma[co] / sqrt(var[co] + eps): the

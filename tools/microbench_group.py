@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Grouped 3x3 convolutions of ResNeXt-101 32x8d stages 2-4 at the bench's 48-image launches: forward, backward-data and
-weight gradient through dvd_hip.conv (XCONV_CFG=8: the xconv_kernel path instead of xgroup_kernel; XWGRAD_VARIANT=2: the
-64 x 64 blocks, 3: four K steps per row step and the round-robin deal of work items -- dvd_xwgrad_select)."""
+weight gradient through dvd_hip.conv (XCONV_CFG: dvd_xconv_select, 8 = haloed positions and the tile choice that goes with
+them, for A/B against 0; XWGRAD_VARIANT=2: the 64 x 64 blocks, 3: four K steps per row step and the round-robin deal of work
+items -- dvd_xwgrad_select)."""
 import json
 import os
 import sys

@@ -40,7 +40,7 @@ def main():
     if os.environ.get('XCONV_ONLY'):                          # comma-separated indices into SHAPES
         shapes = [SHAPES[int(i)] for i in os.environ['XCONV_ONLY'].split(',')]
     nmul = int(os.environ.get('XCONV_NMUL', '1'))            # 3: the 48-image chunks of the bench
-    cfg = int(os.environ.get('XCONV_CFG', '0'))              # dvd_xconv_select: 0 auto, 1 round-2 blocks, 2/3 forced, 4 generic loop
+    cfg = int(os.environ.get('XCONV_CFG', '0'))              # dvd_xconv_select: 0 auto, 1 round-2 blocks, 2/3 forced, 4 generic loop, 8 haloed positions
     from dvd_hip import _lib
     _lib.check(_lib.load().dvd_xconv_select(cfg), 'dvd_xconv_select')
     skip_wgrad = bool(os.environ.get('XCONV_NO_WGRAD'))
