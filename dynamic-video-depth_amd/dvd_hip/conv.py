@@ -4,19 +4,21 @@
   * the DVD_AB measurement switches and the fp16 activation storage's loss-scale state (`AB`, `GRAD_SCALE`);
   * element-wise and pooling layers: `bn_eval_relu`, `to_half`, `add_f16`, `upsample_bilinear2x`, `maxpool3s2`, `AvgPool2d`,
     the depth heads (`head1x1`, `head3x3`, `depth_tail`);
-  * grouped 3x3 convolutions: `GroupedConv3x3C8` (`nn.Conv2d(C, C, 3, padding=1, groups=C // 8, bias=False)`, the `conv2` of
-    the ResNeXt-101 32x8d stage-1 bottlenecks, third_party/midas_blocks.py:35-50; csrc/gconv.hip), `GroupedConv3x3C16` and
-    `GroupedConv3x3C32` (on the grouped xconv path);
+  * the 8-per-group 3x3 kernels (csrc/gconv.hip: the `conv2` of the ResNeXt-101 32x8d stage-1 bottlenecks,
+    third_party/midas_blocks.py:35-50) and the legacy fp32 32-per-group ones (csrc/gconv32.hip, DVD_AB=gconv32);
   * the ResNeXt stem as a stride-1 5x5 convolution over the space-to-depth image (`stem_conv_bn_relu`);
   * dense and grouped 'same' convolutions on the split-operand MFMA kernels (csrc/xconv.hip, csrc/xwgrad3.hip): the packed
     weight cache and its per-step plan (`xconv_packed`, `xconv_packed_scaled`, `PACK_PLAN`), the launch (`_xconv_run`), the
-    weight gradient (`xconv_wgrad`), the autograd Functions `_XConv`, `_XConvS2`, `_XConvBn` with their fused gradient
-    joins and ReLU-mask hand-over (`_Site`), and the entry points the networks call: `xconv2d`, `conv_bn_act`, `XConv2d`.
+    weight gradient (`xconv_wgrad`), the autograd Functions `_XConv` and `_XConvBn` (stride 1 and the native stride 2) with
+    their fused gradient joins and ReLU-mask hand-over (`_Site`);
+  * `_route`: the one place where a layer's hyper-parameters, the tensor and the AB switches become a choice of kernels, and
+    the entry points that run it: `xconv2d`, `conv_bn_act`, `XConv2d` and its subclasses `GroupedConv3x3C8 / C16 / C32`.
 
 Every module keeps the parameter names and shapes of the `nn.Conv2d` it replaces, so state_dicts interchange.  Tensors that
 the kernels do not cover (CPU tensors of the oracle / tests, other dtypes) take the ATen ops; on a GPU in fp32 or fp16 the HIP
 path is the one that runs.
 """
+import collections
 import ctypes
 import os as _os
 import weakref
@@ -66,12 +68,24 @@ def _is16(t):
     return t.dtype == torch.float16
 
 
-def _gs(i):
-    """1-element view of the loss-scale state: 1 = 1 / S (out_scale of parameter gradients), 3 = observed max |S g|."""
+def _gs_state():
     st = GRAD_SCALE['state']
     if st is None:
         raise RuntimeError('fp16 gradients need a loss-scale state (conv.set_grad_scale_state; Model does it with --act_fp16)')
-    return st[i:i + 1]
+    return st
+
+
+def _gs(i):
+    """1-element view of the loss-scale state: 1 = 1 / S (out_scale of parameter gradients), 3 = observed max |S g|."""
+    return _gs_state()[i:i + 1]
+
+
+def _gscale_begin(gy, weight, n):
+    """Start the backward pass's loss scale from max|g_out| and max|w| over the head's n weights (csrc/a16.hip) -> the state."""
+    from .ops import amax
+    state = _gs_state()
+    _lib.check(_lib.load().dvd_gscale_begin(_p(state), _p(amax(gy)), _p(weight), n, _stream()), 'dvd_gscale_begin')
+    return state
 
 
 def _fwd_monitor():
@@ -194,19 +208,13 @@ class _Head1x1(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .ops import amax
         x, weight = ctx.saved_tensors
         relu_in, has_bias = ctx.cfg
         gy = gy.contiguous().float()
         N, C, H, W = x.shape
         lib = _lib.load()
         h16 = _is16(x)
-        state = None
-        if h16:
-            state = GRAD_SCALE['state']
-            if state is None:
-                raise RuntimeError('fp16 gradients need a loss-scale state (conv.set_grad_scale_state)')
-            _lib.check(lib.dvd_gscale_begin(_p(state), _p(amax(gy)), _p(weight), C, _stream()), 'dvd_gscale_begin')
+        state = _gscale_begin(gy, weight, C) if h16 else None
         gx = torch.empty_like(x)
         gw = torch.empty_like(weight)
         gb = torch.empty(1, device=x.device, dtype=torch.float32) if has_bias else None
@@ -268,15 +276,11 @@ class _Head3x3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .ops import amax
         x, weight = ctx.saved_tensors
         gy = gy.contiguous().float()
         N, C, H, W = x.shape
         lib = _lib.load()
-        state = GRAD_SCALE['state']
-        if state is None:
-            raise RuntimeError('fp16 gradients need a loss-scale state (conv.set_grad_scale_state)')
-        _lib.check(lib.dvd_gscale_begin(_p(state), _p(amax(gy)), _p(weight), weight.numel(), _stream()), 'dvd_gscale_begin')
+        state = _gscale_begin(gy, weight, weight.numel())
         gx = torch.empty_like(x)
         gw = torch.empty_like(weight)
         gb = torch.empty(1, device=x.device, dtype=torch.float32) if ctx.has_bias else None
@@ -427,26 +431,11 @@ class _GConv3x3C32(torch.autograd.Function):
 
 
 def gconv3x3_c32(x, weight):
-    """y = conv2d(x, weight, padding=1, groups=C // 32) for weight [C, 32, 3, 3]."""
+    """y = conv2d(x, weight, padding=1, groups=C // 32) for weight [C, 32, 3, 3] on the legacy kernels.  An entry for tests and
+    tools/ (a bare weight, no module): the modules take _route."""
     if x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32:
         return _GConv3x3C32.apply(x, weight)
     return F.conv2d(x, weight, None, 1, 1, 1, x.shape[1] // 32)
-
-
-class GroupedConv3x3C32(nn.Conv2d):
-    """Drop-in for nn.Conv2d(C, C, 3, stride=1, padding=1, groups=C // 32, bias=False) (fp32 MFMA kernels)."""
-
-    def __init__(self, channels):
-        if channels % 32:
-            raise ValueError('GroupedConv3x3C32 needs a multiple of 32 channels')
-        super().__init__(channels, channels, 3, stride=1, padding=1, groups=channels // 32, bias=False)
-
-    def forward(self, x):
-        if x.is_cuda and x.dtype in ACT_DTYPES and not AB['gconv32']:
-            # the grouped split-operand MFMA kernels (csrc/xconv.hip, csrc/xwgrad3.hip): 0.097 ms forward / 0.37 ms backward per
-            # 16-image call at [1024, 24, 42] against 0.156 / 0.42 ms of the fp32-MFMA kernels (tools/microbench_gx.py)
-            return _xconv(x, self.weight, None, None, False, False, self.groups)
-        return gconv3x3_c32(x, self.weight)
 
 
 # ---- the ResNeXt stem natively (round 4) ------------------------------------------------------------------------------
@@ -644,48 +633,12 @@ def _pair_groups_of_16(weight):
     return w32.view(C, 32, 3, 3)
 
 
-class GroupedConv3x3C16(nn.Conv2d):
-    """nn.Conv2d(C, C, 3, stride=1, padding=1, groups=C // 16, bias=False) (ResNeXt stage 2, stride-1 blocks)
-    on the 32-channel MFMA kernels: two groups share one 32x32 tile with a block-diagonal weight.  MIOpen's
-    immediate mode runs this shape per image as im2col + small GEMMs (~80 launches per call)."""
-
-    def __init__(self, channels, stride=1):
-        if channels % 32:
-            raise ValueError('GroupedConv3x3C16 needs a multiple of 32 channels')
-        super().__init__(channels, channels, 3, stride=stride, padding=1, groups=channels // 16, bias=False)
-
-    def forward(self, x):
-        st = self.stride[0]
-        if x.is_cuda and x.dtype in ACT_DTYPES and (st == 1 or not AB['gconv32']):
-            if not AB['gconv32']:
-                w32 = _pair_groups_of_16(self.weight)
-                if st == 2 and xconv_s2_supported(x, w32, self.groups // 2):
-                    return _xconv_s2(x, w32, None, self.groups // 2)
-                y = _xconv(x, w32, None, None, False, False, self.groups // 2)
-                # the stride-2 entry of stage 2: out[i][j] of a strided 'same' 3x3 is the stride-1 result at [s*i][s*j]
-                # (4x the needed work, still half of MIOpen's per-image im2col + GEMM + col2im path)
-                return y if st == 1 else _subsample(y, st)
-            return gconv3x3_c32(x, _pair_groups_of_16(self.weight))
-        return F.conv2d(x, self.weight, None, self.stride, 1, 1, self.groups)
-
-
 def gconv3x3_c8(x, weight):
-    """y = conv2d(x, weight, padding=1, groups=C // 8) for weight [C, 8, 3, 3]."""
+    """y = conv2d(x, weight, padding=1, groups=C // 8) for weight [C, 8, 3, 3].  An entry for tests and tools/ (a bare weight,
+    no module): the modules take _route."""
     if x.is_cuda and x.dtype in ACT_DTYPES and weight.dtype == torch.float32:
         return _GConv3x3C8.apply(x, weight)
     return F.conv2d(x, weight, None, 1, 1, 1, x.shape[1] // 8)
-
-
-class GroupedConv3x3C8(nn.Conv2d):
-    """Drop-in for nn.Conv2d(C, C, 3, stride=1, padding=1, groups=C // 8, bias=False)."""
-
-    def __init__(self, channels):
-        if channels % 8:
-            raise ValueError('GroupedConv3x3C8 needs a multiple of 8 channels')
-        super().__init__(channels, channels, 3, stride=1, padding=1, groups=channels // 8, bias=False)
-
-    def forward(self, x):
-        return gconv3x3_c8(x, self.weight)
 
 
 # ---------------------------------------------------------------------------------------
@@ -973,11 +926,10 @@ def _bias_grad_sum(gy):
 
 
 def _xconv_bwd_data(ctx, g, g_amax, weight, groups, mask_src, g_alias=None, bn_scale=None, **strided):
-    """The backward-data launch of the three xconv Functions and what goes with it: max|gx| comes from the epilogue (fp16: into
+    """The backward-data launch of the two xconv Functions and what goes with it: max|gx| comes from the epilogue (fp16: into
     the loss-scale policy's observed maximum) and is attached to gx (used by the next backward if autograd hands this very
     tensor on); the BatchNorm+ReLU site x came from is told which tensor carries its mask (see _Site).  g_alias: the gradient of
-    x's other consumers, added in the epilogue; bn_scale = (gamma, var, eps): through a fused BatchNorm; strided: stride=-2 and
-    out_hw of _XConvS2."""
+    x's other consumers, added in the epilogue; bn_scale = (gamma, var, eps): through a fused BatchNorm; strided: see _strided_bwd."""
     h16 = _is16(g)
     gx_amax = _gs(3) if h16 else new_scalar(g.device)
     packed = xconv_packed(weight, True, groups) if bn_scale is None else xconv_packed_scaled(weight, groups, *bn_scale)
@@ -990,10 +942,26 @@ def _xconv_bwd_data(ctx, g, g_amax, weight, groups, mask_src, g_alias=None, bn_s
     return gx
 
 
+def _strided(stride):
+    """The keyword that _xconv_run's forward and xconv_wgrad take for a stride-2 convolution (nothing at stride 1)."""
+    return {'stride': 2} if stride == 2 else {}
+
+
+def _strided_bwd(stride, x):
+    """_xconv_run's keywords for the backward-data pass of a stride-2 convolution of x: the kernel reads the compact gradient as
+    if it were zero-interleaved (csrc/xconv.hip XArgs::ZI) and writes x's resolution."""
+    return dict(stride=-2, out_hw=(x.shape[2], x.shape[3])) if stride == 2 else {}
+
+
 class _XConv(torch.autograd.Function):
     """y = conv2d(act(x), w, stride 1, padding k//2) + bias + res'   with act = ReLU or identity and
     res' = residual or relu(residual).  Forward and backward-data on csrc/xconv.hip; backward-weight on
     csrc/xwgrad3.hip (deterministic).
+
+    stride=2: y = conv2d(x, w, bias, stride 2, padding 1) for a 3x3 kernel with whole 16-channel chunks per group
+    (torchvision's Bottleneck.conv2 at the entry of ResNeXt stages 2-4, third_party/midas_blocks.py:35-50), without ReLU,
+    residual or alias: the forward stages the haloed input tile as four phase planes (csrc/xconv.hip XArgs::S2), the
+    backward-data kernel reads the compact gradient (_strided_bwd), the weight gradient takes it zero-interleaved (xconv_wgrad).
 
     Fused gradient joins (round 3).  `alias`: the Function also returns its input as a second differentiable output; the
     OTHER consumers of x (a residual connection, a shortcut convolution) take that alias instead of x, so their gradient
@@ -1005,7 +973,9 @@ class _XConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x_amax, weight, bias, residual, relu_in, res_relu, groups=1, alias=False, res_unmasked=False,
-                in_site=None):
+                in_site=None, stride=1):
+        if stride == 2 and (residual is not None or relu_in or alias):
+            raise RuntimeError('xconv: the stride-2 forms take no residual, input ReLU or alias')
         ctx.set_materialize_grads(False)
         ctx.in_site = in_site if (in_site is not None and not relu_in and not AB['no_maskfuse']) else None
         x = x.contiguous()
@@ -1014,10 +984,10 @@ class _XConv(torch.autograd.Function):
         Cout, _, KS, _ = weight.shape
         y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, KS, bias=bias, residual=residual, relu_in=relu_in,
-                       res_relu=res_relu, groups=groups, x_amax=x_amax, y_amax=amax_slot)
+                       res_relu=res_relu, groups=groups, x_amax=x_amax, y_amax=amax_slot, **_strided(stride))
         ctx.save_for_backward(x, residual if (res_relu and not res_unmasked) else None, x_amax)
         ctx.wparam = weight          # the tensor object that carries the packed copies
-        ctx.cfg = (bool(relu_in), bool(res_relu), bias is not None, residual is not None, groups, bool(res_unmasked))
+        ctx.cfg = (bool(relu_in), bool(res_relu), bias is not None, residual is not None, groups, bool(res_unmasked), int(stride))
         if alias:
             return y, y_amax, x
         return y, y_amax
@@ -1026,92 +996,32 @@ class _XConv(torch.autograd.Function):
     def backward(ctx, gy, _g_amax, g_alias=None):
         x, residual, x_amax = ctx.saved_tensors
         weight = ctx.wparam
-        relu_in, res_relu, has_bias, has_res, groups, res_unmasked = ctx.cfg
+        relu_in, res_relu, has_bias, has_res, groups, res_unmasked, stride = ctx.cfg
         if gy is None:                      # only the alias was used downstream
-            return g_alias, None, None, None, None, None, None, None, None, None, None
+            return (g_alias,) + (None,) * 11
         gy = gy.contiguous()
         need = ctx.needs_input_grad
         gx = gw = gr = None
         gb, g_amax = _gy_reductions(gy, has_bias and need[3], (need[0] or need[2]) and not _is16(gy))
         if need[0]:
             # the mask [x > 0]: of the fused input ReLU, or of the BatchNorm+ReLU site whose output x is (ReLU is already applied)
-            gx = _xconv_bwd_data(ctx, gy, g_amax, weight, groups, x if (relu_in or ctx.in_site is not None) else None, g_alias)
+            gx = _xconv_bwd_data(ctx, gy, g_amax, weight, groups, x if (relu_in or ctx.in_site is not None) else None, g_alias,
+                                 **_strided_bwd(stride, x))
         if need[2]:
-            gw = xconv_wgrad(x, gy, weight.shape, relu_in, groups, x_amax=x_amax, g_amax=g_amax)
+            gw = xconv_wgrad(x, gy, weight.shape, relu_in, groups, x_amax=x_amax, g_amax=g_amax, **_strided(stride))
         if has_bias and need[3] and gb is None:
             gb = _bias_grad_sum(gy)
         if has_res and need[4]:
             gr = gy * (residual > 0).to(gy.dtype) if (res_relu and not res_unmasked) else gy
-        return gx, None, gw, gb, gr, None, None, None, None, None, None
+        return gx, None, gw, gb, gr, None, None, None, None, None, None, None
 
 
-class _XConvS2(torch.autograd.Function):
-    """y = conv2d(x, w, bias, stride 2, padding 1) for a 3x3 kernel, dense or grouped with >= 32 channels per group
-    (torchvision's Bottleneck.conv2 at the entry of ResNeXt stages 2-4, third_party/midas_blocks.py:35-50).  Rounds 2-5 ran
-    the stride-1 kernel and sub-sampled its output (4x the products, a full-resolution round trip); now the forward stages the
-    haloed input tile as four phase planes (csrc/xconv.hip, XArgs::S2) and the backward-data kernel reads the compact
-    gradient as if it were zero-interleaved (XArgs::ZI).  The weight gradient still takes the interleaved gradient from
-    csrc/pool.hip (dvd_subsample2_bwd) into the stride-1 kernels of csrc/xwgrad3.hip."""
-
-    @staticmethod
-    def forward(ctx, x, x_amax, weight, bias, groups, in_site):
-        ctx.set_materialize_grads(False)
-        ctx.in_site = in_site if (in_site is not None and not AB['no_maskfuse']) else None
-        x = x.contiguous()
-        Cout = weight.shape[0]
-        y_amax, amax_slot = _fwd_amax(ctx, x)
-        y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, 3, bias=bias, groups=groups, x_amax=x_amax,
-                       y_amax=amax_slot, stride=2)
-        ctx.save_for_backward(x, x_amax)
-        ctx.wparam = weight
-        ctx.cfg = (bias is not None, groups)
-        return y, y_amax
-
-    @staticmethod
-    def backward(ctx, gy, _g_amax):
-        x, x_amax = ctx.saved_tensors
-        weight = ctx.wparam
-        has_bias, groups = ctx.cfg
-        if gy is None:
-            return None, None, None, None, None, None
-        gy = gy.contiguous()
-        need = ctx.needs_input_grad
-        N, Cin, H, W = x.shape
-        h16 = _is16(gy)
-        gx = gw = None
-        gb, g_amax = _gy_reductions(gy, has_bias and need[3], (need[0] or need[2]) and not h16)
-        if need[0]:
-            gx = _xconv_bwd_data(ctx, gy, g_amax, weight, groups, x if ctx.in_site is not None else None, stride=-2, out_hw=(H, W))
-        if need[2]:
-            gyf = torch.empty(N, gy.shape[1], H, W, device=gy.device, dtype=gy.dtype)       # zero-interleaved gradient
-            _lib.check(_lib.load().dvd_subsample2_bwd(_p(gy), _p(gyf), int(h16), N * gy.shape[1], H, W, _stream()),
-                       'dvd_subsample2_bwd')
-            gw = xconv_wgrad(x, gyf, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax)
-        if has_bias and need[3] and gb is None:
-            gb = _bias_grad_sum(gy)
-        return gx, None, gw, gb, None, None
-
-
-def xconv_s2_supported(x, weight, groups):
-    """3x3 / stride 2 / padding 1 on the strided forms of csrc/xconv.hip: whole 16-channel chunks per group (the
-    buffer-addressed main loop), grouped layers with at least 32 channels per group."""
-    cpg = weight.shape[1]
-    return (x.is_cuda and x.dtype in ACT_DTYPES and weight.dtype == torch.float32 and tuple(weight.shape[2:]) == (3, 3) and
-            cpg % 16 == 0 and (weight.shape[0] // groups) % 16 == 0 and (groups == 1 or cpg >= 32) and not AB['no_s2'])
-
-
-def _xconv_s2(x, weight, bias, groups=1):
-    x_amax = None if _is16(x) else amax_of(x)
-    y, y_amax = _XConvS2.apply(x, x_amax, weight, bias, groups, getattr(x, '_dvd_site', None))
-    return set_amax(y, y_amax)
-
-
-def _xconv(x, weight, bias, residual, relu_in, res_relu, groups=1, alias=False, res_unmasked=False):
+def _xconv(x, weight, bias, residual, relu_in, res_relu, groups=1, alias=False, res_unmasked=False, stride=1):
     """_XConv with the max|.| scalars threaded through: the input's is looked up (or computed), the output's attached.
     alias=True returns (y, alias of x), see _XConv."""
     x_amax = None if _is16(x) else amax_of(x)
     out = _XConv.apply(x, x_amax, weight, bias, residual, relu_in, res_relu, groups, bool(alias), res_unmasked,
-                       getattr(x, '_dvd_site', None))
+                       getattr(x, '_dvd_site', None), stride)
     y = set_amax(out[0], out[1])
     return (y, set_amax(out[2], x_amax)) if len(out) == 3 else y
 
@@ -1121,26 +1031,39 @@ def wgrad_reports_rowsum(wshape, groups):
     return wshape[2] == 1 and groups == 1 and not AB['no_xwgrad3']
 
 
-def xconv_wgrad3_rowsum(x, gy, wshape, groups, x_amax, g_amax, rowsum):
-    """xconv_wgrad of an fp32 3x3 convolution plus rowsum[co] = sum_{n,p} gy[n][co][p] (csrc/xwgrad3.hip dvd_xwgrad3_rowsum: the
-    32 x 32 grouped kernel sums the rows it stages, other shapes take a pass over gy).  A helper of its own: xconv_wgrad's 3x3
-    call stays the plain dvd_xwgrad3."""
-    lib = _lib.load()
-    N, Cin, H, W = x.shape
-    dims = (N, Cin, wshape[0], H, W, groups)
-    gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-    ws = _workspace(lib.dvd_xwgrad3_workspace_bytes(*dims), x.device)
-    _lib.check(lib.dvd_xwgrad3_rowsum(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(rowsum), _p(ws), ctypes.c_size_t(ws.numel()),
-                                      *(dims + (0, _stream()))), 'dvd_xwgrad3_rowsum')
-    return gw
+# (kernel size, fp16 operands?, the exact-fp32 kernel?) -> (entry point, the one taken when a `rowsum` tensor is given | None,
+# workspace query, the integer that follows N, Cin, Cout, H, W in their argument lists: 'groups', the kernel size, or none).
+# The exact-fp32 MFMA kernel (csrc/xwgrad.hip) is the one the split-operand kernels replaced: dense fp32 gradients under
+# DVD_AB=no_xwgrad3.  The entry points of _XWGRAD_ROWSUM_SLOT have a rowsum pointer (null or not) behind the gradient's.
+_XWGRAD = {
+    (1, False, False): ('dvd_xwgrad1s_rowsum', 'dvd_xwgrad1s_rowsum', 'dvd_xwgrad1s_workspace_bytes', None),
+    (3, False, False): ('dvd_xwgrad3', 'dvd_xwgrad3_rowsum', 'dvd_xwgrad3_workspace_bytes', 'groups'),
+    (5, False, False): ('dvd_xwgradk', None, 'dvd_xwgradk_workspace_bytes', 5),
+    (7, False, False): ('dvd_xwgradk', None, 'dvd_xwgradk_workspace_bytes', 7),
+    (11, False, False): ('dvd_xwgradk', None, 'dvd_xwgradk_workspace_bytes', 11),
+    (1, True, False): ('dvd_xwgrad1s_h', None, 'dvd_xwgrad1s_workspace_bytes', None),
+    (3, True, False): ('dvd_xwgrad3_h', None, 'dvd_xwgrad3_workspace_bytes', 'groups'),
+    (5, True, False): ('dvd_xwgradk_h', None, 'dvd_xwgradk_workspace_bytes', 5),
+    (7, True, False): ('dvd_xwgradk_h', None, 'dvd_xwgradk_workspace_bytes', 7),
+    (11, True, False): ('dvd_xwgradk_h', None, 'dvd_xwgradk_workspace_bytes', 11),
+    (1, False, True): ('dvd_xwgrad', None, 'dvd_xwgrad_workspace_bytes', 1),
+    (3, False, True): ('dvd_xwgrad', None, 'dvd_xwgrad_workspace_bytes', 3),
+    (5, False, True): ('dvd_xwgrad', None, 'dvd_xwgrad_workspace_bytes', 5),
+    (7, False, True): ('dvd_xwgrad', None, 'dvd_xwgrad_workspace_bytes', 7),
+    (11, False, True): ('dvd_xwgrad', None, 'dvd_xwgrad_workspace_bytes', 11),
+}
+_XWGRAD_ROWSUM_SLOT = ('dvd_xwgrad1s_rowsum', 'dvd_xwgrad3_rowsum')
 
 
-def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rowsum=None):
+def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rowsum=None, stride=1):
     """dW[co][ci][tap] = sum_{n,p} gy[n][co][p] * act(x)[n][ci][p + tap] on the split-operand MFMA kernels of csrc/xwgrad3.hip:
     1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 (xwgradk: the hourglass's inception branches and the stem's
     space-to-depth form).  fp16 operands take one MFMA per product and the result times 1 / (loss scale) (H16).
-    rowsum: [Cout] tensor that receives sum_{n,p} gy[n][co][p] from the dense fp32 1x1 kernel (it sums the rows it stages
-    anyway, see wgrad_reports_rowsum)."""
+    rowsum: [Cout] tensor that receives sum_{n,p} gy[n][co][p] from the fp32 1x1 and 3x3 entry points (dvd_xwgrad1s_rowsum;
+    dvd_xwgrad3_rowsum: the 32 x 32 grouped kernel sums the rows it stages, other shapes take a pass over gy); the other entry
+    points have no such form and leave it alone (wgrad_reports_rowsum, dvd_xwgrad_rowsum_in_kernel: ask before relying on it).
+    stride=2: gy is the compact gradient of a 3x3 / stride 2 / padding 1 convolution of x; the stride-1 kernels take its
+    zero-interleaved copy at x's resolution (csrc/pool.hip dvd_subsample2_bwd; the zeros add nothing to dW or to rowsum)."""
     Cout, KS = wshape[0], wshape[2]
     h16 = _is16(gy)
     if h16 and not _is16(x):
@@ -1148,36 +1071,32 @@ def xconv_wgrad(x, gy, wshape, relu_in, groups=1, x_amax=None, g_amax=None, rows
     if KS not in (1, 3, 5, 7, 11) or (groups > 1 and KS != 3):
         raise RuntimeError('xconv: the weight gradient exists for 1x1, 3x3 (dense or grouped) and dense 5x5 / 7x7 / 11x11 kernels '
                            '(got %s, %d groups)' % (tuple(wshape), groups))
-    # the kernel family and the integer that follows N, Cin, Cout, H, W in its argument lists; DVD_AB=no_xwgrad3: the dense fp32
-    # gradients on the exact-fp32 MFMA kernel (csrc/xwgrad.hip) that the split-operand ones replaced
-    if AB['no_xwgrad3'] and groups == 1 and not h16:
-        family, extra = 'dvd_xwgrad', (KS,)
-    elif KS == 1:
-        family, extra = 'dvd_xwgrad1s', ()
-    elif KS == 3:
-        family, extra = 'dvd_xwgrad3', (groups,)
-    else:
-        family, extra = 'dvd_xwgradk', (KS,)
+    entry, with_sums, query, extra = _XWGRAD[(KS, h16, AB['no_xwgrad3'] and groups == 1 and not h16)]
     lib = _lib.load()
     N, Cin, H, W = x.shape
-    dims = (N, Cin, Cout, H, W) + extra
-    if not h16:                                 # the operands' scales (fp16 operands carry none)
-        if x_amax is None:
+    dims = (N, Cin, Cout, H, W) + {None: (), 'groups': (groups,)}.get(extra, (extra,))
+    if not h16:                                 # the operands' scales (fp16 operands carry none); the compact gradient's
+        if x_amax is None:                      # maximum is the interleaved one's
             x_amax = amax_of(x)
         if g_amax is None:
             g_amax = amax_of(gy)
-    gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
-    ws = _workspace(getattr(lib, family + '_workspace_bytes')(*dims), x.device)
-    tail = (_p(gw), _p(ws), ctypes.c_size_t(ws.numel())) + dims + (int(bool(relu_in)), _stream())
+    if stride == 2:
+        gyf = torch.empty(N, Cout, H, W, device=gy.device, dtype=gy.dtype)
+        _lib.check(lib.dvd_subsample2_bwd(_p(gy), _p(gyf), int(h16), N * Cout, H, W, _stream()), 'dvd_subsample2_bwd')
+        gy = gyf
     if h16:
-        _lib.check(getattr(lib, family + '_h')(_p(x), _p(gy), _p(_gs(1)), *tail), family + '_h')
-    elif family == 'dvd_xwgrad':
-        _lib.check(lib.dvd_xwgrad(_p(x), _p(gy), *tail), family)
-    elif family == 'dvd_xwgrad1s':
-        _lib.check(lib.dvd_xwgrad1s_rowsum(_p(x), _p(x_amax), _p(gy), _p(g_amax), _p(gw), _p(rowsum), *tail[1:]),
-                   'dvd_xwgrad1s_rowsum')
+        operands = (_p(x), _p(gy), _p(_gs(1)))
+    elif entry == 'dvd_xwgrad':
+        operands = (_p(x), _p(gy))
     else:
-        _lib.check(getattr(lib, family)(_p(x), _p(x_amax), _p(gy), _p(g_amax), *tail), family)
+        operands = (_p(x), _p(x_amax), _p(gy), _p(g_amax))
+    if rowsum is not None and with_sums is not None:
+        entry = with_sums
+    sums = (_p(rowsum),) if entry in _XWGRAD_ROWSUM_SLOT else ()
+    gw = torch.empty(wshape, device=x.device, dtype=torch.float32)
+    ws = _workspace(getattr(lib, query)(*dims), x.device)
+    _lib.check(getattr(lib, entry)(*operands, _p(gw), *sums, _p(ws), ctypes.c_size_t(ws.numel()), *dims, int(bool(relu_in)),
+                                   _stream()), entry)
     return gw
 
 
@@ -1191,7 +1110,7 @@ class _XConvBn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, x_amax, weight, cbias, gamma, beta, mean, var, eps, residual, relu, groups, alias=False, in_site=None,
                 out_site=None, stride=1):
-        """stride 2: the 3x3 / stride 2 / padding 1 forms of the kernels (see _XConvS2), with the same site protocol."""
+        """stride 2: the 3x3 / stride 2 / padding 1 forms of the kernels (see _XConv), with the same site protocol."""
         ctx.set_materialize_grads(False)    # (alias: see _XConv -- the gradient of the input's other consumers arrives in backward)
         ctx.in_site = in_site if (in_site is not None and not AB['no_maskfuse']) else None      # see _Site
         ctx.out_site = out_site if relu else None
@@ -1202,7 +1121,7 @@ class _XConvBn(torch.autograd.Function):
         y_amax, amax_slot = _fwd_amax(ctx, x)
         y = _xconv_run(x, xconv_packed(weight, False, groups), Cout, KS, bias=cbias, residual=residual, relu_out=relu,
                        groups=groups, bn=(gamma, beta, mean, var, eps), x_amax=x_amax, y_amax=amax_slot,
-                       **({'stride': 2} if stride == 2 else {}))
+                       **_strided(stride))
         ctx.save_for_backward(x, y if relu else None, gamma, mean, var, cbias, x_amax)
         ctx.wparam = weight
         ctx.cfg = (float(eps), bool(relu), residual is not None, groups, int(stride))
@@ -1259,20 +1178,13 @@ class _XConvBn(torch.autograd.Function):
                                             _stream()), 'dvd_bnrelu_bwd')
         gx = gw = gcb = gg = None
         if need[0]:                 # (+ the other consumers' gradient) * [x > 0] for the site x came from
-            strided = dict(stride=-2, out_hw=(x.shape[2], x.shape[3])) if stride == 2 else {}
             gx = _xconv_bwd_data(ctx, g, g_amax, weight, groups, x if ctx.in_site is not None else None, g_alias,
-                                 bn_scale=(gamma, var, eps), **strided)
+                                 bn_scale=(gamma, var, eps), **_strided_bwd(stride, x))
         elif g_alias is not None:
             gx = g_alias
         if need_w:
-            gf = g
-            if stride == 2:                 # the zero-interleaved gradient for the stride-1 weight gradient kernels (see _XConvS2)
-                gf = torch.empty(N, Cout, wH, wW, device=g.device, dtype=g.dtype)
-                _lib.check(lib.dvd_subsample2_bwd(_p(g), _p(gf), int(h16), N * Cout, wH, wW, _stream()), 'dvd_subsample2_bwd')
-            if wgrad_sums and grouped3:
-                gw = xconv_wgrad3_rowsum(x, gf, weight.shape, groups, x_amax, g_amax, dbeta)
-            else:
-                gw = xconv_wgrad(x, gf, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if wgrad_sums else None)
+            gw = xconv_wgrad(x, g, weight.shape, False, groups, x_amax=x_amax, g_amax=g_amax, rowsum=dbeta if wgrad_sums else None,
+                             **_strided(stride))
             gg = torch.empty_like(gamma) if gamma is not None else None
             gcb = torch.empty_like(cbias) if cbias is not None else None
             _lib.check(lib.dvd_convbn_finalize(_p(weight.detach()), _p(gw), _p(dbeta), _p(gamma), _p(mean), _p(var), eps,
@@ -1346,101 +1258,166 @@ class _GConvBn(torch.autograd.Function):
         return gx, gw, gg, (dbeta if need[3] else None), None, None, None, None, None
 
 
-def _conv2_site_kind(conv, bn, x, residual, relu):
-    """Which fused site takes a ResNeXt `conv2` + BatchNorm + ReLU that xconv_supported does not cover -> 'c8' (8 per group:
-    csrc/gconv.hip), 'c16' (16 per group, stride 1: groups paired on the grouped xconv kernels), 's2' (3x3 / stride 2 on the
-    strided forms of xconv, stage 2's entry through the pairing) or None: conv(x) followed by bn_eval_relu.
-    fp32 storage only.  fp16 activations keep the composition: their passes move half the bytes, and the loss scale would have
-    to be threaded through dbeta and dvd_convbn_finalize first."""
+# ---- which kernels serve a convolution --------------------------------------------------------------------------------
+# family: 'xconv' (split-operand MFMA kernels, csrc/xconv.hip + csrc/xwgrad3.hip), 'gconv' (8 per group, csrc/gconv.hip),
+# 'gconv32' (the fp32 MFMA kernels of csrc/gconv32.hip, under DVD_AB=gconv32 only) or None (ATen); groups: what the kernels are
+# told; paired: the weight goes through _pair_groups_of_16; stride: the kernel's own (1, or 2: the native 3x3 / stride 2 forms);
+# subsample: None, 'out' (a strided 'same' 3x3 is the stride-1 result at [s*i][s*j]: the stride-1 kernel's output sub-sampled)
+# or 'in' (a strided 1x1 without padding: the 1x1 kernel on the sub-sampled input); plain: None, or the family that serves the
+# bare conv(x) in place of `family` -- kernels without epilogue operands, so everything that fuses (xconv2d, conv_bn_act) stays
+# on `family`.
+_Route = collections.namedtuple('_Route', 'family groups paired stride subsample plain')
+_ATEN = _Route(None, 1, False, 1, None, None)
+
+
+def _route(conv, x):
+    """The route of nn.Conv2d `conv` applied to x, from the layer's hyper-parameters, x's device / dtype / rank and the AB
+    switches -- and from nothing else: the module classes below, xconv2d and conv_bn_act all take it from here."""
+    k, st, g = conv.kernel_size, tuple(conv.stride), conv.groups
+    if not (x.is_cuda and x.dtype in ACT_DTYPES and x.dim() == 4 and conv.weight.dtype == torch.float32 and k[0] == k[1] and
+            st[0] == st[1] and tuple(conv.dilation) == (1, 1)):
+        return _ATEN
+    k, st, pad = k[0], st[0], tuple(conv.padding)
+    if k == 1 and st > 1:                   # the ResNeXt down-sampling shortcut
+        return _Route('xconv', 1, False, 1, 'in', None) if (g == 1 and pad == (0, 0)) else _ATEN
+    if not (k % 2 == 1 and k <= 11 and pad == (k // 2, k // 2) and conv.padding_mode == 'zeros'):
+        return _ATEN
+    cpg = conv.in_channels // g
+    square3 = k == 3 and conv.in_channels == conv.out_channels and conv.bias is None
+    conv2 = square3 and g > 1               # the shape of a ResNeXt bottleneck's `conv2`
+    if conv2 and cpg == 8:                  # stage 1
+        return _Route('gconv', g, False, 1, None, None) if st == 1 else _ATEN
+    # stage 2, 16 per group: two groups share one 32 x 32 tile of the grouped kernels with a block-diagonal weight (MIOpen's
+    # immediate mode runs this shape per image as im2col + small GEMMs, ~80 launches per call)
+    paired = conv2 and cpg == 16 and conv.in_channels % 32 == 0
+    if paired:
+        g, cpg = g // 2, 32
+    if (g > 1 and (k != 3 or cpg < 32)) or (st > 1 and k != 3):
+        return _ATEN
+    plain = None
+    if AB['gconv32'] and conv2 and cpg == 32:
+        # the legacy kernels are fp32 and stride 1: the bare forward of a 32-per-group layer; under the switch the pairing exists
+        # for them alone
+        legacy = st == 1 and x.dtype == torch.float32
+        if paired:
+            return _Route('gconv32', g, True, 1, None, None) if legacy else _ATEN
+        plain = 'gconv32' if legacy else None
+    if st == 1:
+        if square3 and conv.in_channels == 8:           # one group of 8: GroupedConv3x3C8(8)'s forward is the 8-per-group kernels'
+            plain = 'gconv'
+        return _Route('xconv', g, paired, 1, None, plain)
+    # the strided forms need whole 16-channel chunks per group (the buffer-addressed main loop); DVD_AB=no_s2, other strides and
+    # other channel counts: 4x (s^2 x) the needed work at stride 1, still half of MIOpen's per-image im2col + GEMM + col2im path
+    if st == 2 and not AB['no_s2'] and cpg % 16 == 0 and (conv.out_channels // g) % 16 == 0:
+        return _Route('xconv', g, paired, 2, None, None)
+    return _Route('xconv', g, paired, 1, 'out', None)
+
+
+def _xconv_s1(r):
+    """Does the stride-1 xconv kernel take the layer's own weight at x's resolution -- the form that has every epilogue operand
+    (input ReLU, residual, BatchNorm, alias)?"""
+    return r.family == 'xconv' and not r.paired and r.stride == 1 and r.subsample is None
+
+
+def _route_weight(r, conv):
+    """The weight the route's kernels take.  The paired one is a tensor derived per call: it has no PACK_PLAN entry, so its
+    packings (the scaled transposed one included) are launched with the pass, inside a captured graph too, and follow the
+    parameters on every replay."""
+    return _pair_groups_of_16(conv.weight) if r.paired else conv.weight
+
+
+def _routed(r, conv, x):
+    """conv(x) on route r."""
+    family = r.plain or r.family
+    if family is None:
+        return nn.Conv2d.forward(conv, x)
+    if family == 'gconv':
+        return _GConv3x3C8.apply(x, conv.weight)
+    if family == 'gconv32':
+        return _GConv3x3C32.apply(x, _route_weight(r, conv))
+    if r.subsample == 'in':
+        x = _subsample(x, conv.stride[0])
+    y = _xconv(x, _route_weight(r, conv), conv.bias, None, False, False, r.groups, stride=r.stride)
+    return _subsample(y, conv.stride[0]) if r.subsample == 'out' else y
+
+
+def _bn_site(r, conv, bn, x, residual, relu):
+    """Which fused site takes `conv` on route r followed by BatchNorm `bn` (+ residual, + ReLU) -> 'xconv' (the stride-1 kernel,
+    also on the sub-sampled input of a strided 1x1: fp32 and fp16, any epilogue), or one of the ResNeXt `conv2` kinds 'c8'
+    (_GConvBn), 'c16' (paired groups) and 's2' (the native stride-2 forms), or None: conv(x) followed by bn_eval_relu.
+    The `conv2` kinds are fp32 ReLU sites without residual.  fp16 activations keep the composition there: their passes move half
+    the bytes, and the loss scale would have to be threaded through dbeta and dvd_convbn_finalize first."""
+    if r.family is None or bn.training or not bn.track_running_stats:
+        return None
+    if _xconv_s1(r) or r.subsample == 'in':
+        return 'xconv'
     if not (x.dtype == torch.float32 and relu and residual is None and bn.affine and conv.bias is None and
-            conv.weight.dtype == torch.float32 and conv.kernel_size == (3, 3) and tuple(conv.padding) == (1, 1) and
-            tuple(conv.dilation) == (1, 1) and conv.padding_mode == 'zeros' and x.dim() == 4):
+            (conv.groups == 1 or conv.in_channels == conv.out_channels)):
         return None
-    cpg, st = conv.in_channels // conv.groups, tuple(conv.stride)
-    if conv.in_channels != conv.out_channels and conv.groups > 1:
-        return None
-    if st == (1, 1):
-        if cpg == 8 and conv.groups > 1:
-            return 'c8'
-        if cpg == 16 and conv.groups > 1 and conv.in_channels % 32 == 0 and not AB['gconv32']:
-            return 'c16'
-        return None
-    if st == (2, 2) and not AB['no_s2']:
-        if cpg == 16 and conv.groups > 1:
-            return 's2' if (conv.in_channels % 32 == 0 and not AB['gconv32']) else None
-        if xconv_s2_supported(x, conv.weight, conv.groups):
-            return 's2'
+    if r.family == 'gconv':
+        return 'c8'
+    if r.family == 'xconv' and r.subsample is None:
+        return 's2' if r.stride == 2 else 'c16'
     return None
 
 
 def conv_bn_act(conv, bn, x, residual=None, relu=True, alias=False):
-    """relu(bn(conv(x)) (+ residual)) for an nn.Conv2d followed by an eval-mode nn.BatchNorm2d.  Convolutions the xconv
-    kernels cover run as ONE launch (BatchNorm, residual and ReLU in the epilogue), and so do, for fp32 tensors, the ResNeXt
-    `conv2` layers outside that family: 8 and 16 channels per group and the 3x3 / stride 2 entries (_conv2_site_kind);
-    everything else (CPU tensors, training-mode statistics, those `conv2` layers with fp16 activations) is conv(x) followed by
-    the fused BatchNorm+ReLU kernel / the ATen ops.
+    """relu(bn(conv(x)) (+ residual)) for an nn.Conv2d followed by an eval-mode nn.BatchNorm2d.  Convolutions the stride-1 xconv
+    kernel covers run as ONE launch (BatchNorm, residual and ReLU in the epilogue), and so do, for fp32 tensors, the ResNeXt
+    `conv2` layers outside that form: 8 and 16 channels per group and the 3x3 / stride 2 entries (_bn_site); everything else
+    (CPU tensors, training-mode statistics, those `conv2` layers with fp16 activations) is conv(x) followed by the fused
+    BatchNorm+ReLU kernel / the ATen ops.
     alias=True returns (y, x'): x' carries x's values and must be used by every OTHER consumer of x (the block's shortcut);
-    on the fused path their gradient is then added inside this convolution's backward-data kernel instead of by autograd's
+    on the 'xconv' site their gradient is then added inside this convolution's backward-data kernel instead of by autograd's
     accumulation pass (see _XConv); on the other paths x' is x itself."""
-    if x.is_cuda and x.dtype in ACT_DTYPES and not bn.training and bn.track_running_stats and isinstance(conv, nn.Conv2d):
-        xin = None
-        if xconv_supported(conv, x):
-            xin = x
-        elif xconv_strided_1x1_supported(conv, x):
-            xin = _subsample(x, conv.stride[0])
-        if xin is not None:
-            gamma, beta = (bn.weight, bn.bias) if bn.affine else (None, None)
-            x_amax = None if _is16(xin) else amax_of(xin)
-            in_site = getattr(xin, '_dvd_site', None)           # xin is a BatchNorm+ReLU site's output (see _Site)
-            out_site = _Site() if relu else None
-            out = _XConvBn.apply(xin, x_amax, conv.weight, conv.bias, gamma, beta, bn.running_mean, bn.running_var, bn.eps,
-                                 residual, relu, conv.groups, bool(alias and xin is x and not AB['no_alias']), in_site, out_site)
-            out[0]._dvd_site = out_site
-            y = set_amax(out[0], out[1])
-            if len(out) == 3:
-                return y, set_amax(out[2], x_amax)
-            return (y, x) if alias else y
-        kind = _conv2_site_kind(conv, bn, x, residual, relu)
-        if kind is not None:
-            in_site, out_site = getattr(x, '_dvd_site', None), _Site()
-            stats = (bn.running_mean, bn.running_var, bn.eps)
-            if kind == 'c8':
-                y, y_amax = _GConvBn.apply(x, conv.weight, bn.weight, bn.bias, *stats, in_site, out_site)
-            else:
-                # 16 per group: two groups share a 32-channel block of the grouped kernels (see GroupedConv3x3C16).  The paired
-                # weight is a tensor derived per call: it has no PACK_PLAN entry, so its packings (the scaled transposed one
-                # included) are launched with the pass, inside a captured graph too, and follow the parameters on every replay
-                w, groups = conv.weight, conv.groups
-                if w.shape[1] == 16:
-                    w, groups = _pair_groups_of_16(w), groups // 2
-                y, y_amax = _XConvBn.apply(x, amax_of(x), w, None, bn.weight, bn.bias, *stats, None, True, groups, False, in_site,
-                                           out_site, 2 if kind == 's2' else 1)
-            y._dvd_site = out_site
-            y = set_amax(y, y_amax)
-            return (y, x) if alias else y
-    y = bn_eval_relu(bn, conv(x), residual=residual, relu=relu)
+    r = _route(conv, x) if isinstance(conv, nn.Conv2d) else _ATEN
+    kind = _bn_site(r, conv, bn, x, residual, relu)
+    if kind is None:
+        y = bn_eval_relu(bn, conv(x), residual=residual, relu=relu)
+        return (y, x) if alias else y
+    stats = (bn.running_mean, bn.running_var, bn.eps)
+    out_site = _Site() if relu else None
+    if kind == 'c8':
+        out = _GConvBn.apply(x, conv.weight, bn.weight, bn.bias, *stats, getattr(x, '_dvd_site', None), out_site)
+    else:
+        xin = _subsample(x, conv.stride[0]) if r.subsample == 'in' else x
+        gamma, beta = (bn.weight, bn.bias) if bn.affine else (None, None)
+        x_amax = None if _is16(xin) else amax_of(xin)
+        join = bool(kind == 'xconv' and alias and xin is x and not AB['no_alias'])
+        # (xin may be a BatchNorm+ReLU site's output, see _Site)
+        out = _XConvBn.apply(xin, x_amax, _route_weight(r, conv), conv.bias, gamma, beta, *stats, residual, relu, r.groups, join,
+                             getattr(xin, '_dvd_site', None), out_site, r.stride)
+    out[0]._dvd_site = out_site
+    y = set_amax(out[0], out[1])
+    if len(out) == 3:
+        return y, set_amax(out[2], x_amax)
     return (y, x) if alias else y
 
 
+def _conv2_site_kind(conv, bn, x, residual, relu):
+    """_bn_site's answer where it is one of the `conv2` kinds ('c8', 'c16', 's2'), else None."""
+    kind = _bn_site(_route(conv, x), conv, bn, x, residual, relu)
+    return None if kind == 'xconv' else kind
+
+
 def xconv_supported(conv, x):
-    k = conv.kernel_size
-    return (x.is_cuda and x.dtype in ACT_DTYPES and conv.weight.dtype == torch.float32 and
-            (conv.groups == 1 or (k[0] == 3 and conv.in_channels // conv.groups >= 32)) and
-            k[0] == k[1] and k[0] % 2 == 1 and k[0] <= 11 and tuple(conv.stride) == (1, 1) and
-            tuple(conv.dilation) == (1, 1) and tuple(conv.padding) == (k[0] // 2, k[0] // 2) and
-            conv.padding_mode == 'zeros')
+    return _xconv_s1(_route(conv, x))
+
+
+def xconv_s2_supported(conv, x):
+    """3x3 / stride 2 / padding 1 on the strided forms of csrc/xconv.hip?"""
+    r = _route(conv, x)
+    return r.family == 'xconv' and r.stride == 2
 
 
 def xconv_strided_1x1_supported(conv, x):
-    """A dense strided 1x1 convolution without padding (the ResNeXt down-sampling shortcut): the 1x1 kernel on the sub-sampled
-    input, `_subsample(x, conv.stride[0])`."""
-    return (x.is_cuda and x.dtype in ACT_DTYPES and conv.weight.dtype == torch.float32 and conv.kernel_size == (1, 1) and
-            conv.groups == 1 and tuple(conv.padding) == (0, 0) and conv.stride[0] == conv.stride[1] and conv.stride[0] > 1)
+    """A dense strided 1x1 convolution without padding: the 1x1 kernel on the sub-sampled input?"""
+    return _route(conv, x).subsample == 'in'
 
 
 def xconv2d(conv, x, relu_in=False, residual=None, res_relu=False, alias=False, res_unmasked=False):
     """`conv(relu(x) if relu_in else x) + (relu(residual) if res_relu else residual)` for an nn.Conv2d `conv`.
-    GPU fp32 tensors of a dense stride-1 'same' convolution run on the HIP kernels; CPU tensors (the oracle /
+    GPU fp32 / fp16 tensors of a stride-1 'same' convolution the xconv kernel covers run as one launch; CPU tensors (the oracle /
     golden-fixture generator instantiates these modules on the CPU) take the ATen ops the reference uses."""
     if xconv_supported(conv, x):
         if AB['no_alias']:
@@ -1456,24 +1433,40 @@ def xconv2d(conv, x, relu_in=False, residual=None, res_relu=False, alias=False, 
 
 
 class XConv2d(nn.Conv2d):
-    """Drop-in nn.Conv2d (same parameters / state_dict keys) whose stride-1 'same' case (dense, or grouped 3x3 with
-    at least 32 channels per group) runs on the HIP kernels; a strided 1x1 convolution without padding (the ResNeXt
-    down-sampling shortcut) is the 1x1 kernel on the sub-sampled input, a stride-2 3x3 'same' convolution runs on the strided
-    forms of the kernel (_XConvS2, round 6; other strides, and DVD_AB=no_s2: the stride-1 kernel's output sub-sampled).
-    Anything else, and CPU tensors, take ATen."""
+    """Drop-in nn.Conv2d (same parameters / state_dict keys) that runs on the HIP kernels wherever _route finds a family for
+    the layer and the tensor: stride-1 'same' convolutions (dense, or grouped 3x3 with 8, 16 or at least 32 channels per
+    group), 3x3 'same' convolutions of stride 2 (the strided forms of the kernel) and of other strides (the stride-1 kernel's
+    output sub-sampled), and the strided 1x1 without padding (the ResNeXt down-sampling shortcut).  Anything else, and CPU
+    tensors, take ATen."""
 
     def forward(self, x):
-        if xconv_supported(self, x):
-            return _xconv(x, self.weight, self.bias, None, False, False, self.groups)
-        k, st = self.kernel_size, self.stride
-        if (x.is_cuda and x.dtype in ACT_DTYPES and k == (3, 3) and st[0] == st[1] and st[0] > 1 and
-                tuple(self.padding) == (1, 1) and tuple(self.dilation) == (1, 1) and
-                (self.groups == 1 or self.in_channels // self.groups >= 32)):
-            if st[0] == 2 and xconv_s2_supported(x, self.weight, self.groups):
-                return _xconv_s2(x, self.weight, self.bias, self.groups)
-            # out[i][j] of a stride-s 'same' 3x3 convolution is out1[s*i][s*j] of the stride-1 one
-            y = _xconv(x, self.weight, self.bias, None, False, False, self.groups)
-            return _subsample(y, st[0])
-        if xconv_strided_1x1_supported(self, x):
-            return _xconv(_subsample(x, st[0]), self.weight, self.bias, None, False, False)
-        return super().forward(x)
+        return _routed(_route(self, x), self, x)
+
+
+class GroupedConv3x3C8(XConv2d):
+    """nn.Conv2d(C, C, 3, stride=1, padding=1, groups=C // 8, bias=False): the `conv2` of the ResNeXt-101 32x8d stage-1 bottlenecks."""
+
+    def __init__(self, channels):
+        if channels % 8:
+            raise ValueError('GroupedConv3x3C8 needs a multiple of 8 channels')
+        super().__init__(channels, channels, 3, stride=1, padding=1, groups=channels // 8, bias=False)
+
+
+class GroupedConv3x3C16(XConv2d):
+    """nn.Conv2d(C, C, 3, stride=stride, padding=1, groups=C // 16, bias=False) (ResNeXt stage 2)."""
+
+    def __init__(self, channels, stride=1):
+        if channels % 32:
+            raise ValueError('GroupedConv3x3C16 needs a multiple of 32 channels')
+        super().__init__(channels, channels, 3, stride=stride, padding=1, groups=channels // 16, bias=False)
+
+
+class GroupedConv3x3C32(XConv2d):
+    """nn.Conv2d(C, C, 3, stride=1, padding=1, groups=C // 32, bias=False) (ResNeXt stages 3 and 4): on the grouped xconv kernels,
+    0.097 ms forward / 0.37 ms backward per 16-image call at [1024, 24, 42] against 0.156 / 0.42 ms of the fp32-MFMA kernels
+    (tools/microbench_gx.py)."""
+
+    def __init__(self, channels):
+        if channels % 32:
+            raise ValueError('GroupedConv3x3C32 needs a multiple of 32 channels')
+        super().__init__(channels, channels, 3, stride=1, padding=1, groups=channels // 32, bias=False)

@@ -127,3 +127,38 @@ def test_c16_pairs_groups_on_the_mfma_kernels():
     for name, got, want, tol in (('y', y, yr, 2e-5), ('gx', xg.grad, xr.grad, 2e-5), ('gw', mg.weight.grad, want_gw, 5e-5)):
         a, b = got.detach().cpu().numpy(), want.detach().numpy()
         assert np.abs(a - b).max() <= tol * np.abs(b).max() + 1e-6, name
+
+
+@pytest.mark.parametrize('half', [False, True])
+@pytest.mark.parametrize('cpg,stride', [(16, 1), (16, 2), (8, 1)])
+def test_an_xconv2d_of_the_same_hyper_parameters_takes_the_same_route(cpg, stride, half):
+    """The route depends on the layer's hyper-parameters, not on its class: an XConv2d with 16 (8) channels per group runs the
+    kernels GroupedConv3x3C16 (GroupedConv3x3C8) runs, on the same packed bytes in the same order -- output, input gradient and
+    weight gradient are the same bits.  5 x 7 pixels: every tile is an edge tile."""
+    from dvd_hip import conv as C, ops
+    ch = 64 if cpg == 16 else 16
+    a = C.XConv2d(ch, ch, 3, stride=stride, padding=1, groups=ch // cpg, bias=False).cuda()
+    b = (C.GroupedConv3x3C16(ch, stride=stride) if cpg == 16 else C.GroupedConv3x3C8(ch)).cuda()
+    g = torch.Generator().manual_seed(300 + cpg + stride)
+    with torch.no_grad():
+        a.weight.copy_(torch.randn(a.weight.shape, generator=g) / 12.0)
+        b.weight.copy_(a.weight)
+    dtype = torch.float16 if half else torch.float32
+    x = torch.randn(1, ch, 5, 7, generator=g).cuda().to(dtype)
+    gy = torch.randn(1, ch, (5 + stride - 1) // stride, (7 + stride - 1) // stride, generator=g).cuda().to(dtype)
+    got = []
+    try:
+        for m in (a, b):
+            C.set_grad_scale_state(ops.gscale_new(x.device) if half else None)
+            xm = x.clone().requires_grad_(True)
+            y = m(xm)
+            y.backward(gy)
+            fn = type(y.grad_fn).__name__                       # the HIP kernels' Function, not ATen's convolution
+            assert y.dtype == dtype and ('_XConv' in fn or '_GConv3x3C8' in fn), fn
+            got.append((y.detach(), xm.grad, m.weight.grad))
+    finally:
+        C.set_grad_scale_state(None)
+    torch.cuda.synchronize()
+    for name, p, q in zip(('y', 'gx', 'gw'), *got):
+        assert torch.isfinite(p.float()).all() and float(p.float().abs().max()) > 0.0, name
+        assert torch.equal(p, q), name

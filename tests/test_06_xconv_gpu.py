@@ -268,7 +268,7 @@ def test_sixteen_per_group_module_incl_stride_two(stride):
 
 
 def test_stride_two_is_the_subsampled_stride_one_result():
-    """The strided kernels (csrc/xconv.hip XArgs::S2 / ZI, conv._XConvS2) against rounds 2-5's form of the same convolution:
+    """The strided kernels (csrc/xconv.hip XArgs::S2 / ZI, conv._XConv with stride=2) against rounds 2-5's form of the same convolution:
     the stride-1 kernel's output sub-sampled, the gradient zero-interleaved in HBM.  Same products, same split operands (the
     tensor-wide scales are shared), another accumulation order per output: 2e-6 of the largest element; the module with a
     bias, in front of a BatchNorm+ReLU site's input (the mask hand-over of conv._Site)."""
@@ -294,7 +294,9 @@ def test_stride_two_is_the_subsampled_stride_one_result():
                 for n, _ in fn.next_functions:
                     walk(n, depth + 1)
             walk(y.grad_fn)
-            assert any('XConvS2' in n for n in names) == (not off), names
+            # native: the strided kernel's own output; DVD_AB=no_s2: the stride-1 kernel's through _Subsample2
+            assert C.xconv_s2_supported(mod, xg) == (not off)
+            assert (type(y.grad_fn).__name__ == '_XConvBackward') == (not off) and any('Subsample2' in n for n in names) == off, names
             y.backward(gy)
             outs.append((y.detach().clone(), xg.grad.clone(), mod.weight.grad.clone(), mod.bias.grad.clone()))
         finally:

@@ -139,8 +139,8 @@ def test_against_float64(N, Cin, Cout, H, W, k, groups, stride):
     cg = conv.cuda()
     xg = x.cuda().requires_grad_(True)
     if stride == 2:
-        assert C.xconv_s2_supported(xg, cg.weight, groups)
-        y = C._xconv_s2(xg, cg.weight, cg.bias, groups)
+        assert C.xconv_s2_supported(cg, xg)
+        y = C._xconv(xg, cg.weight, cg.bias, None, False, False, groups, stride=2)
     else:
         assert C.xconv_supported(cg, xg)
         y = C.xconv2d(cg, xg)

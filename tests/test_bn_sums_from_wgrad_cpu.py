@@ -3,7 +3,7 @@ applied the ReLU mask runs NO pass of its own over the gradient -- the per-chann
 call (dvd_xwgrad1s_rowsum for the dense 1x1, dvd_xwgrad3_rowsum for the grouped 3x3 convolutions of torchvision's Bottleneck
 behind third_party/midas_blocks.py:35-50), max|g| from the consumer's epilogue -- and a site that masks for itself takes its
 sums from the same call.  The library is a stand-in that computes every entry point's contract in float64 and records the
-calls; conv.xconv_wgrad and conv.xconv_wgrad3_rowsum themselves run.  The gradients are compared with autograd on the float64
+calls; conv.xconv_wgrad itself runs.  The gradients are compared with autograd on the float64
 ATen expression: the stand-ins round their results to the fp32 tensors they are handed, so 1e-5 of the value (+ 1e-6) -- a
 wiring error is an O(1) difference.  The kernels: tests/test_40_wgrad_rowsum_gpu.py."""
 import pytest
@@ -166,7 +166,7 @@ def test_premasked_sites_take_their_sums_from_the_weight_gradient_call(stand_in,
 
     passes = [kw for n, kw in lib.calls if n.startswith('dvd_bnrelu_bwd')]
     assert passes == ([] if consumed else [{'relu': True}]), passes
-    # both sites hand dbeta to their weight-gradient call, the grouped one through the helper's entry point
+    # both sites hand dbeta to their weight-gradient call, the grouped one through the 3x3 entry point that sums
     assert ('dvd_xwgrad1s_rowsum', {'rowsum': True}) in lib.calls and ('dvd_xwgrad3_rowsum', {'rowsum': True}) in lib.calls
     assert 'dvd_xwgrad3' not in lib.names()
     assert C.STATS == {'sites_premasked': 1 + consumed, 'sites_masked': 1 - consumed, 'sites_no_pass': 0}, C.STATS

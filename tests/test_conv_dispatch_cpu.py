@@ -81,10 +81,11 @@ def test_wgrad_dispatch_fp32(recording, ks, groups, name32, name16, extra, relu_
     C, lib, state = recording
     rowsum = torch.zeros(64)
     name, args = _wgrad(C, lib, ks, groups, torch.float32, relu_in, rowsum=rowsum)
-    assert name == name32
+    # a 3x3 with a sums tensor takes the entry point that fills it (and only then: the second call below)
+    assert name == ('dvd_xwgrad3_rowsum' if ks == 3 else name32)
     assert _ints(args) == [1, 64, 64, 4, 4] + extra + [int(relu_in)]
-    # the per-channel sums go to the dense 1x1 launch and to no other
-    assert any(a is rowsum for a in args) == (ks == 1)
+    # the per-channel sums go to the 1x1 and 3x3 launches and to no other
+    assert any(a is rowsum for a in args) == (ks in (1, 3))
     # no fp32 form takes the loss-scale state
     gs = C.GRAD_SCALE['state']
     assert not any(torch.is_tensor(a) and a.numel() == 1 and a.data_ptr() == gs.data_ptr() + 4 for a in args)
