@@ -48,7 +48,7 @@ __device__ __forceinline__ bool tile_exclusive(int wx, int wy) {
 }
 
 // g_depth_2[b,y,x .. x+3] = sum over the tiles whose window covers the quad, fixed order (dj outer, di inner): the ONE
-// definition of the combine, used by combine_slabs_kernel and by the in-kernel combine of the tile kernel.
+// definition of the combine; combine_tiles_kernel takes it for pairs whose windows are shifted.
 template <int TW, int TH, int R>
 __device__ __forceinline__ void combine_quad(const float* __restrict__ slabs, int2 off, float* __restrict__ g_d2, int H, int W,
                                              int ntx, int nty, int b, int y, int x, int direct) {
@@ -131,15 +131,15 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
   Cam& c = c0;
   // pinhole intrinsics without skew (exact zeros / one in K^T and (K^-1)^T): block-uniform, selects pixel<.., PIN = true>
   const bool pinhole = c.Ki[1] == 0.0f && c.Ki[2] == 0.0f && c.Ki[3] == 0.0f && c.Ki[5] == 0.0f && c.Ki[8] == 1.0f &&
-                       c.K[1] == 0.0f && c.K[2] == 0.0f && c.K[3] == 0.0f && c.K[5] == 0.0f && c.K[8] == 1.0f &&
-                       DVD_WARP_PINHOLE;
+                       c.K[1] == 0.0f && c.K[2] == 0.0f && c.K[3] == 0.0f && c.K[5] == 0.0f && c.K[8] == 1.0f;
   // The 51 camera scalars are wave-uniform; left alone they all land in SGPRs and push the
   // kernel past the 102-SGPR file (hundreds of v_readlane spill reloads).  Pin the three
   // matrices used mostly by the FMA-heavy parts into VGPRs instead.
   // (Round 5: the lockstep loop halves the uses per pixel and needs the VGPRs for two pixels' live values, so its
   //  instantiations keep the camera in SGPRs -- a packed instruction takes one SGPR pair as an operand; the pinhole
-  //  form needs 41 of the 51 scalars.  DVD_WARP_CAM_VGPR selects matrices to pin for A/B builds.)
-  constexpr int kCamV = (PX == 2 && SHIPPED && DVD_WARP_V5) ? DVD_WARP_CAM_VGPR : 15;
+  //  form needs 41 of the 51 scalars.)
+  constexpr bool kLockstep = PX == 2 && SHIPPED;      // this instantiation has the two-pixel lockstep loop
+  constexpr int kCamV = kLockstep ? 0 : 15;           // bit mask of the matrices pinned: 1 R1, 2 R2, 4 K, 8 R2T
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     if (kCamV & 1) asm volatile("" : "+v"(c.R1[i]));
@@ -156,9 +156,9 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
     x = tx0 + lx;
     return (q < QW * TH) && (y < a.H) && (x < a.W);
   };
-  // ---- lockstep loop (round 5): per-pair input pointers.  DVD_WARP_V5_EARLY = 1 requests the FIRST thread-step's inputs
-  //      before the window fill (their latency under the fill and the barrier): measured 231 us against 223 us for the
-  //      launch sequence -- the requests queue in front of the window's and the registers they hold cost more; off.
+  // ---- lockstep loop (round 5): per-pair input pointers.  The first thread-step's inputs are requested AFTER the window
+  //      fill: requested before it (their latency under the fill and the barrier) the launch sequence took 231 us against
+  //      223 us -- the requests queue in front of the window's and the registers they hold cost more.
   struct In2 {
     v2f d1, mk, s0, s1, s2;
     float4 fl;
@@ -188,10 +188,6 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
     r.s2 = *reinterpret_cast<const v2f*>(sfb0 + (o + 2u * plane));
     return r;
   };
-  In2 first = {};
-  if constexpr (PX == 2 && SHIPPED && DVD_WARP_V5 && DVD_WARP_V5_EARLY) {
-    if (wv) first = fetch2(threadIdx.x);
-  }
 
   // ---- phase 0: fill the depth_2 window, clear the accumulator.  All of a thread's window loads are
   //      requested before the first one is consumed (the trip count is a compile-time constant).
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
       const int wy = i / (WW / 4), wx = (i - wy * (WW / 4)) * 4;
       const int iy = wy0 + wy, ixx = wx0 + wx;
       v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i < kCells && iy >= 0 && iy < a.H && !DVD_WARP_KO_FILL) {
+      if (i < kCells && iy >= 0 && iy < a.H) {
         if (w4) {
           if (ixx >= 0 && ixx < a.W) v[it] = *reinterpret_cast<const float4*>(d2b + (size_t)iy * a.W + ixx);
         } else {
@@ -233,7 +229,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
     }
   }
   if (threadIdx.x == 0) *lcount = 0u;
-  if constexpr (PX == 2 && SHIPPED && DVD_WARP_V5) {
+  if constexpr (kLockstep) {
     if (threadIdx.x < kCamLdsFloats) {
       float v = 0.0f;
 #pragma unroll
@@ -245,10 +241,9 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
 
   TileIO<WW, WH> io{d2b, win, accw, a.W, wx0, wy0, b * a.HW, logical, a.disp_mul, ta.ovf, lcount};
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  // ---- phase 1: the tile's pixels, PX per thread per step.  The inputs of step i+1 are requested before
-  //      step i is evaluated: all waves of a block leave the barrier together, so without this every
-  //      load latency of the block is exposed at the same time.  Build-time switch DVD_WARP_PREFETCH, off by
-  //      default: measured 297 us with it (the 14 extra live registers spill) against 259 us without
+  // ---- phase 1: the tile's pixels, PX per thread per step.  The inputs of step i+1 are requested after step i is
+  //      evaluated; requested before it (so that not every load latency of the block is exposed at the same time, all
+  //      waves leaving the barrier together) the kernel took 297 us against 259: the 14 extra live registers spill.
   struct In {
     float d1[PX], mk[PX], fl[2 * PX], s0[PX], s1[PX], s2[PX];
   };
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
   // rows): it reads the camera AGAIN instead of keeping the 51 scalars of the prologue alive across the window fill -- they
   // pushed the whole kernel over its register budget (spills in the prologue and in the flush loop of every tile).
   Cam c;
-  if constexpr (PX == 2 && SHIPPED && DVD_WARP_V5) {
+  if constexpr (kLockstep) {
     load_cam(a, b, c);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {                 // (as in the other instantiations: the FMA-heavy matrices in VGPRs)
@@ -299,10 +294,9 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
   } else {
     c = c0;
   }
-  In cur, nxt;
+  In cur;
   fetch(threadIdx.x, cur);
   for (int q = threadIdx.x; q < QW * TH; q += NT) {
-    if (DVD_WARP_PREFETCH) fetch(q + NT, nxt);
     int x, y;
     if (locate(q, x, y)) {
       const int p0 = y * a.W + x;
@@ -337,19 +331,20 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
         }
       }
     }
-    if (DVD_WARP_PREFETCH)
-      cur = nxt;
-    else
-      fetch(q + NT, cur);
+    fetch(q + NT, cur);
   }
   };
   // ---- the lockstep loop (round 5): shipped flag set, pinhole pair, rows of whole pixel pairs
-  auto tile_pixels2 = [&](auto crit_tag, const In2 first) {
+  auto tile_pixels2 = [&](auto crit_tag) {
     constexpr bool CRIT = decltype(crit_tag)::value;
     // (wave-uniform values computed on the vector unit: back into scalar registers, they are loop invariant)
     const float yhw = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rcp_refined(a.half_w))));
     const float yhh = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rcp_refined(a.half_h))));
-    In2 cur = DVD_WARP_V5_EARLY ? first : fetch2(threadIdx.x), nxt = cur;
+    // Nothing happens between the phases of a thread-step here: the next thread-step's inputs requested there (what the strip
+    // kernel does) cost 159.7 us against 156.1.  `nxt` and the statement that never runs are what is left of that form: the
+    // callable has to name a second input set, or these four instantiations leave the register allocator with other
+    // registers (and 64 x 48 with 16 bytes more scratch) than the code that was measured.
+    In2 cur = fetch2(threadIdx.x), nxt = cur;
     for (int q = threadIdx.x; q < QW * TH; q += NT) {
       int x, y;
       if (locate(q, x, y)) {
@@ -357,7 +352,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
         pixel2<GRADS, CRIT>(a, camL, io, y, x, cur.d1, (v2f){cur.fl.x, cur.fl.z}, (v2f){cur.fl.y, cur.fl.w}, cur.mk, cur.s0,
                             cur.s1, cur.s2, yhw, yhh, acc,
                             [&]() {
-                              if (DVD_WARP_V5_PREFETCH) nxt = fetch2(q + NT);
+                              if (false) nxt = fetch2(q + NT);
                             },
                             [&](v2f gd1, v2f g0, v2f g1, v2f g2) {
                               *reinterpret_cast<v2f*>(gd1b + o) = gd1;
@@ -365,16 +360,11 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
                               *reinterpret_cast<v2f*>(gsb0 + (o + plane)) = g1;
                               *reinterpret_cast<v2f*>(gsb0 + (o + 2u * plane)) = g2;
                             });
-      } else if (DVD_WARP_V5_PREFETCH) {
-        nxt = fetch2(q + NT);
       }
-      if (DVD_WARP_V5_PREFETCH)
-        cur = nxt;
-      else
-        cur = fetch2(q + NT);
+      cur = fetch2(q + NT);
     }
   };
-  if constexpr (PX == 2 && SHIPPED && DVD_WARP_V5) {
+  if constexpr (kLockstep) {
     // (a pinhole pair with odd-width rows takes the general instantiation: correct for every camera)
     bool r2t = true;            // R_2 and R_2_T are each other's transposes, bit for bit (wave-uniform)
 #pragma unroll
@@ -383,13 +373,11 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
       for (int j = 0; j < 3; ++j) r2t = r2t && (c.R2[3 * i + j] == c.R2T[3 * j + i]);
     if (pinhole && wv && r2t) {
       if (a.crit_l2)
-        tile_pixels2(std::true_type{}, first);
+        tile_pixels2(std::true_type{});
       else
-        tile_pixels2(std::false_type{}, first);
+        tile_pixels2(std::false_type{});
     } else {
-#ifndef DVD_WARP_NO_GENERAL
       tile_pixels(std::false_type{});
-#endif
     }
   } else {
     if (pinhole)
@@ -404,7 +392,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
     float* slab = ta.slabs + (size_t)logical * (WW * WH);
     float* gb = a.g_d2 + (size_t)b * a.HW;
     const float back = a.disp_mul;
-    for (int i = threadIdx.x; i < (WW * WH) / 4 && !DVD_WARP_KO_FLUSH; i += NT) {
+    for (int i = threadIdx.x; i < (WW * WH) / 4; i += NT) {
       const longlong2 lo = reinterpret_cast<const longlong2*>(accw)[2 * i];
       const longlong2 hi = reinterpret_cast<const longlong2*>(accw)[2 * i + 1];
       const float4 v = make_float4(from_fixed(lo.x) * back, from_fixed(lo.y) * back, from_fixed(hi.x) * back, from_fixed(hi.y) * back);
@@ -432,20 +420,7 @@ __global__ __launch_bounds__(NT, tile_waves_per_simd(TW, TH, R, NT)) void warp_l
   }
 }
 
-template <int TW, int TH, int R>
-__global__ __launch_bounds__(256) void combine_slabs_kernel(const float* __restrict__ slabs, const int2* __restrict__ offs,
-                                                            float* __restrict__ g_d2, int H, int W, int ntx,
-                                                            int nty, int total_quads, int direct, int b0) {
-  const int qid = blockIdx.x * 256 + threadIdx.x;
-  if (qid >= total_quads) return;
-  const int qpr = (W + 3) >> 2;  // quads per row
-  const int row = qid / qpr;
-  const int x = (qid - row * qpr) * 4;
-  const int b = b0 + row / H, y = row - (row / H) * H;      // this launch covers the pairs b0 ...
-  combine_quad<TW, TH, R>(slabs, offs[b], g_d2, H, W, ntx, nty, b, y, x, direct);
-}
-
-// Round 5: the combine with one block per TILE.  The round-4 kernel above ran one thread per quad of every pixel: 37 % of its
+// Round 5: the combine with one block per TILE.  The round-4 kernel ran one thread per quad of every pixel: 37 % of its
 // lanes belonged to quads the tile kernel had already written (exclusive cells) and left at once, every wave first waited
 // for its pair's window offset, and a thread had at most four 16-byte loads in flight -- 35 us for 122 MB (3.5 TB/s).  Here a
 // block owns one tile of the pair's (unshifted) tile grid; for a pair whose windows are not shifted (mean flow below 4 px:
@@ -498,7 +473,7 @@ __global__ __launch_bounds__(256) void combine_tiles_kernel(const float* __restr
     const int di = hx < R + 4 ? -1 : (hx >= TW - R ? 1 : 0);
     const bool okj = dj != 0 && (unsigned)(tj + dj) < (unsigned)nty, oki = di != 0 && (unsigned)(ti + di) < (unsigned)ntx;
     // window coordinates of the quad in tile (ti + a, tj + c): wx = hx + R - a TW, wy = hy + R - c TH.  A window that does
-    // not cover the quad is read at the own window's address instead and multiplied by 0: no branch around a load
+    // not cover the quad gets the own window's address (always valid) and its load is masked off below
     const float* p_own = tile_slab + (hy + R) * WW + (hx + R);
     const float* p_hor = oki ? p_own + (ptrdiff_t)di * (WW * WH) - di * TW : p_own;
     const float* p_ver = okj ? p_own + (ptrdiff_t)dj * ntx * (WW * WH) - dj * TH * WW : p_own;
@@ -506,19 +481,10 @@ __global__ __launch_bounds__(256) void combine_tiles_kernel(const float* __restr
     // (ext-vector values: a select between two HIP float4 STRUCTS goes through the stack)
     const v4f zero = {0.f, 0.f, 0.f, 0.f};
     const v4f own = *reinterpret_cast<const v4f*>(p_own);
-#if DVD_WARP_COMBINE_MASKED
     v4f hor = zero, ver = zero, dia = zero;            // lane-masked loads: only the windows that cover the quad are read
     if (oki) hor = *reinterpret_cast<const v4f*>(p_hor);
     if (okj) ver = *reinterpret_cast<const v4f*>(p_ver);
     if (oki && okj) dia = *reinterpret_cast<const v4f*>(p_dia);
-#else
-    v4f hor = *reinterpret_cast<const v4f*>(p_hor);
-    v4f ver = *reinterpret_cast<const v4f*>(p_ver);
-    v4f dia = *reinterpret_cast<const v4f*>(p_dia);
-    hor = oki ? hor : zero;
-    ver = okj ? ver : zero;
-    dia = (oki && okj) ? dia : zero;
-#endif
     // fixed order of combine_quad: dj outer (-1, 0, 1), di inner (-1, 0, 1)
     const bool hfirst = di < 0, vfirst = dj < 0;
     const v4f r0a = hfirst ? dia : ver, r0b = hfirst ? ver : dia;      // the neighbouring row of tiles (dj != 0)
@@ -529,9 +495,8 @@ __global__ __launch_bounds__(256) void combine_tiles_kernel(const float* __restr
   }
 }
 
-// Second stage: fixed-order sum of the per-block partials (deterministic).
-__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partial, int n,
-                                                               float* __restrict__ sums) {
+// Fixed-order sum of the per-block partial records by one block of 1024 threads (deterministic).
+__device__ __forceinline__ void reduce_partials(const float* __restrict__ partial, int n, float* __restrict__ sums) {
   __shared__ double sh[1024][4];
   double acc[4] = {0, 0, 0, 0};
   for (int i = threadIdx.x; i < n; i += 1024) {
@@ -551,39 +516,18 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __re
     }
     __syncthreads();
   }
-  if (threadIdx.x < 4) {
-    sums[threadIdx.x] = (float)sh[0][threadIdx.x];
-  }
+  if (threadIdx.x < 4) sums[threadIdx.x] = (float)sh[0][threadIdx.x];
 }
 
-// Last launch of the tiled sequence: block 0 sums the per-tile partials (as reduce_partials_kernel),
-// the other blocks apply the window-overflow records with hardware fp32 atomics -- the two are independent,
-// so they share a launch.
+// Last launch of every variant's sequence: block 0 sums the per-block partials, the other blocks (none when g_d2 is null:
+// forward only, the direct variant) apply the window-overflow records with hardware fp32 atomics -- the two are
+// independent, so they share a launch.
 __global__ __launch_bounds__(1024) void warp_finish_kernel(const float* __restrict__ partial, int n,
                                                            float* __restrict__ sums,
                                                            const unsigned* __restrict__ count,
                                                            const int2* __restrict__ rec, unsigned cap, float* g_d2) {
   if (blockIdx.x == 0) {
-    __shared__ double sh[1024][4];
-    double acc[4] = {0, 0, 0, 0};
-    for (int i = threadIdx.x; i < n; i += 1024) {
-      const float4 v = *reinterpret_cast<const float4*>(partial + (size_t)i * 4);
-      acc[0] += v.x;
-      acc[1] += v.y;
-      acc[2] += v.z;
-      acc[3] += v.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sh[threadIdx.x][k] = acc[k];
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-      if (threadIdx.x < s) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sh[threadIdx.x][k] += sh[threadIdx.x + s][k];
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x < 4) sums[threadIdx.x] = (float)sh[0][threadIdx.x];
+    reduce_partials(partial, n, sums);
     return;
   }
   if (g_d2 == nullptr) return;
@@ -635,13 +579,11 @@ static const TileShape kShapes[] = {{96, 32, 512}, {64, 48, 512}, {64, 32, 512},
 constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
 
 // Variant selection: the production path is the tiled kernel with the auto-chosen tile shape.  The parity tests
-// also drive the other shapes, the 4-pixels-per-step mapping and the global-atomics reference variant through
+// also drive the other shapes and the global-atomics reference variant through
 // dvd_warp_loss_select() -- a process-wide test hook, not an environment switch read on every call.
 static int g_variant = 0;   // 0 production: strips (csrc/warp_strip.hip) when the call is eligible, else tiles; 1 direct (global
                             // gathers + hardware atomics); 2 tiles (the production kernel of rounds 2-5) whatever the call
 static int g_tile = -1;     // -1 auto, else index into kShapes
-static int g_px = 0;        // 0 auto, 2 or 4 pixels per thread-step
-static int g_combine = 0;   // 0 per-tile combine (round 5), 1 the per-quad combine of rounds 2-4 (tests: px == 4 selects it too)
 
 // Least padded area wins; ties go to the earlier (larger) shape.
 static int choose_shape(int H, int W) {
@@ -659,9 +601,22 @@ static int choose_shape(int H, int W) {
   return best;
 }
 
+// (shared with the strip generation, csrc/warp_strip.hip)
+WarpWorkspace warp_workspace(size_t n_partials, size_t lists, int B, size_t slab_floats, size_t ovf_cap) {
+  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  WarpWorkspace w;
+  w.off_count = up256(n_partials * 4 * sizeof(float));
+  w.off_offs = up256(w.off_count + lists * sizeof(unsigned));
+  w.off_slabs = up256(w.off_offs + (size_t)B * sizeof(int2));
+  w.off_ovf = up256(w.off_slabs + lists * slab_floats * sizeof(float));
+  w.total = w.off_ovf + lists * ovf_cap * sizeof(int2);
+  return w;
+}
+
 struct Plan {
-  int shape, ntx, nty, ww, wh;
-  size_t n_partials, off_count, off_offs, off_slabs, off_ovf, ovf_cap, total;
+  int shape, ntx, nty;
+  size_t ovf_cap;
+  WarpWorkspace ws;
 };
 
 static Plan make_plan(int B, int H, int W) {
@@ -670,27 +625,11 @@ static Plan make_plan(int B, int H, int W) {
   const TileShape& t = kShapes[p.shape];
   p.ntx = (W + t.tw - 1) / t.tw;
   p.nty = (H + t.th - 1) / t.th;
-  p.ww = t.tw + 2 * kR + 4;
-  p.wh = t.th + 2 * kR + 1;
   const size_t tiles = (size_t)p.ntx * p.nty * B;
-  const size_t direct_blocks = (size_t)blocks_x(H * W, 1) * B;
-  p.n_partials = tiles > direct_blocks ? tiles : direct_blocks;
-  size_t off = p.n_partials * 4 * sizeof(float);
-  off = (off + 255) & ~(size_t)255;
-  p.off_count = off;
-  off += tiles * sizeof(unsigned);
-  off = (off + 255) & ~(size_t)255;
-  p.off_offs = off;
-  off += (size_t)B * sizeof(int2);
-  off = (off + 255) & ~(size_t)255;
-  p.off_slabs = off;
-  off += tiles * (size_t)p.ww * p.wh * sizeof(float);
-  off = (off + 255) & ~(size_t)255;
-  p.off_ovf = off;
-  // per tile: every tap of every pixel -- no list can overflow
-  p.ovf_cap = (size_t)t.tw * t.th * 4;
-  off += tiles * p.ovf_cap * sizeof(int2);
-  p.total = off;
+  const size_t direct_blocks = (size_t)blocks_x(H * W, 1) * B;        // the direct variant's partial records
+  p.ovf_cap = (size_t)t.tw * t.th * 4;        // per tile: every tap of every pixel -- no list can overflow
+  p.ws = warp_workspace(tiles > direct_blocks ? tiles : direct_blocks, tiles, B,
+                        (size_t)(t.tw + 2 * kR + 4) * (t.th + 2 * kR + 1), p.ovf_cap);
   return p;
 }
 
@@ -702,83 +641,46 @@ static Plan make_plan(int B, int H, int W) {
 //     a multi-XCD part an agent-scope fence writes back / invalidates the XCD's whole L2;
 //   * two tile launches cut where the full rounds of blocks end, the first cut's combine on a side stream under the second
 //     launch: 0.252-0.263 ms against 0.234-0.238 -- the event record / wait pair costs more than the overlap returns.
-template <int TW, int TH, int NT>
-static int launch_tiled(const WarpArgs& a, const Plan& p, char* ws, bool grads, hipStream_t stream) {
-  constexpr int WW = TW + 2 * kR + 4, WH = TH + 2 * kR + 1;
-  TileArgs ta;
-  ta.slabs = reinterpret_cast<float*>(ws + p.off_slabs);
-  ta.ovf.count = reinterpret_cast<unsigned*>(ws + p.off_count);
-  ta.ovf.rec = reinterpret_cast<int2*>(ws + p.off_ovf);
-  ta.ovf.cap = (unsigned)p.ovf_cap;
-  int2* offs = reinterpret_cast<int2*>(ws + p.off_offs);
-  ta.offs = offs;
-  ta.ntx = p.ntx;
-  ta.nty = p.nty;
-  ta.direct = ((a.W & 3) == 0 && DVD_WARP_DIRECT_INTERIOR) ? 1 : 0;
-  ta.tile0 = 0;
-  const int tiles = p.ntx * p.nty, nblocks = tiles * a.B;
-  const size_t lds = (size_t)WW * WH * (sizeof(float) + sizeof(unsigned long long)) + kCamLdsFloats * sizeof(float) + 16;
-  const bool shipped = a.midas_mask && a.disp_mode == 1 && !a.loss_on_sf;
-  // 2 pixels per thread-step when that splits the tile evenly over the block and 4 does not
+template <int TW, int TH, int NT, bool GRADS, bool SHIPPED>
+static int launch_tile_kernel(const WarpArgs& a, const TileArgs& ta, int nblocks, hipStream_t stream) {
+  constexpr int lds = tile_lds_bytes(TW, TH, kR);
+  // pixels per thread-step: 2 when that splits the tile evenly over the block and 4 does not
   constexpr bool kEven4 = ((TW / 4) * TH) % NT == 0, kEven2 = ((TW / 2) * TH) % NT == 0;
-  const bool px2 = (g_px ? g_px : ((kEven2 && !kEven4) ? 2 : 4)) == 2;
-  auto tile_launch = [&](int pair0, int npairs) -> int {
-    TileArgs t2 = ta;
-    t2.tile0 = pair0 * tiles;
-    const int nb = npairs * tiles;
-#define DVD_TILED_LAUNCH(G, S)                                                                            \
-  do {                                                                                                    \
-    auto k = px2 ? warp_loss_tiled_kernel<TW, TH, kR, NT, G, S, 2> : warp_loss_tiled_kernel<TW, TH, kR, NT, G, S, 4>; \
-    DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                      \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                \
-    hipLaunchKernelGGL(k, dim3(nb), dim3(NT), lds, stream, a, t2);                                        \
-  } while (0)
-#ifdef DVD_WARP_QUICK
-    {
-#ifndef DVD_WARP_QUICK_GRADS
-#define DVD_WARP_QUICK_GRADS true
-#endif
-      auto k = warp_loss_tiled_kernel<TW, TH, kR, NT, DVD_WARP_QUICK_GRADS, true, 2>;
-      hipLaunchKernelGGL(k, dim3(nb), dim3(NT), lds, stream, a, t2);
-      return DVD_OK;
-    }
-#else
-    if (grads) {
-      if (shipped)
-        DVD_TILED_LAUNCH(true, true);
-      else
-        DVD_TILED_LAUNCH(true, false);
-    } else {
-      if (shipped)
-        DVD_TILED_LAUNCH(false, true);
-      else
-        DVD_TILED_LAUNCH(false, false);
-    }
-#endif
-#undef DVD_TILED_LAUNCH
-    DVD_LAUNCH_OK();
-    return DVD_OK;
-  };
-  auto combine_launch = [&](int pair0, int npairs, hipStream_t st) -> int {
-    const int qpr = (a.W + 3) / 4;
-    const int total_quads = qpr * a.H * npairs;
-    if (DVD_WARP_COMBINE_TILES && g_combine == 0)
-      hipLaunchKernelGGL((combine_tiles_kernel<TW, TH, kR>), dim3(npairs * tiles), dim3(256), 0, st, ta.slabs,
-                         (const int2*)offs, a.g_d2, a.H, a.W, p.ntx, p.nty, ta.direct, pair0);
-    else
-      hipLaunchKernelGGL((combine_slabs_kernel<TW, TH, kR>), dim3((total_quads + 255) / 256), dim3(256), 0, st, ta.slabs,
-                         (const int2*)offs, a.g_d2, a.H, a.W, p.ntx, p.nty, total_quads, ta.direct, pair0);
-    DVD_LAUNCH_OK();
-    return DVD_OK;
-  };
-  if (int e = tile_launch(0, a.B)) return e;
-  if (grads)
-    if (int e = combine_launch(0, a.B, stream)) return e;
-  // partial-sum reduction and overflow records in one launch
-  hipLaunchKernelGGL(warp_finish_kernel, dim3(grads ? 129 : 1), dim3(1024), 0, stream, a.partial, nblocks, a.sums,
-                     ta.ovf.count, ta.ovf.rec, ta.ovf.cap, grads ? a.g_d2 : (float*)nullptr);
+  constexpr int PX = (kEven2 && !kEven4) ? 2 : 4;
+  auto k = warp_loss_tiled_kernel<TW, TH, kR, NT, GRADS, SHIPPED, PX>;
+  DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(k, dim3(nblocks), dim3(NT), lds, stream, a, ta);
   DVD_LAUNCH_OK();
   return DVD_OK;
+}
+
+template <int TW, int TH, int NT>
+static int launch_tiled(const WarpArgs& a, const Plan& p, char* ws, bool grads, hipStream_t stream) {
+  TileArgs ta;
+  ta.slabs = reinterpret_cast<float*>(ws + p.ws.off_slabs);
+  ta.ovf.count = reinterpret_cast<unsigned*>(ws + p.ws.off_count);
+  ta.ovf.rec = reinterpret_cast<int2*>(ws + p.ws.off_ovf);
+  ta.ovf.cap = (unsigned)p.ovf_cap;
+  ta.offs = reinterpret_cast<int2*>(ws + p.ws.off_offs);
+  ta.ntx = p.ntx;
+  ta.nty = p.nty;
+  ta.direct = (a.W & 3) == 0;
+  ta.tile0 = 0;               // one launch covers every pair
+  const int nblocks = p.ntx * p.nty * a.B;
+  const bool shipped = a.midas_mask && a.disp_mode == 1 && !a.loss_on_sf;
+  const int e = grads ? (shipped ? launch_tile_kernel<TW, TH, NT, true, true>(a, ta, nblocks, stream)
+                                 : launch_tile_kernel<TW, TH, NT, true, false>(a, ta, nblocks, stream))
+                      : (shipped ? launch_tile_kernel<TW, TH, NT, false, true>(a, ta, nblocks, stream)
+                                 : launch_tile_kernel<TW, TH, NT, false, false>(a, ta, nblocks, stream));
+  if (e) return e;
+  if (grads) {
+    hipLaunchKernelGGL((combine_tiles_kernel<TW, TH, kR>), dim3(nblocks), dim3(256), 0, stream, ta.slabs,
+                       (const int2*)ta.offs, a.g_d2, a.H, a.W, p.ntx, p.nty, ta.direct, 0);
+    DVD_LAUNCH_OK();
+  }
+  // partial-sum reduction and overflow records in one launch
+  return launch_warp_finish(a.partial, nblocks, a.sums, ta.ovf.count, ta.ovf.rec, ta.ovf.cap,
+                            grads ? a.g_d2 : (float*)nullptr, stream);
 }
 
 static int run(const dvd_warp_cfg* cfg, const float* depth_1, const float* depth_2, const float* flow_1_2,
@@ -799,7 +701,7 @@ static int run(const dvd_warp_cfg* cfg, const float* depth_1, const float* depth
   DVD_REQUIRE((long long)cfg->B * HW * 3 < (1LL << 31), "warp_loss: tensor too large for 32-bit indexing");
   const Plan plan = make_plan(cfg->B, cfg->H, cfg->W);
   const StripPlan splan = make_strip_plan(cfg->B, cfg->H, cfg->W);
-  const size_t need = plan.total > splan.total ? plan.total : splan.total;
+  const size_t need = plan.ws.total > splan.ws.total ? plan.ws.total : splan.ws.total;
   if (workspace_bytes < need) {
     set_error("warp_loss: workspace %zu < %zu bytes", workspace_bytes, need);
     return DVD_ENOSPC;
@@ -859,20 +761,15 @@ static int run(const dvd_warp_cfg* cfg, const float* depth_1, const float* depth
         hipLaunchKernelGGL((warp_loss_kernel<1, false>), grid, block, 0, stream, a);
     }
     DVD_LAUNCH_OK();
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, stream, a.partial, nbx * cfg->B, sums);
-    DVD_LAUNCH_OK();
-    return DVD_OK;
+    return launch_warp_finish(a.partial, nbx * cfg->B, sums, nullptr, nullptr, 0, nullptr, stream);
   }
   char* ws = static_cast<char*>(workspace);
   // Production path (round 6): the strip kernel -- backward pass, shipped flag set (--midas --use_disp), rows of whole
   // 16-byte quads.  Everything else (forward only, the other loss modes, odd widths, the test hooks' tile shapes) stays on
   // the tile kernel below.  Cameras outside the lockstep loop's preconditions are handled inside either kernel.
-  if (g_variant == 0 && g_tile < 0 && g_px == 0 && grads && a.midas_mask && a.disp_mode == 1 && !a.loss_on_sf &&
+  if (g_variant == 0 && g_tile < 0 && grads && a.midas_mask && a.disp_mode == 1 && !a.loss_on_sf &&
       (cfg->W & 3) == 0 && all16)
     return launch_strips(a, splan, ws, stream);
-#ifdef DVD_WARP_QUICK      // development: compile the production instantiation only (tools/isa_stats.py ... -DDVD_WARP_QUICK)
-  return launch_tiled<96, 32, DVD_WARP_QUICK>(a, plan, ws, grads, stream);
-#else
   switch (plan.shape) {
     case 0:
       return launch_tiled<96, 32, 512>(a, plan, ws, grads, stream);
@@ -885,7 +782,6 @@ static int run(const dvd_warp_cfg* cfg, const float* depth_1, const float* depth
     default:
       return launch_tiled<64, 32, 256>(a, plan, ws, grads, stream);
   }
-#endif
 }
 
 }  // namespace dvd
@@ -893,12 +789,11 @@ static int run(const dvd_warp_cfg* cfg, const float* depth_1, const float* depth
 extern "C" {
 
 int dvd_warp_loss_select(int variant, int tile, int px) {
-  DVD_REQUIRE(variant >= 0 && variant <= 2 && tile >= -1 && tile < dvd::kNumShapes && (px == 0 || px == 2 || px == 4),
-              "warp_loss_select: variant %d tile %d px %d", variant, tile, px);
+  DVD_REQUIRE(variant >= 0 && variant <= 2 && tile >= -1 && tile < dvd::kNumShapes, "warp_loss_select: variant %d tile %d",
+              variant, tile);
+  DVD_REQUIRE(px == 0, "warp_loss_select: px %d: the third argument is reserved (0), pixels per thread-step are fixed by the tile shape", px);
   dvd::g_variant = variant;
   dvd::g_tile = tile;
-  dvd::g_px = px;
-  dvd::g_combine = px == 4 ? 1 : 0;      // the 4-pixel test variant also keeps the per-quad combine of rounds 2-4 covered
   return DVD_OK;
 }
 
@@ -911,7 +806,7 @@ int dvd_warp_loss_strip_select(int rows, int shape) {
 size_t dvd_warp_loss_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   // block partial sums + overflow counters + accumulator slabs + overflow lists, of whichever generation needs more
-  const size_t t = dvd::make_plan(B, H, W).total, s = dvd::make_strip_plan(B, H, W).total;
+  const size_t t = dvd::make_plan(B, H, W).ws.total, s = dvd::make_strip_plan(B, H, W).ws.total;
   return t > s ? t : s;
 }
 

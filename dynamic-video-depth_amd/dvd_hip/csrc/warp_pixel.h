@@ -7,42 +7,6 @@
 
 #include "dvd_common.h"
 
-#ifndef DVD_WARP_PREFETCH
-#define DVD_WARP_PREFETCH 0
-#endif
-#ifndef DVD_WARP_DIRECT_INTERIOR
-#define DVD_WARP_DIRECT_INTERIOR 1
-#endif
-#ifndef DVD_WARP_PINHOLE
-#define DVD_WARP_PINHOLE 1      // 0: A/B builds without the pinhole-intrinsics instantiation (tools/build_variant.sh)
-#endif
-#ifndef DVD_WARP_V5
-#define DVD_WARP_V5 1           // 0: A/B builds without the two-pixel lockstep loop of round 5 (tools/build_variant.sh)
-#endif
-#ifndef DVD_WARP_V5_PREFETCH
-#define DVD_WARP_V5_PREFETCH 0  // 1: inputs of thread-step i + 1 requested between the phases of step i (measured: 159.7 vs 156.1 us without)
-#endif
-#ifndef DVD_WARP_COMBINE_TILES
-#define DVD_WARP_COMBINE_TILES 1
-#endif
-#ifndef DVD_WARP_KO_FILL           // knock-out builds (timing studies only; results are wrong): no window loads / no flush
-#define DVD_WARP_KO_FILL 0
-#endif
-#ifndef DVD_WARP_KO_FLUSH
-#define DVD_WARP_KO_FLUSH 0
-#endif
-#ifndef DVD_WARP_COMBINE_MASKED
-#define DVD_WARP_COMBINE_MASKED 1
-#endif
-#ifndef DVD_WARP_V5_EARLY
-#define DVD_WARP_V5_EARLY 0
-#endif
-#ifndef DVD_WARP_V5_SCHED
-#define DVD_WARP_V5_SCHED 1     // scheduling barriers at the forward / backward boundary of the lockstep pixel pair
-#endif
-#ifndef DVD_WARP_CAM_VGPR
-#define DVD_WARP_CAM_VGPR 0     // bit mask of the camera matrices pinned into VGPRs: 1 R1, 2 R2, 4 K, 8 R2T (round 4: 15)
-#endif
 #include <type_traits>
 
 
@@ -459,7 +423,7 @@ __global__ __launch_bounds__(256) void warp_loss_kernel(const WarpArgs a) {
 //          taps are read from it (ds_read2_b32);
 //   accw : depth_2-gradient accumulator, Q31.32 fixed point (ds_add_u64; see kFixScale below).
 // At the end the accumulator window is stored, coalesced, to the tile's slab
-// in the workspace; `combine_slabs_kernel` then sums, in a fixed order, the
+// in the workspace; `combine_tiles_kernel` then sums, in a fixed order, the
 // <= 4 slabs that cover each pixel and writes g_depth_2 once with plain
 // stores: no global atomics, no memset of g_depth_2.  Taps that fall outside
 // the window (|flow| > R) stay correct: they are gathered from global memory
@@ -717,10 +681,6 @@ __device__ __forceinline__ void pixel2(const WarpArgs& a, const CAMT& cam, const
     dsw = (v2f){pA[WW], pB[WW]};
     dse = (v2f){pA[WW + 1], pB[WW + 1]};
   } else {
-#ifdef DVD_WARP_NO_SLOW
-    dnw = dne = dsw = dse = (v2f){0.f, 0.f};
-    return;
-#endif
     float t0, t1, t2, t3, u0, u1, u2, u3;
     io.fetch(y0A * a.W + x0A, x0A, y0A, (x0A + 1) < a.W, (y0A + 1) < a.H, t0, t1, t2, t3);
     io.fetch(y0B * a.W + x0B, x0B, y0B, (x0B + 1) < a.W, (y0B + 1) < a.H, u0, u1, u2, u3);
@@ -799,15 +759,12 @@ __device__ __forceinline__ void pixel2(const WarpArgs& a, const CAMT& cam, const
   const v2f rca2 = {Q2.x >= 1e-3f ? rca.x * rca.x : 0.0f, Q2.y >= 1e-3f ? rca.y * rca.y : 0.0f};
   const v2f h2 = {W2z.x >= 1e-3f ? ue.x * (rcb.x * rcb.x) : 0.0f, W2z.y >= 1e-3f ? ue.y * (rcb.y * rcb.y) : 0.0f};
   // ---- phase boundary: what the backward needs is (gu, gv, u, v, 1/den, ue, rca2, h2, the four weights, the cells, the
-  //      ray); the scheduler may not mix the phases (it would hold both phases' values at once and spill), and the
-  //      caller requests the NEXT thread-step's inputs here, so that they fly under the backward and the scatter
-#if DVD_WARP_V5_SCHED
+  //      ray); the scheduler may not mix the phases (it would hold both phases' values at once and spill: hence the two
+  //      scheduling barriers), and the strip kernel requests the NEXT thread-step's inputs here, so that they fly under the
+  //      backward and the scatter (the tile kernel requests nothing there: it cost 159.7 us against 156.1)
   __builtin_amdgcn_sched_barrier(0);
-#endif
   between_phases();
-#if DVD_WARP_V5_SCHED
   __builtin_amdgcn_sched_barrier(0);
-#endif
   // behind the camera: the projection was replaced by the pixel's own coordinates, no gradient (a zero reciprocal:
   // u, v are finite there)
   const v2f rden = {behindA ? 0.0f : y0.x, behindB ? 0.0f : y0.y};
@@ -845,22 +802,18 @@ __device__ __forceinline__ void pixel2(const WarpArgs& a, const CAMT& cam, const
         const v2f k = (v2f){__builtin_amdgcn_fractf(t.x), __builtin_amdgcn_fractf(t.y)} * kFixScale;
         atomicAdd(pA + off, to_fixed_fast(t.x, k.x));
         atomicAdd(pB + off, to_fixed_fast(t.y, k.y));
-#if DVD_WARP_V5_SCHED
         __builtin_amdgcn_sched_barrier(0);
-#endif
       };
       tap(w_nw, 0);
       tap(w_ne, 1);
       tap(w_sw, WW);
       tap(w_se, WW + 1);
     } else {
-#ifndef DVD_WARP_NO_SLOW
       const v2f t_nw = w_nw * h2, t_ne = w_ne * h2, t_sw = w_sw * h2, t_se = w_se * h2;
       if (h2.x != 0.0f)
         io.scatter(y0A * a.W + x0A, x0A, y0A, (x0A + 1) < a.W, (y0A + 1) < a.H, t_nw.x, t_ne.x, t_sw.x, t_se.x);
       if (h2.y != 0.0f)
         io.scatter(y0B * a.W + x0B, x0B, y0B, (x0B + 1) < a.W, (y0B + 1) < a.H, t_nw.y, t_ne.y, t_sw.y, t_se.y);
-#endif
     }
   }
 }
@@ -904,9 +857,18 @@ __device__ __forceinline__ int2 pair_window_offset(const float* __restrict__ flo
 
 
 // ---- the strip generation (csrc/warp_strip.hip), called from dvd::run in csrc/warp_loss.hip
+// Workspace of a launch sequence of either generation: per-block partial sums | record count per overflow list | window
+// offset per pair | accumulator slabs | overflow records, each part rounded up to 256 bytes.  One list and one slab per tile
+// or unit.
+struct WarpWorkspace {
+  size_t off_count, off_offs, off_slabs, off_ovf, total;
+};
+WarpWorkspace warp_workspace(size_t n_partials, size_t lists, int B, size_t slab_floats, size_t ovf_cap);
+
 struct StripPlan {
   int shape, ntx, nseg, SH;
-  size_t n_units, off_count, off_offs, off_slabs, slab_stride, off_ovf, ovf_cap, total;
+  size_t n_units, slab_stride, ovf_cap;
+  WarpWorkspace ws;
 };
 StripPlan make_strip_plan(int B, int H, int W);
 int strip_select(int rows, int shape);      // test hook; non-zero = rejected

@@ -36,39 +36,6 @@
 
 #include "warp_pixel.h"
 
-#ifndef DVD_STRIP_UNROLL
-#define DVD_STRIP_UNROLL 0          // 1: the two thread-steps of a step as two code copies (precise waits, but loop invariants spill)
-#endif
-#ifndef DVD_STRIP_END_WAIT
-#define DVD_STRIP_END_WAIT -1       // >= 0: vmcnt of the step's closing wait for A/B builds (default: what the walk guarantees)
-#endif
-#ifndef DVD_STRIP_CAM_REGS
-#define DVD_STRIP_CAM_REGS 1        // 1: shapes with a 168-register budget keep the pair's camera in vector registers (0: LDS broadcasts)
-#endif
-#ifndef DVD_STRIP_COMBINE2
-#define DVD_STRIP_COMBINE2 0        // 1: the unit combine requests two quads' slabs before it sums either (measured: 21 us against 16-18)
-#endif
-#ifndef DVD_STRIP_PERSISTENT
-#define DVD_STRIP_PERSISTENT 0
-#endif
-#ifndef DVD_STRIP_PF_EARLY
-#define DVD_STRIP_PF_EARLY 0        // 1: the next thread-step's inputs are requested at the START of a thread-step (0: between its
-                                   // phases: 186.8 against 187.8 us, median of six interleaved runs -- the extra live registers cost
-                                   // what the longer lead buys)
-#endif
-#ifndef DVD_STRIP_KO_BARRIER
-#define DVD_STRIP_KO_BARRIER 0
-#endif
-#ifndef DVD_STRIP_KO_PIXEL
-#define DVD_STRIP_KO_PIXEL 0
-#endif
-#ifndef DVD_STRIP_KO_FLUSH          // knock-out builds (timing studies only; results are wrong)
-#define DVD_STRIP_KO_FLUSH 0
-#endif
-#ifndef DVD_STRIP_KO_FILL
-#define DVD_STRIP_KO_FILL 0
-#endif
-
 namespace dvd {
 
 // R: halo of the window in x (R columns to the left, R + 4 to the right: rows of whole quads); RY: halo in y (RY rows above,
@@ -177,7 +144,6 @@ struct StripArgs {
   int ntx, nseg, SH;  // strips per image row, units per strip column, rows per unit (multiple of TH, >= 2 TH)
   int direct;         // 1: window cells no neighbouring unit covers go straight to g_depth_2
   unsigned slab_stride;   // floats per unit slab = WW * (SH + 2RY + 1)
-  int n_units;
 };
 
 // Window cell (wx, r) of a unit is covered by that unit ALONE when wx in [2R + 4, TW) and r in [2RY + 1, SH): tile_exclusive
@@ -229,25 +195,11 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
   float* red = camL + kCamLdsFloats + 4;                                     // [NW][4] block sums
   static_assert((3 * WW * (C + 1)) % 4 == 0, "camera quads must be 16-byte aligned");
 
-  // ---- DVD_STRIP_PERSISTENT = 1 (an experiment, off: measured 207 us against 171 us -- the outer loop's live values push the
-  //      walk's loop invariants to scratch): persistent blocks (one or two per CU), a block evaluates several units.  Units are numbered so
-  //      that each XCD (block b runs on XCD b % 8: speed only, never correctness) owns a contiguous run of them -- the blocks
-  //      of an XCD take the run's units round robin, so the units in flight on an XCD at any time are neighbours (adjacent
-  //      strips of the same pair share their halo columns of depth_2 in that XCD's L2).  What a unit's start costs in a grid of
-  //      one block per unit -- block launch, clearing 76 KB of accumulator ring -- is paid once per block: every accumulator
-  //      cell a unit touched has been flushed AND cleared when the unit ends.
+  // One block per unit, numbered so that each XCD owns a contiguous run of units (adjacent strips of a pair share their halo
+  // columns of depth_2 in that XCD's L2).  Persistent blocks that walk several units lost, 207 us against 171: the outer
+  // loop's live values push the walk's loop invariants to scratch.
   for (int i = threadIdx.x; i < (C + 1) * WW / 2; i += NT) reinterpret_cast<uint4*>(accw)[i] = make_uint4(0u, 0u, 0u, 0u);
-#if DVD_STRIP_PERSISTENT
-  const int xcd = blockIdx.x & 7, in_xcd = blockIdx.x >> 3, per_xcd = ((int)gridDim.x - xcd + 7) >> 3;
-  const int run_q = sa.n_units >> 3, run_r = sa.n_units & 7;
-  const int run_lo = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
-  const int run_n = run_q + (xcd < run_r ? 1 : 0);
-  for (int run_i = in_xcd; run_i < run_n; run_i += per_xcd) {
-  const int logical = run_lo + run_i;
-#else
-  {
   const int logical = xcd_contiguous_block(blockIdx.x, gridDim.x);
-#endif
   const int upp = sa.ntx * sa.nseg;              // units per pair
   const int b = logical / upp;
   const int t = logical - b * upp;
@@ -283,7 +235,7 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
       const int y = wy_top + r0 + j, x = wx0 + wxq * 4;
       const unsigned dst = win_b + (unsigned)(s0 * WW + q0 * 4) * 4u;        // wave-uniform
       if (q < quads) {
-        if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W && !DVD_STRIP_KO_FILL)
+        if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W)
           glds16(d2b, (unsigned)(y * a.W + x) * 4u, __builtin_amdgcn_readfirstlane(dst));
         else
           *reinterpret_cast<float4*>(win + s0 * WW + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -296,7 +248,7 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
     const int y = wy_top + rg, x = wx0 + q * 4;
     const unsigned dst = win_b + (unsigned)(C * WW) * 4u;
     if (q < QR) {
-      if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W && !DVD_STRIP_KO_FILL)
+      if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W)
         glds16(d2b, (unsigned)(y * a.W + x) * 4u, __builtin_amdgcn_readfirstlane(dst));
       else
         *reinterpret_cast<float4*>(win + C * WW + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -343,7 +295,7 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
     // count the compiler can see, see FULL above
     const bool to_image = sa.direct && unit_exclusive<TW, R, RY>(wx, r, sa.SH) && (unsigned)x < (unsigned)a.W && (unsigned)y < (unsigned)a.H;
     float* dst = to_image ? gb + (size_t)y * a.W + x : slab + r * WW + wx;
-    if (!DVD_STRIP_KO_FLUSH) *reinterpret_cast<float4*>(dst) = v;
+    *reinterpret_cast<float4*>(dst) = v;
   };
   auto flush = [&](int r0, int n) {                  // any number of rows (the unit's last window)
     const int s0 = r0 % C;
@@ -453,12 +405,12 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
   //      its workgroup-scope fence.
   // kEndWait: vector-memory instructions every wave is GUARANTEED to issue behind the step's LDS-direct loads -- the six input
   // loads of the next thread-step, and with FULL the four gradient stores of the thread-step they sit in.
-  constexpr int kEndWait = DVD_STRIP_END_WAIT >= 0 ? DVD_STRIP_END_WAIT : (FULL ? 10 : 6);
+  constexpr int kEndWait = FULL ? 10 : 6;
   auto walk2 = [&](auto crit_tag) {
     constexpr bool CRIT = decltype(crit_tag)::value;
     // the camera of the lockstep loop: vector registers where the shape's budget has room for its 32 values (three waves per
     // SIMD), LDS broadcasts otherwise
-    constexpr bool kCamRegs = DVD_STRIP_CAM_REGS && (BPC * NT) / 256 <= 3;
+    constexpr bool kCamRegs = (BPC * NT) / 256 <= 3;
     typename std::conditional<kCamRegs, CamRegs, const float*>::type camv;
     if constexpr (kCamRegs)
       camv = cam_regs_from_lds(camL);
@@ -484,7 +436,8 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
       io.wyk = wy_top + k * TH;
       io.sk = sk;
       const int y0 = uy0 + k * TH;
-#pragma unroll DVD_STRIP_UNROLL ? NTS : 1
+      // (one code copy for the step's thread-steps: unrolled, the waits are precise but the loop invariants spill)
+#pragma unroll 1
       for (int ts = 0; ts < NTS; ++ts) {
         const int q = threadIdx.x + ts * NT;
         const bool last = ts == NTS - 1;
@@ -492,30 +445,20 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
         In2 nxt;
         int x, y;
         const bool ok = locate(q, y0, x, y);
-        // DVD_STRIP_PF_EARLY: the next thread-step's inputs requested FIRST (a whole thread-step for them to arrive) instead of
-        // between the phases (the backward phase only).  With twelve waves per CU the kernel runs at the rate its memory
-        // latency allows -- its time moves one for one with the bytes of a knocked-out stream
-        // (profiles/r06_warp_strip_experiments.txt) -- but the longer lead did not pay: see the knob.  The scheduling
-        // barrier keeps the early requests from sinking towards their use.
-        constexpr bool kEarly = DVD_STRIP_PF_EARLY && kCamRegs;
-        if (kEarly) {
-          nxt = fetch2(qn, yn);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if ((FULL || ok) && !DVD_STRIP_KO_PIXEL) {
+        // The next thread-step's inputs are requested between the phases, with the backward phase for them to arrive.
+        // Requested first, a whole thread-step ahead, they arrive no sooner in effect: 187.8 against 186.8 us, median of six
+        // interleaved runs -- the extra live registers cost what the longer lead buys.
+        if (FULL || ok) {
           const unsigned o = (unsigned)(y * a.W + x) * 4u;
           pixel2<true, CRIT>(a, camv, io, y, x, cur.d1, (v2f){cur.fl.x, cur.fl.z}, (v2f){cur.fl.y, cur.fl.w}, cur.mk, cur.s0,
-                             cur.s1, cur.s2, yhw, yhh, acc,
-                             [&]() {
-                               if (!kEarly) nxt = fetch2(qn, yn);
-                             },
+                             cur.s1, cur.s2, yhw, yhh, acc, [&]() { nxt = fetch2(qn, yn); },
                              [&](v2f gd1, v2f g0, v2f g1, v2f g2) {
                                *reinterpret_cast<v2f*>(gd1b + o) = gd1;
                                *reinterpret_cast<v2f*>(gsb0 + o) = g0;
                                *reinterpret_cast<v2f*>(gsb0 + (o + plane)) = g1;
                                *reinterpret_cast<v2f*>(gsb0 + (o + 2u * plane)) = g2;
                              });
-        } else if (!kEarly) {
+        } else {
           nxt = fetch2(qn, yn);
         }
         cur = nxt;
@@ -523,10 +466,7 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
       }
       sk += TH;
       sk = sk >= C ? sk - C : sk;
-      if (DVD_STRIP_KO_BARRIER)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(kEndWait) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kEndWait) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kEndWait) : "memory");
     }
   };
   // ---- the general walk (a camera with skew, an R_2_T that is not R_2's transpose: rare): no pipeline, everything waited for
@@ -564,7 +504,6 @@ __global__ __launch_bounds__(NT, (BPC * NT + 255) / 256) void warp_loss_strip_ke
     for (int w = 0; w < NW; ++w) v += red[w * 4 + threadIdx.x];
     a.partial[(size_t)logical * 4 + threadIdx.x] = v;
   }
-  }      // next unit of this block (everything of this one that lives in LDS was read before the barrier above)
 }
 
 // g_depth_2[b, y, x .. x+3] = sum over the units whose window covers the quad, fixed order (dj outer, di inner): combine_quad
@@ -627,7 +566,7 @@ __global__ __launch_bounds__(256) void combine_units_kernel(const float* __restr
   float* gb = g_d2 + (size_t)b * H * W;
   const int kFull = (kTop + kBot) * QW, kRing = kFull + (SH - kTop - kBot) * (kLeft + kRight);
   const ptrdiff_t row_of_units = (ptrdiff_t)ntx * slab_stride;
-  // (DVD_STRIP_COMBINE2: two quads per pass, the loads of both requested before either is summed -- no gain, off)
+  // (one quad per pass: with two, the loads of both requested before either is summed, the kernel took 21 us against 16-18)
   struct Quad {
     v4f own, hor, ver, dia;
     float* dst;
@@ -672,21 +611,11 @@ __global__ __launch_bounds__(256) void combine_units_kernel(const float* __restr
     const v4f t0 = vfirst ? r0a : r1a, t1 = vfirst ? r0b : r1b, t2 = vfirst ? r1a : r0a, t3 = vfirst ? r1b : r0b;
     *reinterpret_cast<v4f*>(q.dst) = (((zero + t0) + t1) + t2) + t3;
   };
-#if DVD_STRIP_COMBINE2
-  for (int idx = threadIdx.x; idx < kRing; idx += 512) {
-    Quad qa, qb;
-    request(idx, qa);
-    request(idx + 256, qb);
-    finish(qa);
-    finish(qb);
-  }
-#else
   for (int idx = threadIdx.x; idx < kRing; idx += 256) {
     Quad qa;
     request(idx, qa);
     finish(qa);
   }
-#endif
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
@@ -760,21 +689,8 @@ StripPlan make_strip_plan(int B, int H, int W) {
   const int ww = kSTW + 2 * kSR + 4;
   p.slab_stride = (size_t)ww * (p.SH + 2 * sh0.ry + 1);
   p.n_units = (size_t)B * p.ntx * p.nseg;
-  size_t off = p.n_units * 4 * sizeof(float);
-  off = (off + 255) & ~(size_t)255;
-  p.off_count = off;
-  off += p.n_units * sizeof(unsigned);
-  off = (off + 255) & ~(size_t)255;
-  p.off_offs = off;
-  off += (size_t)B * sizeof(int2);
-  off = (off + 255) & ~(size_t)255;
-  p.off_slabs = off;
-  off += p.n_units * p.slab_stride * sizeof(float);
-  off = (off + 255) & ~(size_t)255;
-  p.off_ovf = off;
   p.ovf_cap = (size_t)kSTW * p.SH * 4;          // every tap of every pixel of a unit: no list can overflow
-  off += p.n_units * p.ovf_cap * sizeof(int2);
-  p.total = off;
+  p.ws = warp_workspace(p.n_units, p.n_units, B, p.slab_stride, p.ovf_cap);
   return p;
 }
 
@@ -792,8 +708,7 @@ static int launch_strips_shape(const WarpArgs& a, const StripPlan& p, StripArgs&
     attr_set[full] = true;
   }
   const int units = (int)p.n_units;
-  const int slots = DVD_STRIP_PERSISTENT ? BPC * device_cus() : units;
-  hipLaunchKernelGGL(k, dim3(units < slots ? units : slots), dim3(NT), lds, stream, a, sa);
+  hipLaunchKernelGGL(k, dim3(units), dim3(NT), lds, stream, a, sa);
   DVD_LAUNCH_OK();
   hipLaunchKernelGGL((combine_units_kernel<TW, kSR, RY>), dim3(units), dim3(256), 0, stream, sa.slabs, sa.slab_stride,
                      (const int2*)sa.offs, a.g_d2, a.H, a.W, p.ntx, p.nseg, p.SH, sa.direct);
@@ -803,17 +718,16 @@ static int launch_strips_shape(const WarpArgs& a, const StripPlan& p, StripArgs&
 
 int launch_strips(const WarpArgs& a, const StripPlan& p, char* ws, hipStream_t stream) {
   StripArgs sa;
-  sa.slabs = reinterpret_cast<float*>(ws + p.off_slabs);
-  sa.ovf.count = reinterpret_cast<unsigned*>(ws + p.off_count);
-  sa.ovf.rec = reinterpret_cast<int2*>(ws + p.off_ovf);
+  sa.slabs = reinterpret_cast<float*>(ws + p.ws.off_slabs);
+  sa.ovf.count = reinterpret_cast<unsigned*>(ws + p.ws.off_count);
+  sa.ovf.rec = reinterpret_cast<int2*>(ws + p.ws.off_ovf);
   sa.ovf.cap = (unsigned)p.ovf_cap;
-  sa.offs = reinterpret_cast<int2*>(ws + p.off_offs);
+  sa.offs = reinterpret_cast<int2*>(ws + p.ws.off_offs);
   sa.ntx = p.ntx;
   sa.nseg = p.nseg;
   sa.SH = p.SH;
   sa.direct = 1;
   sa.slab_stride = (unsigned)p.slab_stride;
-  sa.n_units = (int)p.n_units;
   DVD_REQUIRE(p.n_units * p.slab_stride < (1ull << 32), "warp_loss: slab workspace too large for 32-bit unit strides");
   switch (p.shape) {
     case 0:

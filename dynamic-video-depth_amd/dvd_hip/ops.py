@@ -726,8 +726,10 @@ def bicubic_resize(x, size, mean=None, std=None):
 
 def warp_loss_select(variant='tiled', tile=-1, px=0, strip_rows=0, strip_shape=0):
     """Test hook: run dvd_warp_loss_fused on another variant -- 'tiled' = production (the strip kernel where it applies, at
-    tile = -1 and px = 0), 'direct' = global gathers + hardware atomics, 'tiles' = the tile kernel of rounds 2-5 whatever the
-    call -- tile shape, pixels-per-step mapping, rows per strip unit or strip shape (csrc/warp_strip.hip kStripShapes).  Process wide; call warp_loss_select() to restore
+    tile = -1), 'direct' = global gathers + hardware atomics, 'tiles' = the tile kernel of rounds 2-5 whatever the
+    call -- tile shape, rows per strip unit or strip shape (csrc/warp_strip.hip kStripShapes).  `px` is reserved like the
+    third argument of dvd_warp_loss_select: callers that still pass px=0 keep working, any other value is rejected by the
+    library (pixels per thread-step are fixed by the tile shape).  Process wide; call warp_loss_select() to restore
     the production path."""
     lib = _lib.load()
     _lib.check(lib.dvd_warp_loss_select({'tiled': 0, 'direct': 1, 'tiles': 2}[variant], int(tile), int(px)), 'dvd_warp_loss_select')

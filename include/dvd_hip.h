@@ -146,11 +146,12 @@ typedef struct dvd_warp_cfg {
 
 size_t dvd_warp_loss_workspace_bytes(int B, int H, int W);
 /* Test hook (process wide; not an environment switch): variant 0 = production -- since ABI 7 the strip kernel
- * (csrc/warp_strip.hip) for a backward call with the shipped flag set and W % 4 == 0 at tile = -1, px = 0, the tiled LDS
+ * (csrc/warp_strip.hip) for a backward call with the shipped flag set and W % 4 == 0 at tile = -1, the tiled LDS
  * kernel otherwise; 1 = reference variant with global gathers + hardware atomics; 2 = the tiled LDS kernel of rounds 2-5
- * whatever the call; tile = -1 (auto) or an index of the tile-shape table; px = 0 (auto), 2 or 4 pixels per thread-step.
- * Every combination computes the same function. */
-int dvd_warp_loss_select(int variant, int tile, int px);
+ * whatever the call; tile = -1 (auto) or an index of the tile-shape table.  The third argument is RESERVED: pass 0.  It used
+ * to choose 2 or 4 pixels per thread-step; that number is fixed by the tile shape now, and any other value is rejected
+ * (DVD_EINVAL).  Every combination computes the same function. */
+int dvd_warp_loss_select(int variant, int tile, int reserved);
 /* Test hook (ABI 7): rows = image rows per unit of the strip kernel -- 0 = chosen from the shape and the device's block slots,
  * else a multiple of the shape's step height, at least two steps (more, shorter units: more seams between units); shape = 0
  * (production: 96-column strips in 32-row steps, 12 rows of vertical halo, 768-thread blocks), 1 (64 x 16, 512 threads),

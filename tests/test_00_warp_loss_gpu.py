@@ -14,20 +14,21 @@ from oracle import losses as L
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=['strips', 'strips64', 'strips64x16', 'strips96x16', 'stripsRy8', 'tiles', 'tile64x32', 'tile96x32x384', 'px4', 'direct'], autouse=True)
+@pytest.fixture(params=['strips', 'strips64', 'strips64x16', 'strips96x16', 'stripsRy8', 'tiles', 'tile64x32', 'tile96x32x384', 'direct'], autouse=True)
 def warp_variant(request):
     """Every case runs on the production path -- since round 6 the strip kernel (csrc/warp_strip.hip: 96-column strips walked in
     16-row steps, LDS rings, LDS-direct window loads) for the shipped flag set and rows of whole quads, the tile kernel
     otherwise -- on strips cut into 64-row units (the shortest: most seams between units, every step a first or last step), on
     the other strip shapes (64-column strips in 16-row steps at 32-row units: one thread-step per barrier; 96 x 16; 96 x 32 with
     the 8-row vertical halo instead of 12),
-    on the tile kernel of rounds 2-5 (auto tile shape; the smallest tile shape; the 384-thread blocks of the 96 x 32 tile;
-    4 pixels per thread-step = the one-pixel loop of rounds 1-4 with the per-quad combine), and on the global-atomics
-    reference variant.  All of them must reproduce the oracle's masks, counts and sub-gradient signs."""
+    on the tile kernel of rounds 2-5 (auto tile shape; the smallest tile shape and the 384-thread blocks of the 96 x 32 tile:
+    both run the one-pixel loop of rounds 1-4 at 4 pixels per thread-step, the number their shape fixes), and on the
+    global-atomics reference variant, whose sums come out of the same fixed-order reduction as everyone else's.  All of them
+    must reproduce the oracle's masks, counts and sub-gradient signs."""
     from dvd_hip import ops
     v = request.param
     ops.warp_loss_select(variant='direct' if v == 'direct' else ('tiled' if v.startswith('strips') else 'tiles'),
-                         tile={'tile64x32': 3, 'tile96x32x384': 4}.get(v, -1), px=4 if v == 'px4' else 0,
+                         tile={'tile64x32': 3, 'tile96x32x384': 4}.get(v, -1),
                          strip_rows={'strips64': 64, 'strips64x16': 32}.get(v, 0),
                          strip_shape={'strips64x16': 1, 'strips96x16': 2, 'stripsRy8': 3}.get(v, 0))
     yield v

@@ -1,6 +1,8 @@
 #!/bin/bash
-# Build an experimental copy of libdvd_hip.so with extra -D flags for ONE translation unit (default: the warp+loss kernel):
-#   tools/build_variant.sh <name> [-DDVD_WARP_PINHOLE=0 ...]           ->  dvd_hip/lib/variants/libdvd_hip_<name>.so
+# Build an experimental copy of libdvd_hip.so with ONE translation unit (default: the warp+loss kernel) taken from another
+# revision, or built with extra flags:
+#   git show <rev>:dynamic-video-depth_amd/dvd_hip/csrc/warp_loss.hip > /tmp/old/warp_loss.hip      (with the headers it includes)
+#   SRC=/tmp/old/warp_loss.hip tools/build_variant.sh <name>           ->  dvd_hip/lib/variants/libdvd_hip_<name>.so
 #   UNIT=xconv tools/build_variant.sh <name> [-D...]
 # Select it at run time with DVD_HIP_LIB=<path> (dvd_hip/_lib.py).  A/B experiments only; the product library is built by
 # dvd_hip/build.py.

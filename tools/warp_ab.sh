@@ -12,10 +12,10 @@ if [ -z "${SKIP_TESTS:-}" ]; then
 fi
 : > $OUT/ab.log
 run() { lib=$1; tile=$2; echo "== lib=$(basename ${lib:-product}) tile=$tile" >> $OUT/ab.log
-        env ${lib:+DVD_HIP_LIB=$lib} timeout 120 python tools/microbench_warp.py --iters 30 --tile $tile --px ${PX:-0} 2>&1 | grep kernel >> $OUT/ab.log; }
+        env ${lib:+DVD_HIP_LIB=$lib} timeout 120 python tools/microbench_warp.py --iters 30 --tile $tile 2>&1 | grep kernel >> $OUT/ab.log; }
 sq() { lib=$1; tile=$2; name=$(basename ${lib:-product} .so)_t$tile
        ( cd /tmp && env ${lib:+DVD_HIP_LIB=$lib} timeout 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_SALU GRBM_GUI_ACTIVE \
-           --output-format csv -d $ROOT/$OUT/sq_$name -o pmc -- python $ROOT/tools/microbench_warp.py --iters 3 --tile $tile --px ${PX:-0} > $ROOT/$OUT/sq_$name.log 2>&1 )
+           --output-format csv -d $ROOT/$OUT/sq_$name -o pmc -- python $ROOT/tools/microbench_warp.py --iters 3 --tile $tile > $ROOT/$OUT/sq_$name.log 2>&1 )
        python tools/pmc_summary.py "$OUT/sq_$name/" 2>&1 | grep -E "warp_loss_tiled|warp_loss_strip|combine" > $OUT/sq_$name.txt; rm -rf $OUT/sq_$name; }
 for t in $TILES; do run "" $t; [ -n "${SQ:-}" ] && sq "" $t; done
 for f in $V/libdvd_hip_*.so; do
