@@ -222,6 +222,12 @@ SIGNATURES = {
     'dvd_track_project': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 +
                           [c_void_p]),
     'dvd_project_bwd': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p]),
+    # forward splat with a soft z-buffer (csrc/splat.hip; additions within ABI 8)
+    'dvd_splat_workspace_bytes': (c_size_t, [c_int] * 4),
+    'dvd_splat_zmin': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_void_p] + [c_int] * 4 + [c_float, c_float, c_void_p]),
+    'dvd_splat_accumulate': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_void_p] + [c_int] * 4 +
+                             [c_float] * 4 + [c_int, c_longlong, c_void_p]),
+    'dvd_splat_resolve': (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float] * 3 + [c_void_p] * 5),
 }
 
 _lock = threading.Lock()

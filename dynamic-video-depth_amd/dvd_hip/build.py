@@ -44,6 +44,7 @@ SOURCES = [
     ('frame_store.hip', ['-ffp-contract=off']),
     ('frame_union.hip', ['-ffp-contract=off']),
     ('track.hip', ['-ffp-contract=off']),
+    ('splat.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -15,6 +15,7 @@
 // one pixel per thread otherwise.  Same fp32 operation order as torch's CPU matmul (dvd_common.h), built with
 // -ffp-contract=off; the division is the compiler's IEEE division (z is not bounded away from 0 here).
 
+#include "track_cam.h"
 #include "warp_pixel.h"
 
 namespace dvd {
@@ -32,64 +33,11 @@ struct TrackArgs {
   float half_w, half_h, wmax, hmax;
 };
 
-struct TrackCam {
-  float R[9], K[9], t[3];
-};
-
 // the table row of image b at step k, or -1 where the video has ended (or the start is not a frame at all)
 __device__ __forceinline__ int target_frame(const TrackArgs& a, int b, int k) {
   const int s = a.start[b];
   const long long g = (long long)s + k;
   return (s >= 0 && g < (long long)a.N) ? (int)g : -1;
-}
-
-__device__ __forceinline__ void load_track_cam(const TrackArgs& a, int g, TrackCam& c) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    c.R[i] = a.R[(size_t)g * 9 + i];
-    c.K[i] = a.K[(size_t)g * 9 + i];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) c.t[i] = a.t[(size_t)g * 3 + i];
-}
-
-// I = ((P - t) @ R_T) @ K: the one projection core of the forward and the backward
-__device__ __forceinline__ void project_point(const TrackCam& c, float P0, float P1, float P2, float& I0, float& I1,
-                                              float& I2) {
-  float Q0, Q1, Q2;
-  rowvec_mat3(P0 - c.t[0], P1 - c.t[1], P2 - c.t[2], c.R, Q0, Q1, Q2);
-  rowvec_mat3(Q0, Q1, Q2, c.K, I0, I1, I2);
-}
-
-template <int PX, bool PLANAR>
-__device__ __forceinline__ void load_points(const float* __restrict__ base, size_t img, int p0, int HW, float P[3][PX]) {
-  if (PLANAR) {
-    const float* s = base + img * 3 * HW + p0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (PX == 4)
-        *reinterpret_cast<float4*>(P[c]) = *reinterpret_cast<const float4*>(s + (size_t)c * HW);
-      else
-        P[c][0] = s[(size_t)c * HW];
-    }
-  } else {
-    const float* s = base + (img * HW + p0) * 3;
-    float v[3 * PX];
-    if (PX == 4) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) *reinterpret_cast<float4*>(v + 4 * q) = *reinterpret_cast<const float4*>(s + 4 * q);
-    } else {
-      v[0] = s[0];
-      v[1] = s[1];
-      v[2] = s[2];
-    }
-#pragma unroll
-    for (int i = 0; i < PX; ++i) {
-      P[0][i] = v[3 * i];
-      P[1][i] = v[3 * i + 1];
-      P[2][i] = v[3 * i + 2];
-    }
-  }
 }
 
 template <int PX, bool PLANAR>
@@ -109,7 +57,7 @@ __global__ __launch_bounds__(256) void track_project_kernel(const TrackArgs a) {
   }
   if (g >= 0) {
     TrackCam c;
-    load_track_cam(a, g, c);
+    load_track_cam(a.R, a.t, a.K, g, c);
     float P[3][PX];
     load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
     const int y = p0 / a.W, x = p0 - y * a.W;
@@ -174,7 +122,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
   for (int i = 0; i < PX; ++i) G[0][i] = G[1][i] = G[2][i] = 0.0f;
   if (g >= 0) {
     TrackCam c;
-    load_track_cam(a, g, c);
+    load_track_cam(a.R, a.t, a.K, g, c);
     float P[3][PX], gu[PX], gv[PX];
     load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
     if (PX == 4) {

@@ -45,7 +45,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import frame_union, tracks
+from . import frame_union, render, tracks
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 
@@ -994,6 +994,25 @@ class Model(NetInterface):
         un-masked field drives the chain, as in training (--use_motion_seg only masks the flow handed to the warp);
         --use_cnn raises NotImplementedError."""
         return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk)
+
+    def render(self, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
+               **splat_params):
+        """The video re-rendered from its own geometry and motion (models/render.py): for every view v the frames sources[v],
+        un-projected with their refined depth, pushed along the scene-flow field to the time of frame target[v] (target[v] - f
+        Euler steps, as in `track`) and splatted into one image with a soft z-buffer (ops.splat, csrc/splat.hip).
+          target   V frame indices: the time of each view and, by default, its camera (rows of store.tables)
+          cam_c2w [V,4,4], K [V,3,3]  (either or both; host arrays) novel cameras: camera-to-world poses / intrinsics, turned
+                   into table rows by the store's own code
+          sources  V lists of frame indices; with advect none later than its target
+          depth    [N,1,H,W] refined depth (default: video_depth of the store);  valid: optional uint8 [N,H,W], 0 drops a pixel
+          advect   False holds time: the frames are drawn as they are (a static scene; the only mode under --use_cnn, where
+                   True raises NotImplementedError)
+          chunk    source images integrated per pass (default: 8 GB of world points); the result does not depend on it
+          splat_params  z_near, z_tol, w_tap, w_min, value_bound (default 1: colours), fill of ops.splat
+        Returns device tensors: image [V,3,H,W], depth [V,1,H,W] (the nearest surface, 0 where nothing landed), weight
+        [V,1,H,W] (summed bilinear weight) and hit uint8 [V,H,W].  Bitwise reproducible; nothing synchronises with the device."""
+        return render.render(self, store, target, sources, cam_c2w=cam_c2w, K=K, depth=depth, advect=advect, chunk=chunk,
+                             valid=valid, **splat_params)
 
     def _train_pred(self):
         """The reference's train-time `pred` dict (:243-264 + `sf_loss_pp` of :308), materialised on demand from the

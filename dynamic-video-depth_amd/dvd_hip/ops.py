@@ -190,6 +190,202 @@ def project_backward(g_uv, points, start, tables, planar=True, out=None, accumul
     return out
 
 
+# -- forward splat with a soft z-buffer (csrc/splat.hip) -------------------------------------------------------------------
+SPLAT_MAX_C = 8
+SPLAT_DEFAULTS = dict(z_near=1e-3, z_tol=0.05, w_tap=1.0 / 64, w_min=0.25, value_bound=1.0, fill=0.0)
+
+
+def splat_shift(n):
+    """The fixed-point shift of the splat's accumulators for at most n points per view: min(40, 62 - ceil_log2(n)).  A term
+    is at most 2^shift in magnitude, so n of them stay within 2^62."""
+    n = int(n)
+    if n < 1:
+        raise RuntimeError('splat_shift: n must be >= 1, got %d' % n)
+    return min(40, 62 - (n - 1).bit_length())
+
+
+def _splat_sources(what, points, values, view, tables, n_views, valid, planar, host_view):
+    """Everything the splat passes check about their sources before a launch -> (points, values, valid, view on the device,
+    the three tables, S, C, H, W, V, n_max).  n_max: the largest number of points one view can receive -- from the host copy
+    of `view` where there is one, S * H * W otherwise (a device tensor is never read back)."""
+    import numpy as np
+    points = _dev32(points, 'points')
+    if points.dim() != 4 or points.shape[1 if planar else 3] != 3 or points.numel() == 0:
+        raise RuntimeError('%s: points must be [S,3,H,W] (planar) or [S,H,W,3], got %s' % (what, tuple(points.shape)))
+    S = int(points.shape[0])
+    H, W = (int(v) for v in (points.shape[2:4] if planar else points.shape[1:3]))
+    dev = points.device
+    if H < 2 or W < 2:
+        raise RuntimeError('%s: images of %d x %d; a bilinear tap set needs H, W >= 2' % (what, H, W))
+    if S > 65535:
+        raise RuntimeError('%s: at most 65535 source images per launch, got %d' % (what, S))
+    values = _dev32(values, 'values')
+    if values.device != dev or values.dim() != 4 or values.shape[0] != S or tuple(values.shape[2:]) != (H, W) or \
+            not 1 <= values.shape[1] <= SPLAT_MAX_C:
+        raise RuntimeError('%s: values must be [%d,C,%d,%d] with 1 <= C <= %d on the device of the points, got %s' % (
+            what, S, H, W, SPLAT_MAX_C, tuple(values.shape)))
+    C = int(values.shape[1])
+    if valid is not None:
+        if not (torch.is_tensor(valid) and valid.is_cuda and valid.device == dev and valid.dtype == torch.uint8 and
+                tuple(valid.shape) == (S, H, W)):
+            raise RuntimeError('%s: valid must be a GPU uint8 tensor [%d,%d,%d] on the device of the points' % (what, S, H, W))
+        valid = valid if valid.is_contiguous() else valid.contiguous()
+    V = int(n_views)
+    if isinstance(n_views, bool) or V != n_views or not 1 <= V <= 65535:
+        raise RuntimeError('%s: n_views must be an integer in 1 .. 65535, got %r' % (what, n_views))
+    tabs = []
+    for k, per in zip(TRACK_TABLES, (9, 3, 9)):
+        if k not in tables:
+            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRACK_TABLES)))
+        tab = _dev32(tables[k], 'table ' + k)
+        if tab.device != dev:
+            raise RuntimeError('%s: table %s and the points are on different devices' % (what, k))
+        if tab.dim() < 2 or tab.shape[0] != V or tab.numel() != V * per:
+            raise RuntimeError('%s: table %s must hold %d values for each of %d views, got %s' % (what, k, per, V, tuple(tab.shape)))
+        tabs.append(tab)
+    host = None
+    if torch.is_tensor(view) and view.is_cuda:
+        if view.dtype != torch.int32 or view.dim() != 1 or view.shape[0] != S or not view.is_contiguous() or view.device != dev:
+            raise RuntimeError('%s: view must be a contiguous GPU int32 tensor of %d view ids on the device of the points' % (what, S))
+        if host_view is not None:
+            host = np.asarray(host_view)
+    else:
+        host = np.asarray(view.cpu() if torch.is_tensor(view) else view)
+        view = None
+    if host is not None:
+        if host.dtype.kind == 'f' and host.size and np.all(np.isfinite(host)) and np.all(host == np.floor(host)):
+            host = host.astype(np.int64)
+        if host.dtype.kind not in 'iu' or host.shape != (S,):
+            raise RuntimeError('%s: view must hold %d integral view ids, got %s %s' % (what, S, host.dtype, host.shape))
+        if int(host.min()) < -2 ** 31 or int(host.max()) >= 2 ** 31:
+            raise RuntimeError('%s: view ids must fit 32 bits' % what)
+        live = host[(host >= 0) & (host < V)]
+        per_view = int(np.bincount(live.astype(np.int64), minlength=1).max()) if live.size else 0
+        n_max = max(1, per_view) * H * W
+        if view is None:
+            view = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev, non_blocking=True)
+    else:
+        n_max = S * H * W
+    return points, values, valid, view, tabs, S, C, H, W, V, n_max
+
+
+def _splat_params(what, **p):
+    """The numeric parameters as floats, refused here with the kernels' own rules."""
+    p = {k: float(v) for k, v in p.items()}
+    ok = {'z_near': lambda v: v >= 0, 'z_tol': lambda v: v >= 0, 'w_tap': lambda v: 0 < v <= 0.25, 'w_min': lambda v: v > 0,
+          'value_bound': lambda v: v > 0, 'fill': lambda v: True}
+    for k, v in p.items():
+        if not (ok[k](v) and (k == 'fill' or v < float('inf'))):
+            raise RuntimeError('%s: %s=%r is out of range' % (what, k, v))
+    return p
+
+
+def splat_workspace(n_views, C, H, W, device):
+    """The splat's workspace as torch tensors, uncleared: (zbuf int32 [V,H,W], acc int64 [V,H,W,C+1])."""
+    V, C, H, W = int(n_views), int(C), int(H), int(W)
+    nbytes = _lib.load().dvd_splat_workspace_bytes(V, C, H, W)
+    if nbytes == 0:
+        raise RuntimeError('splat_workspace: no workspace for V=%d C=%d H=%d W=%d' % (V, C, H, W))
+    zbuf = torch.empty((V, H, W), device=device, dtype=torch.int32)
+    acc = torch.empty((V, H, W, C + 1), device=device, dtype=torch.int64)
+    assert zbuf.numel() * 4 + acc.numel() * 8 == nbytes
+    return zbuf, acc
+
+
+def splat_clear(zbuf, acc):
+    """The two clears every splat starts from: zbuf to 0xFF bytes (empty), acc to 0."""
+    zbuf.fill_(-1)
+    acc.zero_()
+
+
+def _splat_ws_ok(what, zbuf, acc, dev, V, C, H, W):
+    if not (torch.is_tensor(zbuf) and zbuf.device == dev and zbuf.dtype == torch.int32 and tuple(zbuf.shape) == (V, H, W) and
+            zbuf.is_contiguous()):
+        raise RuntimeError('%s: zbuf must be a contiguous int32 tensor %s on the device of the points' % (what, (V, H, W)))
+    if acc is not None and not (torch.is_tensor(acc) and acc.device == dev and acc.dtype == torch.int64 and
+                                tuple(acc.shape) == (V, H, W, C + 1) and acc.is_contiguous()):
+        raise RuntimeError('%s: acc must be a contiguous int64 tensor %s on the device of the points' % (what, (V, H, W, C + 1)))
+
+
+def splat_zmin(zbuf, points, values, view, tables, n_views, valid=None, planar=True, z_near=1e-3, w_tap=1.0 / 64,
+               host_view=None):
+    """Pass a of the splat (dvd_splat_zmin): the nearest depth per target pixel into a cleared zbuf."""
+    what = 'splat_zmin'
+    points, values, valid, view, (R, t, K_T), S, C, H, W, V, _ = _splat_sources(what, points, values, view, tables, n_views,
+                                                                                 valid, planar, host_view)
+    p = _splat_params(what, z_near=z_near, w_tap=w_tap)
+    _splat_ws_ok(what, zbuf, None, points.device, V, C, H, W)
+    _lib.check(_lib.load().dvd_splat_zmin(_p(points), int(bool(planar)), _p(values), _p(valid), _p(view), _p(R), _p(t), _p(K_T),
+                                          V, _p(zbuf), S, C, H, W, p['z_near'], p['w_tap'], _stream()), 'dvd_splat_zmin')
+
+
+def splat_accumulate(zbuf, acc, shift, n_max, points, values, view, tables, n_views, valid=None, planar=True, z_near=1e-3,
+                     z_tol=0.05, w_tap=1.0 / 64, value_bound=1.0, host_view=None):
+    """Pass b of the splat (dvd_splat_accumulate): the taps within z_tol of zbuf's depth, added to acc in fixed point.  n_max
+    bounds the points one view receives over all the calls that add into this acc; shift <= splat_shift(n_max)."""
+    what = 'splat_accumulate'
+    points, values, valid, view, (R, t, K_T), S, C, H, W, V, _ = _splat_sources(what, points, values, view, tables, n_views,
+                                                                                 valid, planar, host_view)
+    p = _splat_params(what, z_near=z_near, z_tol=z_tol, w_tap=w_tap, value_bound=value_bound)
+    _splat_ws_ok(what, zbuf, acc, points.device, V, C, H, W)
+    _lib.check(_lib.load().dvd_splat_accumulate(_p(points), int(bool(planar)), _p(values), _p(valid), _p(view), _p(R), _p(t),
+                                                _p(K_T), V, _p(zbuf), _p(acc), S, C, H, W, p['z_near'], p['z_tol'], p['w_tap'],
+                                                p['value_bound'], int(shift), int(n_max), _stream()), 'dvd_splat_accumulate')
+
+
+def splat_resolve(zbuf, acc, shift, w_min=0.25, value_bound=1.0, fill=0.0, out=None):
+    """Pass c of the splat (dvd_splat_resolve) -> dict of image [V,C,H,W], depth [V,1,H,W], weight [V,1,H,W], hit uint8 [V,H,W]."""
+    what = 'splat_resolve'
+    if not (torch.is_tensor(acc) and acc.is_cuda and acc.dim() == 4):
+        raise RuntimeError('%s: acc must be a GPU tensor [V,H,W,C+1] (dvd_hip has no CPU path)' % what)
+    V, H, W, C = (int(v) for v in acc.shape)
+    C -= 1
+    _splat_ws_ok(what, zbuf, acc, acc.device, V, C, H, W)
+    p = _splat_params(what, w_min=w_min, value_bound=value_bound, fill=fill)
+    shapes = {'image': ((V, C, H, W), torch.float32), 'depth': ((V, 1, H, W), torch.float32),
+              'weight': ((V, 1, H, W), torch.float32), 'hit': ((V, H, W), torch.uint8)}
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        o = out.get(k) if out is not None else None
+        if o is None:
+            o = torch.empty(shape, device=acc.device, dtype=dtype)
+        elif not (torch.is_tensor(o) and o.device == acc.device and o.dtype == dtype and tuple(o.shape) == shape and
+                  o.is_contiguous()):
+            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the workspace' % (what, k, dtype, shape))
+        res[k] = o
+    _lib.check(_lib.load().dvd_splat_resolve(_p(zbuf), _p(acc), V, C, H, W, int(shift), p['w_min'], p['value_bound'], p['fill'],
+                                             _p(res['image']), _p(res['depth']), _p(res['weight']), _p(res['hit']), _stream()),
+               'dvd_splat_resolve')
+    return res
+
+
+def splat(points, values, view, tables, n_views, valid=None, planar=True, z_near=1e-3, z_tol=0.05, w_tap=1.0 / 64, w_min=0.25,
+          value_bound=1.0, fill=0.0, out=None, host_view=None):
+    """Forward bilinear splat with a soft z-buffer (csrc/splat.hip) -> dict of image [V,C,H,W], depth [V,1,H,W], weight
+    [V,1,H,W] and hit uint8 [V,H,W], V = n_views.
+      points   [S,3,H,W] (planar) or [S,H,W,3] world points;  values [S,C,H,W], 1 <= C <= 8;  valid uint8 [S,H,W] or None
+      view     S view ids: a host sequence / array / CPU tensor (uploaded here) or a GPU int32 tensor (never read back; with
+               host_view, its host copy, the accumulators keep more fraction bits).  -1 or >= n_views skips the image.
+      tables   {'R': [V,3,3] world->camera, 't': [V,3], 'K_T': [V,3,3]}: the rows of the V views
+      z_near   points at or in front of it are dropped;  z_tol: a tap is blended if z <= zmin * (1 + z_tol)
+      w_tap    the least bilinear weight with which a tap counts;  w_min: the least summed weight of a hit pixel
+      value_bound  values are clamped to +-value_bound;  fill: the image where nothing hit
+    Allocates the workspace with torch, clears it and runs the three passes on the current stream.  Integer atomics only:
+    the same inputs give the same bits whatever the order of the sources."""
+    what = 'splat'
+    points, values, valid, view, tabs, S, C, H, W, V, n_max = _splat_sources(what, points, values, view, tables, n_views, valid,
+                                                                             planar, host_view)
+    _splat_params(what, z_near=z_near, z_tol=z_tol, w_tap=w_tap, w_min=w_min, value_bound=value_bound, fill=fill)
+    tables = dict(zip(TRACK_TABLES, tabs))
+    shift = splat_shift(n_max)
+    zbuf, acc = splat_workspace(V, C, H, W, points.device)
+    splat_clear(zbuf, acc)
+    splat_zmin(zbuf, points, values, view, tables, V, valid=valid, planar=planar, z_near=z_near, w_tap=w_tap)
+    splat_accumulate(zbuf, acc, shift, n_max, points, values, view, tables, V, valid=valid, planar=planar, z_near=z_near,
+                     z_tol=z_tol, w_tap=w_tap, value_bound=value_bound)
+    return splat_resolve(zbuf, acc, shift, w_min=w_min, value_bound=value_bound, fill=fill, out=out)
+
+
 # -- max|x| scalars ----------------------------------------------------------------------------------------------------
 # Every tensor that feeds a matrix kernel carries max|x| (or an upper bound) in a 1-element GPU tensor: the kernels derive
 # the power-of-two scale of their fp16 operand split from it on the device (csrc/dvd_split.h); the host never reads it.
@@ -402,7 +598,8 @@ BYTE_CLASS_KERNELS = {
     'amax': ('amax_kernel', 'chansum_'), 'pack': ('xconv_wamax', 'xconv_pack_kernel'), 'pool': ('maxpool3s2', 'subsample2_', 'avgpool_'),
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
-    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+    'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
+                                                   'splat_resolve_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

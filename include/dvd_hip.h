@@ -775,6 +775,51 @@ int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, c
                     const float* t, const float* K_T, int N, float* g_points, int accumulate, int T1, int B, int H, int W,
                     dvd_stream_t stream);
 
+/* Forward splat of world points into target cameras with a soft z-buffer (additions within ABI 8; csrc/splat.hip,
+ * models/render.py): the scatter that goes with dvd_track_project's gather.  It draws a frame, pushed along the scene-flow
+ * field by the Euler chain of Model.forward_sf_net_multi_step (models/scene_flow_motion_field.py:360-367), in the camera of
+ * another frame or in one that never existed; the projection is project_ptcld.forward
+ * (losses/scene_flow_projection.py:27-44) through the same device function as dvd_track_project.
+ *   points     [S, 3, H, W] (points_planar != 0) or [S, H, W, 3]: world points of S source images
+ *   values     [S, C, H, W], 1 <= C <= 8: what is drawn (colours)
+ *   valid      uint8 [S, H, W] or NULL: a zero byte drops the point
+ *   view       DEVICE array of S ints: the target view of every source image; < 0 or >= V skips the image (nothing of it is
+ *              read, nothing written).  Any number of images may share a view.
+ *   R, t, K_T  the camera tables of the V views, [V, 3, 3], [V, 3], [V, 3, 3], as dvd_track_project takes them
+ *   zbuf       unsigned int [V, H, W], cleared to 0xFF bytes by the caller;  acc  unsigned long long [V, H, W, C + 1],
+ *              cleared to 0 by the caller.  dvd_splat_workspace_bytes(V, C, H, W) is the size of both together (0 for sizes
+ *              the entries refuse); it needs no GPU.
+ * Per point I = ((P - t_v) @ R_v) @ K_T_v, z = I.z, (u, v) = I.xy / (z + 1e-8).  The point is live iff its valid byte is
+ * non-zero, every value is finite, z > z_near, z is finite, -1 < u < W and -1 < v < H -- decided in float before any
+ * conversion to an integer, so no index derived from the data leaves the image.  Its taps are (floor u + i, floor v + j),
+ * i, j in {0, 1}, with the bilinear weights w; a tap counts iff it is inside the image and w >= w_tap.
+ *   dvd_splat_zmin        zbuf <- min over the counting taps of the bit pattern of z (integer atomicMin; z > 0)
+ *   dvd_splat_accumulate  a counting tap with z <= zmin * (1 + z_tol) adds llrintf(ldexpf(x, shift)) for x = w and for
+ *                         x = w * clamp(c, +-value_bound) / value_bound per channel to the pixel's words of acc (64-bit integer
+ *                         atomicAdd, two's complement).  n_max: the caller's bound on the number of points one view receives
+ *                         over ALL accumulate calls into this workspace; shift + ceil_log2(n_max) <= 62 is required, which
+ *                         makes overflow impossible (every term is at most 2^shift in magnitude).  May be called several
+ *                         times (chunks of source images) between one dvd_splat_zmin pass over all of them and the resolve.
+ *   dvd_splat_resolve     per target pixel: weight [V,1,H,W] = acc_w * 2^-shift; hit uint8 [V,H,W] = weight >= w_min; image
+ *                         [V,C,H,W] = value_bound * acc_c / acc_w where hit, else fill; depth [V,1,H,W] = zmin where hit, else
+ *                         0.  Plain stores, one writer per element; 4 pixels per thread where W % 4 == 0 and the bases are
+ *                         16-byte aligned.
+ * Integer min and add commute: the result is bitwise independent of source order, launch order and run.  Refused with
+ * DVD_EINVAL before any HIP call: a null pointer, C outside 1..8, H or W < 2, S or V outside 1..65535, z_near < 0, z_tol < 0,
+ * w_tap outside (0, 0.25], w_min <= 0, value_bound <= 0, shift outside 1..40 or too large for n_max.  Bytes are counted
+ * under DVD_BYTES_GEOMETRY. */
+size_t dvd_splat_workspace_bytes(int V, int C, int H, int W);
+int dvd_splat_zmin(const float* points, int points_planar, const float* values, const unsigned char* valid, const int* view,
+                   const float* R, const float* t, const float* K_T, int V, unsigned int* zbuf, int S, int C, int H, int W,
+                   float z_near, float w_tap, dvd_stream_t stream);
+int dvd_splat_accumulate(const float* points, int points_planar, const float* values, const unsigned char* valid,
+                         const int* view, const float* R, const float* t, const float* K_T, int V, const unsigned int* zbuf,
+                         unsigned long long* acc, int S, int C, int H, int W, float z_near, float z_tol, float w_tap,
+                         float value_bound, int shift, long long n_max, dvd_stream_t stream);
+int dvd_splat_resolve(const unsigned int* zbuf, const unsigned long long* acc, int V, int C, int H, int W, int shift,
+                      float w_min, float value_bound, float fill, float* image, float* depth, float* weight,
+                      unsigned char* hit, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
