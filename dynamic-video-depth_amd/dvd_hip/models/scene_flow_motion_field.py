@@ -24,6 +24,11 @@ What is different is HOW a step runs.  The reference builds one autograd graph o
      backward graph (or a forward+backward recompute graph); then one RCCL all-reduce per net over its flat gradient
      buffer and one fused optimiser launch per net (Adam, or SGD under --optim sgd).
 
+`Model._train_on_batch` is that list: the step's plan, its image sets and phase 1 (models/depth_runner.py),
+`SfStep(...).run(schedule)` for phase 2, `Model._finish_step` for phase 3.  The plan (Euler steps per pair, gap groups, MLP
+chunks, what phase 2 will allocate), the choice between phase 2's four schedules and the schedules themselves live in
+models/sf_step.py; the Model is not an argument to anything there.
+
 Every convolution (the 7x7 stride-2 stem included, round 4), BatchNorm+ReLU, pooling, up-sampling and the MLP run on this
 package's HIP kernels (csrc/); the matrix kernels evaluate fp32 products from two fp16 terms per operand (csrc/dvd_split.h).
 `--act_fp16` (BASELINE configs[4]) stores the depth net's activations and their gradients as fp16 (csrc/a16.hip: the loss scale
@@ -45,308 +50,12 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import frame_union, render, tracks
+from . import frame_union, render, sf_step, tracks
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
+from .sf_step import gap_plan, pairs_per_chunk      # noqa: F401 (re-exported)
 
 CAM_KEYS = ops.CAM_KEYS
-
-
-def pairs_per_chunk(B, budget_bytes, stash_bytes, gstash_bytes, steps, with_reg):
-    """Pairs that go through the scene-flow MLP kernels at once: what --mlp_stash_gb (`budget_bytes`) holds of one pair's
-    activation stashes (`stash_bytes` per Euler evaluation; the regulariser needs two) and backward scratch (`gstash_bytes`)."""
-    per_pair = stash_bytes * max(steps, 2 if with_reg else 1) + gstash_bytes
-    return int(max(1, min(B, budget_bytes // per_pair)))
-
-
-def gap_plan(steps_per_pair, budget_bytes, stash_bytes, gstash_bytes, with_reg):
-    """The schedule of a step whose pairs differ in frame gap.  steps_per_pair: Euler steps of every pair, in the caller's
-    order.  Returns a dict:
-      perm    the gap-grouped order: pairs sorted by their step count, stable (grouped[j] = caller[perm[j]]);
-      groups  [(b0, b1, steps)] over the grouped order, one per distinct step count, ascending;
-      chunks  [(b0, b1, steps)]: what goes through the MLP kernels at once -- pairs_per_chunk(...) pairs of ONE group, never
-              across a group boundary;
-      whole_bytes  stashes of a step that keeps every forward stash until its backward (sum_b steps_b stashes + the backward
-                   scratch of the largest chunk + the regulariser's extra stash for the largest gap-1 chunk);
-      chunk_bytes  stashes of the most expensive single chunk (late-normaliser / recompute schedules).
-    A list whose entries are all equal gives ONE group, the identity permutation and the chunk list and byte figures of a
-    uniform-gap step."""
-    steps_per_pair = [int(v) for v in steps_per_pair]
-    B = len(steps_per_pair)
-    perm = sorted(range(B), key=lambda b: steps_per_pair[b])        # sorted() is stable
-    groups, chunks = [], []
-    b0 = 0
-    while b0 < B:
-        st = steps_per_pair[perm[b0]]
-        b1 = b0
-        while b1 < B and steps_per_pair[perm[b1]] == st:
-            b1 += 1
-        groups.append((b0, b1, st))
-        Bc = pairs_per_chunk(B, budget_bytes, stash_bytes, gstash_bytes, st, with_reg)
-        chunks.extend((c0, min(b1, c0 + Bc), st) for c0 in range(b0, b1, Bc))
-        b0 = b1
-    longest = max(c1 - c0 for c0, c1, _ in chunks)
-    longest_gap1 = max([c1 - c0 for c0, c1, st in chunks if st == 1] or [0]) if with_reg else 0
-    whole = sum(steps_per_pair) * stash_bytes + longest * gstash_bytes + longest_gap1 * stash_bytes
-    chunk = max((c1 - c0) * (stash_bytes * max(st, 2 if with_reg else 1) + gstash_bytes) for c0, c1, st in chunks)
-    return {'perm': perm, 'groups': groups, 'chunks': chunks, 'whole_bytes': whole, 'chunk_bytes': chunk}
-
-
-class _SfStep:
-    """Phase 2 of `Model._train_on_batch` (geometry + scene-flow network + losses, forward and backward): what its pieces share
-    for ONE step, and the three schedules the MLP's activation stashes allow.  Per-chunk data (stashes, backward scratch) stay
-    locals of the schedule methods: they bound the step's peak HBM; the object itself does not outlive the step."""
-    def __init__(self, model, inp, depth_1, depth_2, steps, time_step, warm, do_reg, groups):
-        opt = self.opt = model.opt
-        self.inp, self.mlp, self.flat_sf, self.sf_grad_main = inp, model._mlp, model._flat_sf, model._sf_grad_main
-        self.depth_1, self.depth_2 = depth_1, depth_2
-        self.steps, self.time_step, self.warm, self.do_reg = steps, time_step, warm, do_reg
-        B, _, H, W = inp.img_1.shape
-        self.B, self.H, self.W, self.HW = B, H, W, H * W
-        # frame gaps (gap_plan's groups): one group (0, B, steps) for a uniform batch; a mixed batch is in gap-grouped order and
-        # `steps` is its largest count -- every chunk of the MLP path carries its own
-        self.groups = groups
-        self.mixed = len(self.groups) > 1
-        # --weight_steps (:189-190): a uniform batch scales flow_mul / disp_mul of the ONE warp+loss launch and divides the
-        # logged loss again; a mixed batch weights per gap group (group_mul) and logs the unweighted sums as they are
-        self.mul = steps if (opt.weight_steps and not self.mixed) else 1
-        self.disp_mode = 1 if opt.use_disp else (2 if opt.use_disp_ratio else 0)
-        self.sums = torch.zeros(8, device=model.device)            # [S0..S3, sum|sf1-sf0|, 0, 0, 0]
-        self.g_d1_main, self.g_d2_main = torch.empty_like(depth_1), torch.empty_like(depth_2)
-        self.g_d1_reg = self.sf_all = self.g_sf_all = None    # allocated by run_late only / by begin_mlp or the U-Net path
-        self.inv_div = 1.0 / opt.sf_mag_div
-        self.mask_2 = inp.mask_2.reshape(B, H, W)
-        # --use_motion_seg (:253-254): the integrated scene flow is multiplied by motion_seg_1 before the
-        # warp; the un-masked field still drives the Euler chain and the regulariser
-        self.mseg = inp.motion_seg_1.reshape(B, H, W) if opt.use_motion_seg else None
-        self.cfg_all = self.warp_cfg(B)
-        self.union = None            # opt.share_frames: (index tables, img_u, fid_u) of phase 1, for phase 3
-
-    def warp_cfg(self, n_pairs, mul=None):
-        opt = self.opt
-        mul = self.mul if mul is None else mul
-        return ops.warp_cfg(n_pairs, self.H, self.W, midas_mask=opt.midas, crit_l2=self.warm, disp_mode=self.disp_mode,
-                            loss_on_sf=not opt.use_disp, flow_mul=opt.flow_mul * mul, disp_mul=opt.disp_mul * mul)
-
-    def group_mul(self, steps):
-        """--weight_steps in a mixed batch: the gradient weight of a pair with `steps` Euler steps (else None = self.mul)."""
-        return steps if (self.opt.weight_steps and self.mixed) else None
-
-    def set_global_batch(self, n_global):
-        """n_global: pairs of ALL ranks (parallel.agree_on_step_plan); the regulariser is a mean over them."""
-        self.n_global = n_global
-        self.reg_coef = self.opt.acc_mul / (3.0 * n_global * self.HW + 1e-6)
-
-    def begin_mlp(self, Bc, chunks):
-        """The MLP path's batch-wide tensors.  chunks: gap_plan's (b0, b1, steps) list -- what goes through the MLP kernels at
-        once; no chunk crosses a gap group --, Bc its longest chunk."""
-        k, B, inp = self.flat_sf, self.B, self.inp
-        self.gW_main = [k.view(self.sf_grad_main, 2 * i) for i in range(6)]
-        self.gb_main = [k.view(self.sf_grad_main, 2 * i + 1) for i in range(6)]
-        self.gW_reg = [k.view(k.grad, 2 * i) for i in range(6)]
-        self.gb_reg = [k.view(k.grad, 2 * i + 1) for i in range(6)]
-        self.Bc = Bc
-        self.chunks = list(chunks)
-        self.P1_all = ops.unproject(self.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True)
-        self.sf_all = torch.zeros(B, 3, self.H, self.W, device=self.depth_1.device)
-        self.g_sf_all = torch.empty_like(self.sf_all)
-
-    def mlp_forward_chunk(self, b0, b1, steps, keep_first=None, acc=None, with_stash=True):
-        """Euler integration of the scene flow over `steps` frames (:360-367).  keep_first: also
-        return sf_0 and q = P1 + sf_0 of the first evaluation (the regulariser's sf_0, see below).
-        acc: the tensor the integrated flow is accumulated into (default: this chunk of sf_all); with_stash=False: no
-        activation stashes (the first pass of the recompute schedule)."""
-        mlp = self.mlp
-        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
-        n_pix = (b1 - b0) * self.HW
-        stashes, p_cur, first = [], self.P1_all[b0:b1], None
-        acc = self.sf_all[b0:b1] if acc is None else acc
-        for i in range(steps):
-            st = mlp.new_stash(n_pix) if with_stash else None
-            want_next = i + 1 < steps or (keep_first and i == 0)
-            p_next = torch.empty_like(p_cur) if want_next else None
-            # the regulariser's two evaluations ARE Euler evaluations 0 and 1 (see merged_backward_chunk): keep their
-            # outputs (evaluation 0's only when it is not the accumulated flow itself)
-            sf_i = torch.empty_like(p_cur) if (keep_first and i < 2 and steps > 1) else None
-            mlp.forward(p_cur, ts, t_offset=i * self.time_step, out_scale=self.inv_div, sf_out=sf_i, p_next=p_next,
-                        acc=acc, stash=st)
-            if keep_first and i == 0:
-                first = [sf_i, p_next, None]    # sf_i is None when steps == 1: sf_0 is the accumulated flow itself
-            if keep_first and i == 1:
-                first[2] = sf_i                 # sf_1 = MLP(P1 + sf_0, t_1 + dt)
-            stashes.append(st)
-            p_cur = p_next
-        return (stashes, first) if keep_first is not None else stashes
-
-    def warp(self, b0, b1, mul=None):
-        inp, mseg = self.inp, self.mseg
-        sf_used = self.sf_all[b0:b1]
-        if mseg is not None:
-            sf_used = ops.mul_mask(torch.empty_like(sf_used), sf_used, mseg[b0:b1])
-        cfg = self.cfg_all if ((b0, b1) == (0, self.B) and mul is None) else self.warp_cfg(b1 - b0, mul)
-        csum = torch.empty(4, device=self.sums.device)
-        ops.warp_loss_fused(cfg, self.depth_1[b0:b1], self.depth_2[b0:b1], inp.flow_1_2[b0:b1], self.mask_2[b0:b1],
-                            sf_used, {kk: getattr(inp, kk)[b0:b1] for kk in CAM_KEYS},
-                            out=(csum, self.g_d1_main[b0:b1], self.g_d2_main[b0:b1], self.g_sf_all[b0:b1]))
-        if mseg is not None:
-            ops.mul_mask(self.g_sf_all[b0:b1], self.g_sf_all[b0:b1], mseg[b0:b1])
-        self.sums[:4] += csum
-
-    def mlp_backward_chunk(self, b0, b1, steps, stashes, gst):
-        """Backward through the Euler chain: g_p_i = g_p_{i+1} + J_i^T (g_acc + g_p_{i+1})."""
-        mlp, inv_div, gW_main, gb_main = self.mlp, self.inv_div, self.gW_main, self.gb_main
-        nb, n_pix = b1 - b0, (b1 - b0) * self.HW
-        g_p = None
-        for i in reversed(range(steps)):
-            g_new = torch.empty_like(self.P1_all[b0:b1])
-            mlp.backward_dx(stashes[i], inv_div, self.g_sf_all[b0:b1], g_new, gst, gW_main[5], gb_main[5], (nb, self.H, self.W),
-                            g_out2=g_p, g_p_add=g_p)
-            mlp.backward_dw(stashes[i], gst, n_pix, gW_main[:5], gb_main[:5])
-            g_p = g_new
-        ops.unproject_backward(g_p, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_main[b0:b1], accumulate=True)
-
-    def reg_chunk(self, b0, b1, gst):
-        """Acceleration regulariser (:326-344), P1 un-detached."""
-        mlp, inv_div, gW_reg, gb_reg, sums = self.mlp, self.inv_div, self.gW_reg, self.gb_reg, self.sums
-        n_pix, shape = (b1 - b0) * self.HW, (b1 - b0, self.H, self.W)
-        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
-        P1 = self.P1_all[b0:b1]
-        sa, sb = mlp.new_stash(n_pix), mlp.new_stash(n_pix)
-        sf0, sf1, q = torch.empty_like(P1), torch.empty_like(P1), torch.empty_like(P1)
-        mlp.forward(P1, ts, 0.0, inv_div, sf_out=sf0, p_next=q, stash=sa)
-        mlp.forward(q, ts, self.time_step, inv_div, sf_out=sf1, stash=sb)
-        g1 = torch.empty_like(P1)
-        ops.acc_reg(sf0, sf1, self.reg_coef, g1, sums[4:5], accumulate=True)
-        g_q = torch.empty_like(P1)
-        mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], shape)
-        mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
-        g_P = torch.empty_like(P1)
-        mlp.backward_dx(sa, inv_div, g1, g_P, gst, gW_reg[5], gb_reg[5], shape, gscale=-1.0, g_out2=g_q, g_p_add=g_q)
-        mlp.backward_dw(sa, gst, n_pix, gW_reg[:5], gb_reg[:5])
-        ops.unproject_backward(g_P, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_reg[b0:b1])
-
-    def merged_backward_chunk(self, b0, b1, steps, stashes, first, gst, inv):
-        """Main loss and acceleration regulariser through ONE backward of the first evaluation.
-
-        The regulariser's sf_0 = MLP(P1, t_1) (:329-333) is the first Euler evaluation of the main
-        path (:360-367: same points, same time, same weights), so its forward, stash, dX and dW
-        passes are shared: with G = inv * g_sf (main, late normaliser already known) the first
-        evaluation receives  G + g_p1 - g1 + g_q  where g1 = dR/dsf_1, g_q = J_b^T g1, and
-        g_P1 = g_p1 + g_q + J_0^T(...).  One MLP evaluation per step less than the reference.
-        From gap 2 on the regulariser's sf_1 = MLP(P1 + sf_0, t_1 + dt) (:335-338) is Euler evaluation 1 as well
-        (:360-367), so that one is shared too (round 4): evaluation 1 receives G + g_p2 + g1, and a gap-k step costs k
-        evaluations instead of the reference's k + 2."""
-        mlp, do_reg, inv_div, sums, reg_coef = self.mlp, self.do_reg, self.inv_div, self.sums, self.reg_coef
-        gW_reg, gb_reg = self.gW_reg, self.gb_reg
-        n_pix, shape = (b1 - b0) * self.HW, (b1 - b0, self.H, self.W)
-        ts = self.inp.time_stamp_1[b0:b1] if self.opt.time_dependent else None
-        P1, g_sf = self.P1_all[b0:b1], self.g_sf_all[b0:b1]
-        g_q = g1 = None
-        shared1 = do_reg and steps > 1      # the regulariser's second evaluation is Euler evaluation 1 as well (:335-338 = :360-367)
-        if do_reg:
-            sf0 = first[0] if first[0] is not None else self.sf_all[b0:b1]
-            g1 = torch.empty_like(P1)
-            if shared1:
-                ops.acc_reg(sf0, first[2], reg_coef, g1, sums[4:5], accumulate=True)
-            else:
-                sb, sf1 = mlp.new_stash(n_pix), torch.empty_like(P1)
-                mlp.forward(first[1], ts, self.time_step, inv_div, sf_out=sf1, stash=sb)
-                ops.acc_reg(sf0, sf1, reg_coef, g1, sums[4:5], accumulate=True)
-                g_q = torch.empty_like(P1)
-                mlp.backward_dx(sb, inv_div, g1, g_q, gst, gW_reg[5], gb_reg[5], shape)
-                mlp.backward_dw(sb, gst, n_pix, gW_reg[:5], gb_reg[:5])
-                del sb, sf1
-        g_p = None
-        for i in reversed(range(1, steps)):
-            g_new = torch.empty_like(P1)
-            g_o2 = g_p
-            if shared1 and i == 1:          # evaluation 1's output also feeds the regulariser: + dR/dsf_1 (not normalised)
-                g_o2 = g1 if g_p is None else ops.scale_add(torch.empty_like(P1), g1, b=g_p)
-            mlp.backward_dx(stashes[i], inv_div, g_sf, g_new, gst, gW_reg[5], gb_reg[5], shape, scale_ptr=inv,
-                            g_out2=g_o2, g_p_add=g_p)
-            mlp.backward_dw(stashes[i], gst, n_pix, gW_reg[:5], gb_reg[:5])
-            g_p = g_new
-        extra, add = g_p, g_p                    # gradient reaching sf_0 besides G, and reaching P1 directly
-        if shared1:                              # g_p already holds everything that reaches q = P1 + sf_0
-            extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_p)          # g_p - g1
-        elif do_reg:
-            extra = ops.scale_add(torch.empty_like(P1), g1, scale=-1.0, b=g_q)          # -g1 + g_q
-            add = g_q
-        g_P = torch.empty_like(P1)
-        mlp.backward_dx(stashes[0], inv_div, g_sf, g_P, gst, gW_reg[5], gb_reg[5], shape, scale_ptr=inv,
-                        g_out2=extra, g_p_add=add)
-        mlp.backward_dw(stashes[0], gst, n_pix, gW_reg[:5], gb_reg[:5])
-        ops.unproject_backward(g_P, True, self.inp.R_1[b0:b1], self.inp.K_inv[b0:b1], out=self.g_d1_main[b0:b1], accumulate=True)
-
-    def normaliser(self, sums):
-        """All-reduce the loss sums -> the loss scalars and inv = 1/(S0+1e-8) as a device scalar."""
-        parallel.all_reduce_sum_(sums)
-        scalars = ops.loss_finalize(self.cfg_all, self.sums)
-        return scalars, scalars[0:1]
-
-    def warp_whole_batch(self):
-        """ONE warp+loss launch over all pairs.  The batch-global normaliser is then known before the scene-flow network's
-        backward: all-reduce the four loss sums now and hand inv to the backward kernels as a device scalar."""
-        if self.mixed and self.opt.weight_steps:
-            # per-pair weights: one launch per gap group, its flow_mul / disp_mul times the group's step count (the gradients
-            # carry the weight); the loss sums are added as they are -- the logged losses are the unweighted ones (:226)
-            for b0, b1, st in self.groups:
-                self.warp(b0, b1, self.group_mul(st))
-        else:
-            self.warp(0, self.B)
-        scalars, inv = self.normaliser(self.sums[:4])
-        ops.scale_add(self.g_d1_main, self.g_d1_main, scale_ptr=inv)
-        return scalars, inv
-
-    def run_whole_batch(self):
-        """Schedule 1 of 3 (each returns (scalars, inv)): the forward stashes of the whole batch stay alive until the backward."""
-        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
-        kept = [self.mlp_forward_chunk(b0, b1, n, keep_first=bool(self.do_reg)) for b0, b1, n in self.chunks]
-        scalars, inv = self.warp_whole_batch()
-        for (b0, b1, n), (st, first) in zip(self.chunks, kept):
-            self.merged_backward_chunk(b0, b1, n, st, first, gst, inv)
-            del st[:]
-        del kept
-        parallel.all_reduce_sum_(self.sums[4:])
-        return scalars, inv
-
-    def run_recompute(self):
-        """Round 6: when the forward stashes of the whole batch do NOT fit (BASELINE configs[4]: 64 pairs at 768 x 1344 = 211 GB
-        of stashes), the late-normaliser schedule costs 3 forward + 3 dX + 3 dW passes per pair and Euler step -- the
-        regulariser cannot share the main path's backward while the normaliser is unknown.  The RECOMPUTE schedule runs the
-        Euler chain once WITHOUT stashes for every pair (the cheapest form of the forward kernel), one warp+loss launch over
-        the whole batch, and then per chunk the stashed forward again + the merged backward: 3 forward + 2 dX + 2 dW at
-        gap 1 (2k + k + k instead of (k + 2) x 3 at gap k), same arithmetic as the whole-batch schedule (the recomputed
-        evaluations are bit-identical: the forward kernel is deterministic).  --mlp_recompute 0 restores the late schedule."""
-        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
-        with ops.counting_recomputed():          # the stashed evaluations below are the ones the backward needs
-            for b0, b1, n in self.chunks:
-                self.mlp_forward_chunk(b0, b1, n, with_stash=False)
-        scalars, inv = self.warp_whole_batch()
-        for b0, b1, n in self.chunks:
-            # the same evaluations again, stashed; their flow goes to a scratch accumulator (sf_all already holds it)
-            st, first = self.mlp_forward_chunk(b0, b1, n, keep_first=bool(self.do_reg), acc=torch.zeros_like(self.sf_all[b0:b1]))
-            self.merged_backward_chunk(b0, b1, n, st, first, gst, inv)
-            del st[:], first
-        parallel.all_reduce_sum_(self.sums[4:])
-        return scalars, inv
-
-    def run_late(self):
-        """Per-chunk warp+loss launches (--mlp_recompute 0, or another rank needs it): the batch-global normaliser only exists
-        after the last chunk; main-path gradients stay un-normalised in buffers of their own, the regulariser runs apart."""
-        gst = self.mlp.new_gstash(min(self.Bc, self.B) * self.HW)
-        self.g_d1_reg = torch.zeros_like(self.depth_1) if self.do_reg else None
-        for b0, b1, n in self.chunks:
-            st = self.mlp_forward_chunk(b0, b1, n)
-            self.warp(b0, b1, self.group_mul(n))
-            self.mlp_backward_chunk(b0, b1, n, st, gst)
-            del st
-            if self.do_reg:
-                self.reg_chunk(b0, b1, gst)
-        del gst
-        scalars, inv = self.normaliser(self.sums)
-        ops.scale_add(self.flat_sf.grad, self.sf_grad_main, scale_ptr=inv, b=self.flat_sf.grad)   # MLP gradient = inv * main + reg
-        return scalars, inv
 
 
 def midas_resize_of(opt):
@@ -551,86 +260,6 @@ class Model(NetInterface):
         return self._depth.graphs if self._depth is not None else {}
 
     # ------------------------------------------------------------------------------------
-    def _plan_step(self, steps_per_pair, HW, do_reg):
-        """The ONE plan of a step, uniform gaps or mixed: gap_plan with this model's stash sizes and --mlp_stash_gb, and
-          reserve  what phase 2 will allocate (the room phase 1 leaves free): the MLP stashes of the whole batch if they are one
-                   chunk or fit --mlp_whole_batch_gb, else those of ONE chunk (late-normaliser / recompute schedules).  (Rounds
-                   1-5 reserved min(whole batch, the ceiling) in the chunked case too: 160 GB for 48 GB of stashes at BASELINE
-                   configs[4]'s 64 pairs, and not one depth-net slot was kept there.)
-          Bc       the longest chunk (B if there is one chunk);
-          whole    several chunks, but the forward stashes of the whole batch fit and stay alive until the backward."""
-        B = len(steps_per_pair)
-        if self._mlp is None:
-            # --use_cnn: the whole batch goes through the U-Net at once (the plan gives the gap groups only); its autograd
-            # state per pixel and evaluation is measured: one evaluation per pair and Euler step, + the regulariser's
-            plan = gap_plan(steps_per_pair, 1.0, 1, 0, do_reg)
-            need = HW * self._cnn_bytes_per_px() * (sum(steps_per_pair) + (B if do_reg else 0))
-        else:
-            plan = gap_plan(steps_per_pair, self.opt.mlp_stash_gb * 2 ** 30, self._mlp.stash_floats(HW) * 4,
-                            self._mlp.gstash_floats(HW) * 4, do_reg)
-            one = len(plan['chunks']) == 1
-            fits = plan['whole_bytes'] <= float(getattr(self.opt, 'mlp_whole_batch_gb', 160.0)) * 2 ** 30
-            plan['Bc'] = B if one else max(b1 - b0 for b0, b1, _ in plan['chunks'])
-            plan['whole'] = fits and not one
-            need = plan['whole_bytes'] if (one or fits) else plan['chunk_bytes']
-        plan['reserve'] = need + 24 * B * HW * 4
-        return plan
-
-    def _integer_steps(self, batch_or_input):
-        """Euler steps of this batch = round(mean(ts2 - ts1) / time_step) (:248-250), recomputed every step:
-        consecutive batches mix frame gaps and allocators reuse addresses, so nothing about the tensors'
-        identity says the gap is unchanged (one tiny reduction + read-back per 2 s step)."""
-        ts1, ts2 = batch_or_input['time_stamp_1'], batch_or_input['time_stamp_2']
-        step = batch_or_input['time_step']
-        time_step = float(step.squeeze().item()) if torch.is_tensor(step) else float(step)
-        gap = torch.mean(ts2.float() - ts1.float())
-        return int((gap / time_step).round().long().item()), time_step
-
-    def _batch_frame_ids(self, batch, B):
-        """opt.share_frames: the frame ids of the batch's two image sets as ONE float tensor [2B] (ids are whole numbers far
-        below 2^24, exact in fp32), from `fid_1` / `fid_2` (frame-store items) or `frame_id_1` / `frame_id_2` (pair packs)."""
-        for k1, k2 in (('fid_1', 'fid_2'), ('frame_id_1', 'frame_id_2')):
-            if k1 in batch and k2 in batch:
-                ids = [torch.as_tensor(batch[k]).reshape(-1) for k in (k1, k2)]
-                if ids[0].numel() != B or ids[1].numel() != B:
-                    raise ValueError('opt.share_frames: %s / %s hold %d / %d ids for %d pairs' % (
-                        k1, k2, ids[0].numel(), ids[1].numel(), B))
-                return ids
-        raise ValueError('opt.share_frames needs the frame id of every image: the batch has neither fid_1 / fid_2 nor '
-                         'frame_id_1 / frame_id_2 (its keys: %s)' % sorted(batch))
-
-    def _steps_per_pair(self, batch, with_ids=False):
-        """(steps, steps_per_pair, time_step, ids): the Euler steps of every pair, round((ts2[b] - ts1[b]) / time_step) -- time
-        stamps are constant per pair (datasets/davis_sequence.py) --, in the caller's order, with ONE device-to-host read.
-        steps: for a uniform batch exactly _integer_steps' value (the rounded mean gap, :248-250), else the largest count.
-        with_ids (opt.share_frames): the same read also brings the frame ids of the two image sets, ids = (f1, f2) as lists of
-        ints in the caller's order; else ids is None."""
-        ts1, ts2, step = batch['time_stamp_1'], batch['time_stamp_2'], batch['time_step']
-        time_step = float(step.squeeze().item()) if torch.is_tensor(step) else float(step)
-        d = ts2.float() - ts1.float()
-        B = int(d.shape[0]) if d.dim() > 0 else 1
-        parts = [(d.reshape(B, -1)[:, 0] / time_step).round(), (torch.mean(d) / time_step).round().reshape(1)]
-        if with_ids:
-            parts += [t.to(d.device, non_blocking=True).float() for t in self._batch_frame_ids(batch, B)]
-        both = torch.cat(parts).tolist()
-        ids = None
-        if with_ids:
-            raw, both = both[B + 1:], both[:B + 1]
-            if not all(np.isfinite(raw)) or any(v != int(v) or v < 0 or v >= 2 ** 24 for v in raw):
-                raise ValueError('opt.share_frames: frame ids must be whole numbers in [0, 2^24), got %s' % (raw,))
-            ids = ([int(v) for v in raw[:B]], [int(v) for v in raw[B:]])
-        if not all(np.isfinite(both)):          # (the uniform path keeps whatever it does with such time stamps)
-            steps = self._integer_steps(batch)[0]
-            return steps, [steps] * B, time_step, ids
-        per_pair, mean = [int(v) for v in both[:B]], int(both[B])
-        if all(v == per_pair[0] for v in per_pair):
-            return mean, [mean] * B, time_step, ids
-        for b, v in enumerate(per_pair):
-            if v < 1:
-                raise ValueError('pair %d of a batch that mixes frame gaps has time stamps %g frames apart (%d Euler steps): '
-                                 'every pair needs at least one' % (b, float(ts2[b].flatten()[0] - ts1[b].flatten()[0]) / time_step, v))
-        return max(per_pair), per_pair, time_step, ids
-
     def _group_input(self, perm):
         """Bring the loaded batch (self._input) into gap-grouped order: ONE dvd_gather_pairs launch over every per-pair
         tensor.  The caller's batch dict is not touched; exports go back through the inverse (_caller_order)."""
@@ -657,15 +286,6 @@ class Model(NetInterface):
         out.update(zip(keys, ops.gather_pairs([tensors[k] for k in keys], inv)))
         return out
 
-    def _cnn_bytes_per_px(self):
-        """Autograd state of ONE U-Net evaluation per pixel (--use_cnn): the measured value once a step has run; before that
-        an a-priori figure that grows with the depth of the U-Net -- 2.6 KB per pixel was measured for n_down = 3 on the
-        CPU path; the GPU path's Conv2dBlocks also keep a reflect-padded copy and a sliced .contiguous() copy of their
-        inputs, hence the factor 1.5."""
-        if self._cnn_px_measured > 0:
-            return self._cnn_px_measured
-        return 2600.0 * 1.5 * (1.0 + 0.15 * max(0, int(getattr(self.opt, 'n_down', 3)) - 3))
-
     # ------------------------------------------------------------------------------------
     def _train_on_batch(self, epoch, batch_ind, batch):
         opt = self.opt
@@ -686,28 +306,32 @@ class Model(NetInterface):
         for k, v in batch.items():                   # strip the DataLoader dimension (:177-179)
             if type(v) != list:
                 batch[k] = v.squeeze(0)
+
+        # ---- the plan (models/sf_step.py).  Pairs of different frame gaps: everything below works on the batch in gap-grouped
+        #      order (gap_plan), each group integrated over its own number of Euler steps; a uniform batch is ONE group in the
+        #      caller's order
         share, share_quantum = share_frames_of(opt)
-        steps, steps_pp, time_step, ids = self._steps_per_pair(batch, with_ids=share)
+        steps, steps_pp, time_step, ids = sf_step.steps_per_pair(batch, with_ids=share)
         self.steps, self.steps_per_pair = steps, steps_pp
         self.load_batch(batch)
         inp = self._input
         B, _, H, W = inp.img_1.shape
         HW, dev = H * W, self.device
         do_reg = opt.interp_steps > 0 and (not warm or opt.warm_reg) and opt.acc_mul > 0
-        # pairs of different frame gaps: everything below works on the batch in gap-grouped order (gap_plan), each group
-        # integrated over its own number of Euler steps; a uniform batch is ONE group in the caller's order
-        plan = self._plan_step(steps_pp, HW, do_reg)
+        mlp_bytes = None if self._mlp is None else (self._mlp.stash_floats(HW) * 4, self._mlp.gstash_floats(HW) * 4)
+        plan = sf_step.plan_step(steps_pp, HW, do_reg, mlp_bytes, sf_step.cnn_bytes_per_px(self._cnn_px_measured, opt), opt)
         if plan['perm'] != list(range(B)):
             self._group_input(plan['perm'])
-        fid1, fid2 = self._frame_ids(inp)
+        schedule, needs_late = sf_step.choose_schedule(plan, B, opt.use_cnn, bool(int(getattr(opt, 'mlp_recompute', 1))))
 
-        # ---- phase 1: depth maps; the autograd state of as many chunks as fit stays alive for phase 3 (kept slots),
-        #      the rest is a no-graph forward that phase 3 recomputes
+        # ---- the step's image sets (images, frame ids, first slot), and phase 1 over them: depth maps; the autograd state of
+        #      as many chunks as fit stays alive for phase 3 (kept slots), the rest is a no-graph forward that phase 3 recomputes
         keeping = not (warm or not getattr(opt, 'depth_graphs', 1) or float(getattr(opt, 'depth_keep_gb', 150.0)) <= 0)
         if keeping:
             self._depth.choose_chunk(B, HW, plan['reserve'], dev)
-        n_slots = -(-B // self._chunk())
-        self.depth_images_last_step, self.last_union, union = 2 * B, None, None
+        fid1, fid2 = (None, None) if opt.midas else (inp.frame_id_1, inp.frame_id_2)      # (the hourglass's per-frame embedding)
+        n_slots, tab, union = -(-B // self._chunk()), None, None
+        self.depth_images_last_step, self.last_union = 2 * B, None
         if share:
             # opt.share_frames: the depth net runs once per DISTINCT frame of the step (same id = same image: trusted).  The
             # union rows (padded to a multiple of opt.share_quantum with copies of row 0) are one image set in slots 0..;
@@ -715,86 +339,54 @@ class Model(NetInterface):
             perm = plan['perm']
             tab = ops.UnionTables(frame_union.plan_union([ids[0][p] for p in perm], [ids[1][p] for p in perm],
                                                          share_quantum), dev)
-            img_u = ops.union_gather(inp.img_1.contiguous(), inp.img_2.contiguous(), tab)
-            fid_u = None if fid1 is None else ops.union_gather(fid1.contiguous(), fid2.contiguous(), tab)
+            union = (ops.union_gather(inp.img_1.contiguous(), inp.img_2.contiguous(), tab),
+                     None if fid1 is None else ops.union_gather(fid1.contiguous(), fid2.contiguous(), tab))
             n_slots = -(-tab.U_pad // self._chunk())
-            if not keeping:
-                with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
-                    depth_u = self._depth.forward(img_u, fid_u)
-            else:
-                depth_u = self._depth.forward_keep(img_u, fid_u, 0, plan['reserve'], n_slots)
-                self._depth.trim(dev, plan['reserve'])
-            depth_1, depth_2 = ops.union_scatter(depth_u, tab)
-            union = (tab, img_u, fid_u)
-            self.depth_images_last_step = tab.U_pad
-            self.last_union = {'U': tab.U, 'U_pad': tab.U_pad, 'B': B}
-        elif not keeping:
+            self.depth_images_last_step, self.last_union = tab.U_pad, {'U': tab.U, 'U_pad': tab.U_pad, 'B': B}
+        sets, n_slots_total = sf_step.image_sets(inp.img_1, fid1, inp.img_2, fid2, n_slots, union)
+        if keeping:
+            depths = [self._depth.forward_keep(img, fid, slot0, plan['reserve'], n_slots_total) for img, fid, slot0 in sets]
+            self._depth.trim(dev, plan['reserve'])
+        else:
             # (non-warm steps without kept slots: phase 3 recomputes every chunk's forward; a warm-up step has no depth-net backward)
             with (contextlib.nullcontext() if warm else ops.counting_recomputed()):
-                depth_1 = self._depth.forward(inp.img_1, fid1)
-                depth_2 = self._depth.forward(inp.img_2, fid2)
-        else:
-            depth_1 = self._depth.forward_keep(inp.img_1, fid1, 0, plan['reserve'], 2 * n_slots)
-            depth_2 = self._depth.forward_keep(inp.img_2, fid2, n_slots, plan['reserve'], 2 * n_slots)
-            self._depth.trim(dev, plan['reserve'])
+                depths = [self._depth.forward(img, fid) for img, fid, _ in sets]
+        depth_1, depth_2 = depths if tab is None else ops.union_scatter(depths[0], tab)
 
-        # ---- phase 2: geometry + scene-flow network + losses, forward and backward (_SfStep)
-        step = _SfStep(self, inp, depth_1, depth_2, steps, time_step, warm, do_reg, plan['groups'])
-        step.union = union
-        if opt.use_cnn:
-            _late, n_global, capturing = parallel.agree_on_step_plan(dev, False, B, False)
-            step.set_global_batch(n_global)
-            scalars, inv = self._unet_forward_backward(step)
-            return self._finish_step(epoch, batch_ind, batch, step, scalars, inv, True, capturing, n_slots)
-        self._mlp.pack([p for p in self.net_sceneflow.parameter_list()[0::2]], self.net_sceneflow.parameter_list()[1::2])
-        # The MLP activation stashes bound how many pairs go through the MLP kernels at once
-        # (Bc).  If the forward stashes of the WHOLE batch fit the budget next to one chunk of
-        # backward scratch, the warp+loss kernel runs once over all pairs (one launch of
-        # B*H*W pixels fills the chip far better than B/Bc smaller ones); otherwise every
-        # chunk gets its own warp+loss launch -- or, by default, the recompute schedule (_SfStep.run_recompute).
-        Bc, whole = plan['Bc'], plan['whole']
-        recompute = Bc < B and not whole and bool(int(getattr(opt, 'mlp_recompute', 1)))
+        # ---- phase 2: geometry + scene-flow network + losses, forward and backward (sf_step.SfStep)
+        step = sf_step.SfStep(opt, dev, self._mlp, self._flat_sf, self._sf_grad_main, self.net_sceneflow, inp, depth_1, depth_2,
+                              plan, time_step, warm, do_reg, self._depth.free_hbm, self._cnn_px_measured)
         # ranks may hold different batch sizes / frame gaps: agree on the schedule (early or late normaliser)
         # and on the size of the global batch before the first data-dependent collective
         # (also agreed across ranks: does ANY rank still have to capture a depth-net graph in phase 3?  Then every rank keeps
-        #  the MLP-gradient all-reduce out of flight until after phase 3, so the order of collectives is the same everywhere)
-        will_capture = not warm and self._depth.backward_will_capture(
-            *([(0, union[1])] if union is not None else [(0, inp.img_1), (n_slots, inp.img_2)]))
-        late, n_global, capturing = parallel.agree_on_step_plan(dev, not (whole or Bc >= B or recompute), B, will_capture)
-        step.set_global_batch(n_global)
-        step.begin_mlp(Bc, plan['chunks'])
-        self._last_chunks = list(step.chunks)
-        if late:
-            scalars, inv = step.run_late()
-        elif recompute:
-            scalars, inv = step.run_recompute()
-        else:
-            scalars, inv = step.run_whole_batch()
-        return self._finish_step(epoch, batch_ind, batch, step, scalars, inv, not late, capturing, n_slots)
+        #  the MLP-gradient all-reduce out of flight until after phase 3, so the order of collectives is the same everywhere.
+        #  A --use_cnn step never announces a capture)
+        will_capture = not (warm or opt.use_cnn) and self._depth.backward_will_capture(*[(slot0, img) for img, _, slot0 in sets])
+        late, n_global, capturing = parallel.agree_on_step_plan(dev, needs_late, B, will_capture)
+        schedule = sf_step.agreed_schedule(schedule, late)
+        if self._mlp is not None:
+            self._last_chunks = list(plan['chunks'])
+        scalars, inv = step.run(schedule, n_global)
+        self._cnn_px_measured = step.cnn_px_measured
+        return self._finish_step(epoch, batch_ind, batch, step, scalars, inv, schedule != 'late', capturing, sets, tab)
 
-    def _frame_ids(self, inp):
-        """Frame ids of the two image sets (the hourglass's per-frame embedding); the MiDaS net takes none."""
-        return (None, None) if self.opt.midas else (inp.frame_id_1, inp.frame_id_2)
-
-    def _finish_step(self, epoch, batch_ind, batch, step, scalars, inv, early_norm, capturing, n_slots):
+    def _finish_step(self, epoch, batch_ind, batch, step, scalars, inv, early_norm, capturing, sets, tab):
         """Phase 3 and the end of the step, for the MLP and the U-Net path alike.  early_norm: phase 2 has already normalised
-        g_d1_main (regulariser included); else (_SfStep.run_late) inv * main + reg is formed here."""
-        opt, inp, warm, k = self.opt, step.inp, step.warm, self._flat_sf
+        g_d1_main (regulariser included); else (SfStep.run_late) inv * main + reg is formed here.  sets: phase 1's image sets;
+        tab: the union's index tables when they are ONE set (opt.share_frames), else None."""
+        opt, warm, k = self.opt, step.warm, self._flat_sf
         # the MLP gradient all-reduce overlaps the depth-net backward, except in a step that still has to
         # capture the depth net's forward+backward graph (no collective in flight during a capture)
         h_sf = None if capturing else k.all_reduce_grads(async_op=True)
 
         # ---- phase 3: depth-net backward from the depth gradients
         if not warm:
-            fid1, fid2 = self._frame_ids(inp)
             g_d1 = step.g_d1_main if early_norm else ops.scale_add(step.g_d1_main, step.g_d1_main, scale_ptr=inv, b=step.g_d1_reg)
             g_d2 = ops.scale_add(step.g_d2_main, step.g_d2_main, scale_ptr=inv)
-            if step.union is not None:      # opt.share_frames: ONE backward over the distinct frames, from the summed gradients
-                tab, img_u, fid_u = step.union
-                self._depth.backward(img_u, fid_u, ops.union_reduce(g_d1, g_d2, tab), slot0=0)
-            else:
-                self._depth.backward(inp.img_1, fid1, g_d1, slot0=0)
-                self._depth.backward(inp.img_2, fid2, g_d2, slot0=n_slots)
+            # (opt.share_frames: ONE backward over the distinct frames, from the summed gradients)
+            g_sets = [g_d1, g_d2] if tab is None else [ops.union_reduce(g_d1, g_d2, tab)]
+            for (img, fid, slot0), g in zip(sets, g_sets):
+                self._depth.backward(img, fid, g, slot0=slot0)
             # 421 MB (MiDaS) in --grad_buckets large all-reduces, each bucket's Adam launch overlapping the next
             # bucket's reduction
             skip = None
@@ -831,65 +423,6 @@ class Model(NetInterface):
                       'mseg': step.mseg}
         self._export_train_visuals(epoch, batch_ind, batch)
         return batch_log
-
-    # -- --use_cnn: phase 2 with the U-Net scene-flow network -------------------------------------------------------------
-    def _sf_net_cnn(self, p, t):
-        """Model.forward_sf_net with --use_cnn (:346-357)."""
-        x = torch.cat([p, t], 1) if self.opt.time_dependent else p
-        return self.net_sceneflow(x) / self.opt.sf_mag_div
-
-    def _unet_forward_backward(self, step):
-        """Phase 2 when the scene-flow network is the U-Net (networks/FCNUnet.py): the network runs under PyTorch autograd on
-        this package's convolution kernels, the geometry and the losses stay the ONE fused warp+loss launch -- its scene-flow
-        gradient is what the U-Net's backward starts from, with the batch-global normaliser applied as a device scalar.  The
-        regulariser's first evaluation is Euler evaluation 0, as in the MLP path.  Returns (scalars, inv) like the schedules."""
-        dev, inp, steps, time_step, do_reg = self.device, step.inp, step.steps, step.time_step, step.do_reg
-        B, H, W, HW, sums = step.B, step.H, step.W, step.HW, step.sums
-        P1 = ops.unproject(step.depth_1, inp.R_1, inp.t_1, inp.K_inv, planar=True).requires_grad_(True)
-        ts = inp.time_stamp_1
-        # the whole batch goes through the U-Net under autograd: fail early, with the numbers, instead of somewhere inside it
-        evals = steps + (1 if do_reg else 0)        # (a mixed batch: its largest step count, an upper bound)
-        need = B * HW * self._cnn_bytes_per_px() * evals
-        free, _total = self._depth.free_hbm(dev)
-        if need > free:
-            msg = ('--use_cnn: the U-Net\'s autograd state for %d pairs at %dx%d (%d evaluations, %.0f B per pixel and '
-                   'evaluation) needs %.1f GB, %.1f GB are free: use fewer pairs per step or a smaller --depth_keep_gb'
-                   % (B, H, W, evals, self._cnn_bytes_per_px(), need / 2 ** 30, free / 2 ** 30))
-            if self._cnn_px_measured > 0:        # a measured footprint: fail early, with the numbers
-                raise RuntimeError(msg)
-            # an a-priori estimate must not reject a configuration that may well run
-            warnings.warn(msg + ' (a-priori estimate: nothing has been measured yet, trying anyway)')
-        mem0 = torch.cuda.memory_allocated(dev)
-        with torch.enable_grad():
-            accs, firsts = [], []
-            for b0, b1, n in step.groups:        # mixed frame gaps: the U-Net runs per gap group (one group otherwise)
-                whole = (b0, b1) == (0, B)
-                sf_acc, p, t, sf0 = None, (P1 if whole else P1[b0:b1]), (ts if whole else ts[b0:b1]), None
-                for i in range(n):
-                    s_i = self._sf_net_cnn(p, t)
-                    sf0 = s_i if i == 0 else sf0
-                    sf_acc = s_i if sf_acc is None else sf_acc + s_i
-                    p, t = p + s_i, t + time_step
-                accs.append(sf_acc)
-                firsts.append(sf0)
-            sf_acc, sf0 = (accs[0], firsts[0]) if len(accs) == 1 else (torch.cat(accs, 0), torch.cat(firsts, 0))
-        # measured footprint of an evaluation (like DepthRunner.keep_per_px for the depth net's slots): the planner's next decisions
-        # use it instead of the a-priori figure
-        self._cnn_px_measured = max(self._cnn_px_measured, (torch.cuda.memory_allocated(dev) - mem0) / float(HW * sum(n * (b1 - b0) for b0, b1, n in step.groups)))
-        step.sf_all = sf_acc.detach().contiguous()
-        step.g_sf_all = g_sf = torch.empty_like(step.sf_all)
-        scalars, inv = step.warp_whole_batch()
-        ops.scale_add(g_sf, g_sf, scale_ptr=inv)
-        sf_acc.backward(g_sf, retain_graph=bool(do_reg))        # parameter gradients land in the flat buffer's views
-        if do_reg:
-            with torch.enable_grad():
-                sf1 = self._sf_net_cnn(P1 + sf0, ts + time_step)
-                dsum = (sf1 - sf0).abs().sum()
-            sums[4:5] += dsum.detach()
-            (dsum * step.reg_coef).backward()
-        parallel.all_reduce_sum_(sums[4:])
-        ops.unproject_backward(P1.grad.contiguous(), True, inp.R_1, inp.K_inv, out=step.g_d1_main, accumulate=True)
-        return scalars, inv
 
     def _step_scalars_to_host(self, scalars, sums, warm):
         """The step's ONE device -> host copy: the loss scalars, the regulariser sum and -- with fp16 activation storage --
@@ -968,7 +501,7 @@ class Model(NetInterface):
         P = ops.unproject(depth, inp.R_1, inp.t_1, inp.K_inv, planar=True)
         if self.opt.use_cnn:
             with torch.no_grad():
-                return {'depth': depth, 'sf_1_2': self._sf_net_cnn(P, inp.time_stamp_1)}
+                return {'depth': depth, 'sf_1_2': sf_step.sf_net_cnn(self.net_sceneflow, self.opt, P, inp.time_stamp_1)}
         sf = torch.empty_like(P)
         self._mlp.pack(self.net_sceneflow.parameter_list()[0::2], self.net_sceneflow.parameter_list()[1::2])
         ts = inp.time_stamp_1 if self.opt.time_dependent else None
