@@ -228,6 +228,9 @@ SIGNATURES = {
     'dvd_splat_accumulate': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int, c_void_p, c_void_p] + [c_int] * 4 +
                              [c_float] * 4 + [c_int, c_longlong, c_void_p]),
     'dvd_splat_resolve': (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float] * 3 + [c_void_p] * 5),
+    # a finished optimisation scored along its tracks (csrc/eval.hip; an addition within ABI 8)
+    'dvd_eval_tracks': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_int, c_float, c_float,
+                                c_int, c_void_p, c_longlong, c_void_p, c_longlong] + [c_int] * 4 + [c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -45,6 +45,7 @@ SOURCES = [
     ('frame_union.hip', ['-ffp-contract=off']),
     ('track.hip', ['-ffp-contract=off']),
     ('splat.hip', ['-ffp-contract=off']),
+    ('eval.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

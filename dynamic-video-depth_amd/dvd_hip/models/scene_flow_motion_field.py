@@ -50,7 +50,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import frame_union, render, sf_step, tracks
+from . import evaluate, frame_union, render, sf_step, tracks
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 from .sf_step import gap_plan, pairs_per_chunk      # noqa: F401 (re-exported)
@@ -546,6 +546,25 @@ class Model(NetInterface):
         [V,1,H,W] (summed bilinear weight) and hit uint8 [V,H,W].  Bitwise reproducible; nothing synchronises with the device."""
         return render.render(self, store, target, sources, cam_c2w=cam_c2w, K=K, depth=depth, advect=advect, chunk=chunk,
                              valid=valid, **splat_params)
+
+    def evaluate(self, store, start=None, n_steps=None, depth=None, chunk=None, maps=False, z_tol=0.05):
+        """How consistent are the refined depth, the scene-flow field, the cameras and the optical flow? (models/evaluate.py)
+        The pixels of the frames `start` (default: every frame but the last) are pushed along the field for n_steps frames
+        (default: the largest gap of the store's catalogue), as in `track`, and every step is compared with the frame it lands
+        in by one fused kernel (ops.eval_tracks, csrc/eval.hip).  depth: [N,1,H,W] refined depth (default: video_depth of the
+        store); chunk: start frames per pass, the result does not depend on it; z_tol: a point deeper than the target's depth
+        * (1 + z_tol) is occluded.  Returns device tensors (K = n_steps, B = len(start); row k - 1 is step k):
+          sums int64 [K,B,6], shift   the kernel's exact sums (n_inside, n_occluded, rel, photo, n_flow, epe; values * 2^shift)
+          n_inside, n_occluded, n_flow  int64 [K,B]: points that land inside the target image, those of them behind a nearer
+                   surface, and points with a valid optical flow of the pair (start, start + k) in the store
+          depth_rel, photo  float64 [K,B]: mean |z - d| / d and mean L1 colour difference over the seen points
+          flow_epe  float64 [K,B]: mean end-point distance between the induced motion and the stored flow (NaN without pairs)
+          by_step  the three means and `occluded` (n_occluded / n_inside) pooled over the start frames, float64 [K]
+          disp_mse  float64 [N]: _vali_on_batch's disparity MSE against depth_mvs, frame by frame
+          maps     (maps=True) float32 [K,B,3,H,W]: rel, photo, epe per pixel, -1 where the point does not count
+          steps_valid  int32 [B]
+        Bitwise reproducible; nothing synchronises with the device.  --use_cnn raises NotImplementedError."""
+        return evaluate.evaluate(self, store, start=start, n_steps=n_steps, depth=depth, chunk=chunk, maps=maps, z_tol=z_tol)
 
     def _train_pred(self):
         """The reference's train-time `pred` dict (:243-264 + `sf_loss_pp` of :308), materialised on demand from the

@@ -90,6 +90,25 @@ def integrate(mlp, points, ts, valid, time_step, out_scale, chunk):
                             p_next=points[k + 1, r0:r1])
 
 
+def start_slab(model, store, depth, start, T1):
+    """The zeroed slab [T1,B,3,H,W] of the start frames `start` with row 0 filled -- their refined depth un-projected with
+    their own cameras -- and their time stamps [B,1,H,W] (None for a time-independent field)."""
+    dev, T, H, W = store.device, store.tables, store.H, store.W
+    B = len(start)
+    # the start frames' rows of the store, by the store's own gather (one launch): depth, camera, time stamp
+    d0 = torch.empty(B, 1, H, W, device=dev)
+    R0, K0, t0 = torch.empty(B, 3, 3, device=dev), torch.empty(B, 3, 3, device=dev), torch.empty(B, 3, device=dev)
+    entries = [(depth, d0, 'copy', 0), (T['R_T'], R0, 'copy', 0), (T['K_inv_T'], K0, 'copy', 0), (T['t'], t0, 'copy', 0)]
+    ts = None
+    if model.opt.time_dependent:
+        ts = torch.empty(B, 1, H, W, device=dev)
+        entries.append((T['ts_vali'], ts, 'fill', 0))
+    ops.store_gather(entries, np.array([start, start, start], dtype=np.int32))
+    points = torch.zeros(T1, B, 3, H, W, device=dev)
+    ops.unproject(d0, R0, t0, K0, planar=True, out=points[0])
+    return points, ts
+
+
 def track(model, store, start, n_steps, depth=None, chunk=None):
     """Model.track: see there."""
     opt = model.opt
@@ -112,17 +131,7 @@ def track(model, store, start, n_steps, depth=None, chunk=None):
         raise ValueError('track: depth must be [%d,1,%d,%d], got %s' % (N, H, W, tuple(depth.shape)))
     model.eval()
     with torch.no_grad():
-        # the start frames' rows of the store, by the store's own gather (one launch): depth, camera, time stamp
-        d0 = torch.empty(B, 1, H, W, device=dev)
-        R0, K0, t0 = torch.empty(B, 3, 3, device=dev), torch.empty(B, 3, 3, device=dev), torch.empty(B, 3, device=dev)
-        entries = [(depth, d0, 'copy', 0), (T['R_T'], R0, 'copy', 0), (T['K_inv_T'], K0, 'copy', 0), (T['t'], t0, 'copy', 0)]
-        ts = None
-        if opt.time_dependent:
-            ts = torch.empty(B, 1, H, W, device=dev)
-            entries.append((T['ts_vali'], ts, 'fill', 0))
-        ops.store_gather(entries, np.array([start, start, start], dtype=np.int32))
-        points = torch.zeros(T1, B, 3, H, W, device=dev)
-        ops.unproject(d0, R0, t0, K0, planar=True, out=points[0])
+        points, ts = start_slab(model, store, depth, start, T1)
         params = model.net_sceneflow.parameter_list()
         model._mlp.pack(params[0::2], params[1::2])
         integrate(model._mlp, points, ts, valid, 1.0 / (N + 0.0), 1.0 / opt.sf_mag_div, int(chunk))

@@ -386,6 +386,110 @@ def splat(points, values, view, tables, n_views, valid=None, planar=True, z_near
     return splat_resolve(zbuf, acc, shift, w_min=w_min, value_bound=value_bound, fill=fill, out=out)
 
 
+# -- a finished optimisation scored along its tracks (csrc/eval.hip) ---------------------------------------------------------
+EVAL_CAP = 1024.0            # photo and epe are capped here (2^10); rel at 1
+EVAL_SUMS = ('n_inside', 'n_occluded', 'depth_rel', 'photo', 'n_flow', 'flow_epe')
+
+
+def eval_shift(n_pixels):
+    """The fixed-point shift of eval_tracks' sums for images of n_pixels points: min(32, 62 - 10 - ceil_log2(n_pixels)).  A
+    term is at most 2^10 * 2^shift, so the n_pixels terms of a row stay within 2^62."""
+    n = int(n_pixels)
+    if n < 1:
+        raise RuntimeError('eval_shift: n_pixels must be >= 1, got %d' % n)
+    return min(32, 62 - 10 - (n - 1).bit_length())
+
+
+def _step_view(what, name, t, shape, dtype, dev):
+    """A [T,B,...] destination whose steps may be further apart than B rows (the columns of a larger tensor) -> its step
+    stride in elements."""
+    if not (torch.is_tensor(t) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and
+            t[0].is_contiguous() and (shape[0] == 1 or t.stride(0) >= t[0].numel())):
+        raise RuntimeError('%s: %s must be a %s tensor %s on the device of the points, contiguous within a step' % (
+            what, name, dtype, shape))
+    return int(t.stride(0)) if shape[0] > 1 else int(t[0].numel())
+
+
+def eval_tracks(points, source, tables, depth_all, img_all, k_first=1, pairs=None, z_tol=0.05, d_min=1e-3, sums=None,
+                maps=False, host_source=None):
+    """Integrated world points against the frames they land in (dvd_eval_tracks, csrc/eval.hip) -> {'sums', 'shift'[, 'maps']}.
+      points   [T,B,3,H,W] planar: row r of image b is frame source[b]'s pixels at the time of frame source[b] + k_first + r
+      source   B frame ids: host sequence / array / CPU tensor (uploaded here) or a GPU int32 tensor (then host_source, its
+               host copy, saves the read-back of the range check);  tables {'R', 't', 'K_T'} as track_project takes them
+      depth_all [N,1,H,W] refined depth;  img_all [N,3,H,W]
+      pairs    None or (pair_row, flow_1_2 [P,H,W,2], mask uint8 [P,H,W], 0 = valid): pair_row [T,B] holds the row of the flow
+               pair (source[b], target frame) or -1 -- a host array (uploaded here) or a GPU int32 tensor (never read back)
+      z_tol    a point deeper than the target's depth * (1 + z_tol) is occluded;  d_min: floor of the depth rel divides by
+      sums     None (a cleared tensor is made) or an int64 [T,B,6] tensor to ACCUMULATE into; its steps may be the columns of
+               a larger tensor.  Entries: n_inside, n_occluded, sum rel, sum photo, n_flow, sum epe, the value sums in units
+               of 2^-shift.
+      maps     True, or a float32 [T,B,3,H,W] destination: rel, photo, epe per point, -1 where the point does not count
+    Rows whose target frame is past the end of the tables add nothing.  Integer atomics only: the same inputs give the same
+    bits for any grid.  Everything is checked on the host before the launch; no device tensor is read back."""
+    import numpy as np
+    what = 'eval_tracks'
+    points, source, (R, t, K_T), T, B, H, W, N = _track_args(what, points, source, tables, True, host_source)
+    dev = points.device
+    if isinstance(k_first, bool) or k_first not in (0, 1):
+        raise RuntimeError('%s: k_first must be 0 or 1, got %r' % (what, k_first))
+    z_tol, d_min = float(z_tol), float(d_min)
+    if not (0.0 <= z_tol < float('inf')):
+        raise RuntimeError('%s: z_tol=%r is out of range' % (what, z_tol))
+    if not (0.0 < d_min < float('inf')):
+        raise RuntimeError('%s: d_min=%r is out of range' % (what, d_min))
+    depth_all, img_all = _dev32(depth_all, 'depth_all'), _dev32(img_all, 'img_all')
+    if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
+        raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
+            what, N, H, W, tuple(depth_all.shape)))
+    if img_all.device != dev or tuple(img_all.shape) != (N, 3, H, W):
+        raise RuntimeError('%s: img_all must be [%d,3,%d,%d] on the device of the points, got %s' % (
+            what, N, H, W, tuple(img_all.shape)))
+    pair_row = flow = mask = None
+    P = 0
+    if pairs is not None:
+        if not isinstance(pairs, (tuple, list)) or len(pairs) != 3 or any(p is None for p in pairs):
+            raise RuntimeError('%s: pairs must be (pair_row, flow_1_2, mask), all three' % what)
+        pair_row, flow, mask = pairs
+        flow = _dev32(flow, 'flow_1_2')
+        if flow.device != dev or flow.dim() != 4 or tuple(flow.shape[1:]) != (H, W, 2) or flow.shape[0] < 1:
+            raise RuntimeError('%s: flow_1_2 must be [P,%d,%d,2] on the device of the points, got %s' % (what, H, W, tuple(flow.shape)))
+        P = int(flow.shape[0])
+        if not (torch.is_tensor(mask) and mask.is_cuda and mask.device == dev and mask.dtype == torch.uint8 and
+                tuple(mask.shape) == (P, H, W)):
+            raise RuntimeError('%s: mask must be a GPU uint8 tensor [%d,%d,%d] on the device of the points' % (what, P, H, W))
+        mask = mask if mask.is_contiguous() else mask.contiguous()
+        if torch.is_tensor(pair_row) and pair_row.is_cuda:
+            if pair_row.dtype != torch.int32 or tuple(pair_row.shape) != (T, B) or not pair_row.is_contiguous() or \
+                    pair_row.device != dev:
+                raise RuntimeError('%s: pair_row must be a contiguous GPU int32 tensor [%d,%d] on the device of the points' % (what, T, B))
+        else:
+            host = np.asarray(pair_row.cpu() if torch.is_tensor(pair_row) else pair_row)
+            if host.dtype.kind not in 'iu' or host.shape != (T, B):
+                raise RuntimeError('%s: pair_row must hold [%d,%d] integral rows, got %s %s' % (what, T, B, host.dtype, host.shape))
+            if host.size and (int(host.min()) < -1 or int(host.max()) >= P):
+                raise RuntimeError('%s: pair_row spans [%d, %d]; -1 or a row of the %d flow pairs' % (
+                    what, int(host.min()), int(host.max()), P))
+            pair_row = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev, non_blocking=True)
+    shift = eval_shift(H * W)
+    if sums is None:
+        sums = torch.zeros((T, B, 6), device=dev, dtype=torch.int64)
+    sums_stride = _step_view(what, 'sums', sums, (T, B, 6), torch.int64, dev)
+    maps_stride = 0
+    if maps is True:
+        maps = torch.empty((T, B, 3, H, W), device=dev, dtype=torch.float32)
+    elif maps is False or maps is None:
+        maps = None
+    if maps is not None:
+        maps_stride = _step_view(what, 'maps', maps, (T, B, 3, H, W), torch.float32, dev)
+    _lib.check(_lib.load().dvd_eval_tracks(_p(points), _p(source), int(k_first), _p(R), _p(t), _p(K_T), N, _p(depth_all),
+                                           _p(img_all), _p(pair_row), _p(flow), _p(mask), P, z_tol, d_min, shift, _p(sums),
+                                           sums_stride, _p(maps), maps_stride, T, B, H, W, _stream()), 'dvd_eval_tracks')
+    res = {'sums': sums, 'shift': shift}
+    if maps is not None:
+        res['maps'] = maps
+    return res
+
+
 # -- max|x| scalars ----------------------------------------------------------------------------------------------------
 # Every tensor that feeds a matrix kernel carries max|x| (or an upper bound) in a 1-element GPU tensor: the kernels derive
 # the power-of-two scale of their fp16 operand split from it on the device (csrc/dvd_split.h); the host never reads it.
@@ -599,7 +703,7 @@ BYTE_CLASS_KERNELS = {
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
-                                                   'splat_resolve_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'splat_resolve_kernel', 'eval_tracks_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

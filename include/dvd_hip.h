@@ -820,6 +820,39 @@ int dvd_splat_resolve(const unsigned int* zbuf, const unsigned long long* acc, i
                       float w_min, float value_bound, float fill, float* image, float* depth, float* weight,
                       unsigned char* hit, dvd_stream_t stream);
 
+/* A finished optimisation scored along its tracks (an addition within ABI 8; csrc/eval.hip, models/evaluate.py): frame f
+ * pushed along the scene-flow field to the time of frame g should agree with frame g wherever it is visible there.
+ *   points     [T, B, 3, H, W], planar: row r of image b holds the world points of frame source[b]'s pixels at the time of
+ *              frame g = source[b] + k_first + r (the slab models/tracks.py integrates; k_first = 1 skips its row 0)
+ *   source     DEVICE array of B ints;  k_first  0 or 1.  Where g >= N (or source[b] < 0) the row is dead: it reads nothing,
+ *              adds nothing, and its maps are -1.
+ *   R, t, K_T  the per-frame tables [N, 3, 3], [N, 3], [N, 3, 3] as dvd_track_project takes them
+ *   depth_all  [N, 1, H, W] refined depth;  img_all  [N, 3, H, W] colours
+ *   pair_row   DEVICE int [T, B]: the row of the flow pair (source[b], g) in flow_1_2 / mask, or -1 (a row >= P counts as -1);
+ *   flow_1_2   [P, H, W, 2];  mask  uint8 [P, H, W], 0 = valid.  All three or none.
+ * Per point, in fp32 with the operations of dvd_track_project (the same u, v, z and taps, bit for bit):
+ *   inside     z > 0 && 0 <= u <= W - 1 && 0 <= v <= H - 1;   d = depth_all[g] at (u, v) (bilinear, border) where inside
+ *   occluded   z > d * (1 + z_tol);   seen = inside && !occluded
+ *   rel        min(|z - d| / max(d, d_min), 1)                                     where seen
+ *   photo      min((|c0 - o0| + |c1 - o1| + |c2 - o2|) / 3, 1024), c = img_all[g] at (u, v) with d's taps and weights,
+ *              o = the pixel's own colour in img_all[source[b]]                    where seen
+ *   epe        min(hypot((u - x) - flow.x, (v - y) - flow.y), 1024)                where pair_row >= 0, mask == 0 and z > 0
+ *   sums       long long [T, B, 6], ACCUMULATED into (the caller clears it): n_inside, n_occluded, sum q(rel), sum q(photo),
+ *              n_flow, sum q(epe), q(x) = llrint((double)x * 2^shift).  1 <= shift <= min(32, 62 - 10 - ceil_log2(H * W)), so
+ *              a row cannot overflow.  Consecutive steps are sums_step_stride elements apart (>= B * 6): a launch over a
+ *              chunk of images may write its columns of a larger tensor.
+ *   maps       float [T, B, 3, H, W] or NULL: rel, photo, epe -- the very fp32 values that were quantised -- and -1 where the
+ *              point does not count; steps maps_step_stride elements apart (>= B * 3 * H * W).
+ * The block reduces in 64-bit integers (registers, a shuffle tree, LDS) and issues at most six integer atomicAdd: the sums
+ * are bitwise reproducible and independent of the grid.  Refused with DVD_EINVAL before any HIP call: a null pointer, the
+ * three flow arguments not all-or-none, T or B outside 1..65535, H or W < 2, H * W >= 2^30, k_first not 0 or 1, z_tol < 0 or
+ * NaN, d_min <= 0 or NaN, a shift outside its range, a step stride below its row.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_eval_tracks(const float* points, const int* source, int k_first, const float* R, const float* t, const float* K_T,
+                    int N, const float* depth_all, const float* img_all, const int* pair_row, const float* flow_1_2,
+                    const unsigned char* mask, int P, float z_tol, float d_min, int shift, long long* sums,
+                    long long sums_step_stride, float* maps, long long maps_step_stride, int T, int B, int H, int W,
+                    dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
