@@ -231,7 +231,12 @@ SIGNATURES = {
     # a finished optimisation scored along its tracks (csrc/eval.hip; an addition within ABI 8)
     'dvd_eval_tracks': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_int, c_float, c_float,
                                 c_int, c_void_p, c_longlong, c_void_p, c_longlong] + [c_int] * 4 + [c_void_p]),
+    # depth metrics against a ground truth: the exact median of ratios per segment and the fused score (csrc/select.hip,
+    # csrc/depth_score.hip; additions within ABI 8)
+    'dvd_ratio_median': (c_int, [c_void_p] * 3 + [c_float, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'dvd_depth_score': (c_int, [c_void_p] * 5 + [c_float, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
 }
+RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 
 _lock = threading.Lock()
 _lib = None

@@ -46,6 +46,8 @@ SOURCES = [
     ('track.hip', ['-ffp-contract=off']),
     ('splat.hip', ['-ffp-contract=off']),
     ('eval.hip', ['-ffp-contract=off']),
+    ('select.hip', ['-ffp-contract=off']),
+    ('depth_score.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -50,7 +50,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import evaluate, frame_union, render, sf_step, tracks
+from . import evaluate, frame_union, render, score_depth, sf_step, tracks
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 from .sf_step import gap_plan, pairs_per_chunk      # noqa: F401 (re-exported)
@@ -565,6 +565,21 @@ class Model(NetInterface):
           steps_valid  int32 [B]
         Bitwise reproducible; nothing synchronises with the device.  --use_cnn raises NotImplementedError."""
         return evaluate.evaluate(self, store, start=start, n_steps=n_steps, depth=depth, chunk=chunk, maps=maps, z_tol=z_tol)
+
+    def score_depth(self, store, depth=None, gt=None, align='median_video', regions=True, mask=None, maps=False):
+        """How close is the refined depth to the ground truth of the frame files? (models/score_depth.py)  The converse of
+        `evaluate`: the numbers a paper reports, after aligning the prediction to the ground truth by one scale.
+        depth: [N,1,H,W] (default: video_depth of the store); gt: [N,1,H,W] (default: store.depth_mvs); align: 'none' (scale
+        1), 'median_frame' (per frame the median of gt / depth over its countable pixels) or 'median_video' (one median over
+        the countable pixels of all frames) -- exact medians from ops.ratio_median (csrc/select.hip); regions: split by the
+        store's motion segmentation where it has one; mask: uint8 [N,H,W], non-zero = allowed.  A pixel counts iff gt > 1e-2,
+        depth > 0, the scaled depth is finite and the mask allows it.  Returns device tensors (rows: all / static / dynamic):
+          sums int64 [N,3,9], shift   the kernel's exact sums (ops.SCORE_SUMS; values * 2^shift);  scale fp32 [N];  n int64 [N,3]
+          abs_rel, sq_rel, rmse, rmse_log, silog, d1, d2, d3  float64 [N,3], NaN where n = 0 (silog = mean l^2 - mean(l)^2)
+          video    the same quantities (and n) as [3], from the sums pooled over the frames in int64
+          maps, counted  (maps=True) float32 [N,3,H,W]: abs_rel, sq, l per pixel, and uint8 [N,H,W]: 1 where the pixel counts
+        Bitwise reproducible; nothing synchronises with the device."""
+        return score_depth.score_depth(self, store, depth=depth, gt=gt, align=align, regions=regions, mask=mask, maps=maps)
 
     def _train_pred(self):
         """The reference's train-time `pred` dict (:243-264 + `sf_loss_pp` of :308), materialised on demand from the

@@ -490,6 +490,112 @@ def eval_tracks(points, source, tables, depth_all, img_all, k_first=1, pairs=Non
     return res
 
 
+# -- depth metrics against a ground truth (csrc/select.hip, csrc/depth_score.hip) ------------------------------------------------
+SCORE_CAP = 1024.0           # abs_rel, sq_rel, sq and l^2 are capped here (2^10); l at +-SCORE_LOG_CAP
+SCORE_LOG_CAP = 32.0
+SCORE_SUMS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log_sq', 'log', 'n_d1', 'n_d2', 'n_d3')
+SCORE_REGIONS = ('all', 'static', 'dynamic')
+SCORE_MAPS = ('abs_rel', 'sq', 'log')
+
+
+def _dev_u8(what, name, t, shape, dev):
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.uint8 and tuple(t.shape) == shape):
+        raise RuntimeError('%s: %s must be a GPU uint8 tensor %s on the device of the data' % (what, name, list(shape)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def ratio_median(num, den, mask=None, den_min=0.0):
+    """The exact median of num / den per segment (dvd_ratio_median, csrc/select.hip) -> {'median' [S] fp32, 'count' [S] int64}.
+      num, den  [S, L] fp32 (a 1-D tensor is one segment);  mask  None or uint8 [S, L], non-zero = keep
+      An element is selected iff den > den_min and its mask byte allows it.  median[s] is numpy's median of the selected fp32
+      quotients, bit for bit (NaN where count is 0 or a selected quotient is a NaN).
+    A radix select on the device: no sort, no key array, no host synchronisation; the same bits from run to run."""
+    what = 'ratio_median'
+    num, den = _dev32(num, 'num'), _dev32(den, 'den')
+    if num.dim() == 1:
+        num = num[None]
+    if den.dim() == 1:
+        den = den[None]
+    if num.dim() != 2 or num.shape != den.shape or num.device != den.device or num.numel() == 0:
+        raise RuntimeError('%s: num and den must be non-empty [S,L] tensors of one shape on one device, got %s and %s' % (
+            what, tuple(num.shape), tuple(den.shape)))
+    S, L = int(num.shape[0]), int(num.shape[1])
+    if S > 65535 or S * L >= 2 ** 31:
+        raise RuntimeError('%s: S=%d segments of L=%d elements: S <= 65535 and S * L < 2^31 are required' % (what, S, L))
+    den_min = float(den_min)
+    if den_min != den_min:
+        raise RuntimeError('%s: den_min is NaN' % what)
+    if mask is not None and torch.is_tensor(mask) and mask.dim() == 1:
+        mask = mask[None]
+    mask = _dev_u8(what, 'mask', mask, (S, L), num.device)
+    dev = num.device
+    median = torch.empty(S, device=dev, dtype=torch.float32)
+    count = torch.empty(S, device=dev, dtype=torch.int64)
+    nbytes = S * _lib.RATIO_MEDIAN_WORKSPACE_PER_SEGMENT
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().dvd_ratio_median(_p(num), _p(den), _p(mask), den_min, S, L, _p(median), _p(count), _p(ws), nbytes,
+                                            _stream()), 'dvd_ratio_median')
+    return {'median': median, 'count': count}
+
+
+def depth_score(pred, gt, scale, seg=None, mask=None, g_min=1e-2, sums=None, maps=False, shift=None):
+    """A predicted depth against its ground truth (dvd_depth_score, csrc/depth_score.hip) -> {'sums', 'shift'[, 'maps', 'counted']}.
+      pred, gt  [N,1,H,W] fp32;  scale  GPU fp32 [N]: the prediction is scored as scale[n] * pred (ratio_median's output, or ones)
+      seg       None or [N,H,W] fp32: <= 0.5 static, > 0.5 dynamic;  mask  None or uint8 [N,H,W], non-zero = allowed
+      A pixel counts iff gt > g_min, pred > 0, scale * pred is finite and the mask allows it.
+      sums      None (a cleared tensor is made) or an int64 [N,3,9] tensor to ACCUMULATE into -- rows all / static / dynamic,
+                words SCORE_SUMS, the value sums in units of 2^-shift
+      maps      True: also 'maps' [N,3,H,W] (abs_rel, sq, l: the fp32 values that were quantised, 0 where the pixel does not
+                count) and 'counted' uint8 [N,H,W]
+      shift     None: eval_shift(N * H * W); a caller that pools the rows of several calls passes the shift of all its pixels
+    Integer atomics only: the same inputs give the same bits for any grid.  No device tensor is read back."""
+    what = 'depth_score'
+    pred, gt = _dev32(pred, 'pred'), _dev32(gt, 'gt')
+    if pred.dim() != 4 or pred.shape[1] != 1 or pred.shape != gt.shape or pred.device != gt.device or pred.numel() == 0:
+        raise RuntimeError('%s: pred and gt must be non-empty [N,1,H,W] tensors of one shape on one device, got %s and %s' % (
+            what, tuple(pred.shape), tuple(gt.shape)))
+    N, _, H, W = (int(v) for v in pred.shape)
+    dev = pred.device
+    scale = _dev32(scale, 'scale')
+    if scale.device != dev or tuple(scale.shape) != (N,):
+        raise RuntimeError('%s: scale must be a GPU float32 tensor [%d] on the device of pred, got %s' % (what, N, tuple(scale.shape)))
+    if seg is not None:
+        seg = _dev32(seg, 'seg')
+        if seg.device != dev or tuple(seg.shape) != (N, H, W):
+            raise RuntimeError('%s: seg must be [%d,%d,%d] on the device of pred, got %s' % (what, N, H, W, tuple(seg.shape)))
+    mask = _dev_u8(what, 'mask', mask, (N, H, W), dev)
+    g_min = float(g_min)
+    if not (0.0 <= g_min < float('inf')):
+        raise RuntimeError('%s: g_min=%r is out of range' % (what, g_min))
+    if N > 65535 or H * W >= 2 ** 30:
+        raise RuntimeError('%s: N=%d frames of %dx%d: N <= 65535 and H * W < 2^30 are required' % (what, N, H, W))
+    limit = eval_shift(N * H * W)
+    if shift is None:
+        shift = limit
+    if isinstance(shift, bool) or int(shift) != shift or not (1 <= shift <= limit):
+        raise RuntimeError('%s: shift=%r outside 1 .. %d for %d pixels' % (what, shift, limit, N * H * W))
+    shift = int(shift)
+    if sums is None:
+        sums = torch.zeros((N, 3, 9), device=dev, dtype=torch.int64)
+    elif not (torch.is_tensor(sums) and sums.device == dev and sums.dtype == torch.int64 and tuple(sums.shape) == (N, 3, 9) and
+              sums.is_contiguous()):
+        raise RuntimeError('%s: sums must be a contiguous int64 tensor [%d,3,9] on the device of pred' % (what, N))
+    point_maps = counted = None
+    if maps is True:
+        point_maps = torch.empty((N, 3, H, W), device=dev, dtype=torch.float32)
+        counted = torch.empty((N, H, W), device=dev, dtype=torch.uint8)
+    elif maps not in (False, None):
+        raise RuntimeError('%s: maps must be True or False' % what)
+    _lib.check(_lib.load().dvd_depth_score(_p(pred), _p(gt), _p(scale), _p(seg), _p(mask), g_min, shift, _p(sums), _p(point_maps),
+                                           _p(counted), N, H, W, _stream()), 'dvd_depth_score')
+    res = {'sums': sums, 'shift': shift}
+    if point_maps is not None:
+        res['maps'], res['counted'] = point_maps, counted
+    return res
+
+
 # -- max|x| scalars ----------------------------------------------------------------------------------------------------
 # Every tensor that feeds a matrix kernel carries max|x| (or an upper bound) in a 1-element GPU tensor: the kernels derive
 # the power-of-two scale of their fp16 operand split from it on the device (csrc/dvd_split.h); the host never reads it.
@@ -703,7 +809,8 @@ BYTE_CLASS_KERNELS = {
     'gconv_c8': ('gconv3x3_c8',), 'elementwise': ('mul_mask_kernel', 'scale_add_kernel', 'acc_reg_kernel', 'sum_partials_kernel',
                                                   'head1x1_', 'cast_scale_kernel'),
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
-                                                   'splat_resolve_kernel', 'eval_tracks_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
+                                                   'depth_score_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

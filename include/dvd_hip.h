@@ -853,6 +853,48 @@ int dvd_eval_tracks(const float* points, const int* source, int k_first, const f
                     long long sums_step_stride, float* maps, long long maps_step_stride, int T, int B, int H, int W,
                     dvd_stream_t stream);
 
+/* The exact median of num / den per segment (an addition within ABI 8; csrc/select.hip): the reference's
+ * `np.median(nn_depth[idx, idy] / mvs_depth[idx, idy])` over `np.where(mvs_depth > 1e-3)`
+ * (scripts/preprocess/shutterstock/generate_frame_midas.py:153-160), and the median alignment of models/score_depth.py.
+ *   num, den   float [S, L]: S contiguous segments of L elements;  mask  uint8 [S, L] or NULL
+ *   An element is selected iff den > den_min (a NaN fails) and its mask byte, if given, is non-zero; its key is the correctly
+ *   rounded fp32 quotient num / den.
+ *   median     float [S]: numpy's median of the selected quotients, bit for bit -- with the n values sorted, v[(n-1)/2] for
+ *              odd n, (v[n/2-1] + v[n/2]) / 2 with the sum formed first in fp32 for even n, NaN for n = 0, NaN if any selected
+ *              quotient is a NaN; +-inf sort as the extremes.   count  long long [S]: n.
+ *   workspace  at least S * DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT bytes of device memory, 4-byte aligned; cleared by the entry.
+ * A most-significant-digit radix select (4 passes of 8 bits) that follows both middle ranks at once: per pass a histogram
+ * kernel re-reads num, den and the mask (no key array is written) and a one-block-per-segment kernel fixes the next digit on the
+ * device.  Nothing synchronises with the host; only integers are added, so the result is the same bits from run to run and for
+ * every grid.  Refused with DVD_EINVAL before any HIP call: a null pointer, S outside 1..65535, L < 1, S * L >= 2^31, a NaN
+ * den_min, a misaligned pointer, a workspace that is too small.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+#define DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT 8224
+int dvd_ratio_median(const float* num, const float* den, const unsigned char* mask, float den_min, int S, long long L,
+                     float* median, long long* count, void* workspace, size_t workspace_bytes, dvd_stream_t stream);
+
+/* A predicted depth scored against its ground truth (an addition within ABI 8; csrc/depth_score.hip, models/score_depth.py):
+ * the error terms behind abs-rel, sq-rel, RMSE, log-RMSE and the delta < 1.25^k accuracies, where the reference's validation
+ * (models/scene_flow_motion_field.py `_vali_on_batch`, disp_vali's gt > 1e-2) knows one scalar.
+ *   pred, gt   float [N, 1, H, W];  scale  DEVICE float [N] (dvd_ratio_median's output, or ones)
+ *   seg        float [N, H, W] or NULL;  mask  uint8 [N, H, W] or NULL, non-zero = allowed
+ * Per pixel in fp32: q = scale[n] * pred; it counts iff gt > g_min, pred > 0, q is finite and the mask allows it.  d = q - g,
+ *   abs_rel = min(|d| / g, 1024), sq_rel = min(d * d / g, 1024), sq = min(d * d, 1024),
+ *   l = min(max(logf(q) - logf(g), -32), 32), l2 = min(l * l, 1024), delta_k = max(q / g, g / q) < 1.25^k for k = 1, 2, 3.
+ *   sums       long long [N, 3, 9], ACCUMULATED into (the caller clears it).  Row 0: every counted pixel, row 1: seg <= 0.5
+ *              (static), row 2: seg > 0.5 (dynamic); without seg rows 1 and 2 receive nothing.  Words: n, sum q(abs_rel),
+ *              sum q(sq_rel), sum q(sq), sum q(l2), sum q(l) (signed, two's complement), n_delta1, n_delta2, n_delta3, with
+ *              q(x) = llrint((double)x * 2^shift).  1 <= shift <= min(32, 62 - 10 - ceil_log2(N * H * W)): neither a row nor the
+ *              rows of a video pooled can overflow.
+ *   maps       float [N, 3, H, W] or NULL: abs_rel, sq, l -- the very fp32 values that were quantised -- and 0 where the pixel
+ *              does not count;  counted  uint8 [N, H, W] (with maps, both or none): 1 where it counts.
+ * The block reduces in 64-bit integers (registers, a shuffle tree, LDS) and issues at most nine integer atomicAdd per region:
+ * the sums are bitwise reproducible and independent of the grid.  Refused with DVD_EINVAL before any HIP call: a null pointer,
+ * maps without counted or the reverse, N outside 1..65535, H or W < 1, H * W >= 2^30, g_min < 0 or not finite, a shift outside
+ * its range, a misaligned pointer.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_depth_score(const float* pred, const float* gt, const float* scale, const float* seg, const unsigned char* mask,
+                    float g_min, int shift, long long* sums, float* maps, unsigned char* counted, int N, int H, int W,
+                    dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
