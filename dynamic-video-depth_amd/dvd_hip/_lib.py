@@ -235,6 +235,11 @@ SIGNATURES = {
     # csrc/depth_score.hip; additions within ABI 8)
     'dvd_ratio_median': (c_int, [c_void_p] * 3 + [c_float, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dvd_depth_score': (c_int, [c_void_p] * 5 + [c_float, c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    # backward-in-time advection: the fixed-point update of the inverse Euler step and the projection with a row offset
+    # (csrc/invert.hip, csrc/track.hip; additions within ABI 8)
+    'dvd_track_invert_update': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    'dvd_track_project_from': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int] + [c_void_p] * 3 +
+                               [c_int] * 5 + [c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

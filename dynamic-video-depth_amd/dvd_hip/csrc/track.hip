@@ -7,7 +7,9 @@
 // (sample_coord) and the tap arithmetic (bilinear) are those of the fused warp+loss kernel (warp_pixel.h), as in
 // dvd_flow_warp_fwd.  The cameras are rows of per-frame tables: image b of step k looks up frame start[b] + k, so ONE launch
 // projects every step of an integrated trajectory (models/tracks.py); a frame past the end of the tables writes zeros and
-// reads nothing.  dvd_project_bwd is the 2x3 Jacobian of (u, v) w.r.t. P, transposed, per point.
+// reads nothing.  dvd_track_project_from adds a row offset k0 (frame start[b] + k + k0; negative for a slab that also holds
+// the rows BEFORE the start frame, csrc/invert.hip) and gives zeros on either side of the video.  dvd_project_bwd is the 2x3
+// Jacobian of (u, v) w.r.t. P, transposed, per point.
 //
 // A pure map plus one 4-tap gather: 12 B read and 17 B written per point, plus the taps; no atomics, every output element
 // is written by exactly one thread with plain vector stores, so results are bitwise reproducible.  One thread per 4
@@ -30,14 +32,15 @@ struct TrackArgs {
   const float* g_uv;          // backward: [T1,B,H,W,2]
   float* g_points;            // backward: the layout of points
   int B, N, H, W, HW, displacement, accumulate;
+  int k0;                     // row k looks up frame start[b] + k + k0 (0 for every entry but dvd_track_project_from)
   float half_w, half_h, wmax, hmax;
 };
 
-// the table row of image b at step k, or -1 where the video has ended (or the start is not a frame at all)
+// the table row of image b at step k, or -1 where the video has ended or not begun (or the start is not a frame at all)
 __device__ __forceinline__ int target_frame(const TrackArgs& a, int b, int k) {
   const int s = a.start[b];
-  const long long g = (long long)s + k;
-  return (s >= 0 && g < (long long)a.N) ? (int)g : -1;
+  const long long g = (long long)s + k + a.k0;
+  return (s >= 0 && g >= 0 && g < (long long)a.N) ? (int)g : -1;
 }
 
 template <int PX, bool PLANAR>
@@ -197,21 +200,17 @@ static int track_shape_ok(const char* who, int T1, int B, int N, int H, int W) {
   return DVD_OK;
 }
 
-}  // namespace dvd
-
-extern "C" {
-
-int dvd_track_project(const float* points, int points_planar, const int* start, const float* R, const float* t,
-                      const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
-                      float* depth_at, unsigned char* inside, int T1, int B, int H, int W, dvd_stream_t stream) {
-  using namespace dvd;
+static int track_project_launch(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                                const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                                float* depth_at, unsigned char* inside, int T1, int B, int H, int W, int k0,
+                                dvd_stream_t stream) {
   DVD_REQUIRE(points && start && R && t && K_T && uv, "track_project: null pointer");
   DVD_REQUIRE(!depth_all || depth_at, "track_project: depth_all without depth_at");
   if (int st = track_shape_ok("track_project", T1, B, N, H, W)) return st;
   TrackArgs a = {};
   a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.depth_all = depth_all;
   a.uv = uv, a.z = z, a.depth_at = depth_all ? depth_at : nullptr, a.inside = inside;
-  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.displacement = displacement;
+  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.displacement = displacement, a.k0 = k0;
   a.half_w = (float)((W - 1) / 2.0), a.half_h = (float)((H - 1) / 2.0), a.wmax = (float)(W - 1), a.hmax = (float)(H - 1);
   const double pts = (double)T1 * B * a.HW;
   bytes_add(DVD_BYTES_GEOMETRY, pts * (12.0 + 8.0 + (z ? 4.0 : 0.0) + (inside ? 1.0 : 0.0) + (depth_all ? 4.0 : 0.0)) +
@@ -231,6 +230,25 @@ int dvd_track_project(const float* points, int points_planar, const int* start, 
     hipLaunchKernelGGL((track_project_kernel<1, false>), grid, block, 0, s, a);
   DVD_LAUNCH_OK();
   return DVD_OK;
+}
+
+}  // namespace dvd
+
+extern "C" {
+
+int dvd_track_project(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                      const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                      float* depth_at, unsigned char* inside, int T1, int B, int H, int W, dvd_stream_t stream) {
+  return dvd::track_project_launch(points, points_planar, start, R, t, K_T, depth_all, N, uv, displacement, z, depth_at, inside,
+                                   T1, B, H, W, 0, stream);
+}
+
+int dvd_track_project_from(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                           const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                           float* depth_at, unsigned char* inside, int T1, int B, int H, int W, int k0, dvd_stream_t stream) {
+  DVD_REQUIRE(k0 > -(1 << 30) && k0 < (1 << 30), "track_project_from: bad row offset k0=%d", k0);
+  return dvd::track_project_launch(points, points_planar, start, R, t, K_T, depth_all, N, uv, displacement, z, depth_at, inside,
+                                   T1, B, H, W, k0, stream);
 }
 
 int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, const int* start, const float* R,

@@ -10,6 +10,10 @@ another's holes and the nearest surface wins.
                                ping-pong buffers; the last row of every source lands in one [S,3,H,W] tensor
   afterwards                   ONE ops.splat over all sources of all views: two clears and three launches
 
+With backward=True a source may also be LATER than its target: it is carried back by f - g inverse Euler steps
+(ops.invert_step, the backward half of models/tracks.py) on the same ping-pong buffers plus one that holds the field's output,
+so a view is filled from both sides and the disocclusions only later frames see stop being holes.
+
 `render_plan` is the host-side half (validation, the flat list of sources and their step counts); `render` is what
 `Model.render` runs.  Nothing here synchronises with the device.
 """
@@ -38,11 +42,12 @@ def _as_list(x):
     return list(x)
 
 
-def render_plan(n_frames, target, sources, advect=True):
+def render_plan(n_frames, target, sources, advect=True, backward=False):
     """The flat source list of a render: (source frames, their view index, their Euler step counts), each of length S.
     target: V frame indices; sources: V lists of frame indices, sources[v] drawn into view v.  ValueError for an empty list, a
     frame that is not an integer or not in the video, a length mismatch and, with advect, a source later than its target (the
-    field integrates forwards only).  Without advect every step count is 0 and any frames go together."""
+    field integrates forwards only) unless backward, which makes the step counts signed: g - f < 0 for a source that is
+    carried back in time.  Without advect every step count is 0 and any frames go together."""
     if isinstance(n_frames, bool) or int(n_frames) != n_frames or n_frames < 1:
         raise ValueError('render_plan: n_frames must be a positive integer, got %r' % (n_frames,))
     n_frames = int(n_frames)
@@ -64,7 +69,7 @@ def render_plan(n_frames, target, sources, advect=True):
             raise ValueError('render_plan: view %d has no source frames' % v)
         for f in src:
             f = _frame('source frame', f, n_frames)
-            if advect and f > g:
+            if advect and f > g and not backward:
                 raise ValueError('render_plan: source frame %d is later than its target frame %d; the scene-flow field '
                                  'integrates forwards only (advect=False renders held time)' % (f, g))
             frames.append(f)
@@ -107,10 +112,11 @@ def _segments(flags, b0, b1):
     return out
 
 
-def advect_points(model, store, depth, frames, steps, chunk):
+def advect_points(model, store, depth, frames, steps, chunk, n_iter=4):
     """World points of the source frames at their targets' times -> [S,3,H,W]: un-projected refined depth, then steps[s]
-    stash-free Euler steps of the MLP.  A chunk of source images goes through the chain at once on two ping-pong buffers; the
-    step that finishes a source writes straight into its row of the result."""
+    stash-free Euler steps of the MLP, or -steps[s] inverse steps (ops.invert_step with n_iter iterations) where steps[s] < 0.
+    A chunk of source images goes through the chain at once on two ping-pong buffers (and one for the field's output where a
+    source goes back); the step that finishes a source writes straight into its row of the result."""
     opt, dev, T = model.opt, store.device, store.tables
     N, H, W = store.cat.n_frames, store.H, store.W
     S = len(frames)
@@ -120,6 +126,7 @@ def advect_points(model, store, depth, frames, steps, chunk):
         params = model.net_sceneflow.parameter_list()
         model._mlp.pack(params[0::2], params[1::2])
         ping = [torch.empty(min(chunk, S), 3, H, W, device=dev) for _ in range(2)]
+        sf = torch.empty(min(chunk, S), 3, H, W, device=dev) if min(steps) < 0 else None
     time_step, out_scale = 1.0 / (N + 0.0), 1.0 / opt.sf_mag_div
     for c0 in range(0, S, chunk):
         c1 = min(c0 + chunk, S)
@@ -134,20 +141,27 @@ def advect_points(model, store, depth, frames, steps, chunk):
             entries.append((T['ts_vali'], ts, 'fill', 0))
         ops.store_gather(entries, np.array([fr, fr, fr], dtype=np.int32))
         # step 0: a source that is not advected is finished by its un-projection
-        for r0, r1, moving in _segments([s > 0 for s in st], 0, B):
+        for r0, r1, moving in _segments([s != 0 for s in st], 0, B):
             dst = ping[0][r0:r1] if moving else out[c0 + r0:c0 + r1]
             ops.unproject(d0[r0:r1], R0[r0:r1], t0[r0:r1], K0[r0:r1], planar=True, out=dst)
-        for k in range(max(st)):
+        for k in range(max(max(st), 0)):
             src, nxt = ping[k % 2], ping[(k + 1) % 2]
             for r0, r1 in tracks._runs(st, 0, B, k):                      # the rows that still have step k to do ...
                 for q0, q1, last in _segments([s == k + 1 for s in st], r0, r1):      # ... and whether it is their last
                     model._mlp.forward(src[q0:q1], None if ts is None else ts[q0:q1], t_offset=k * time_step,
                                        out_scale=out_scale, p_next=out[c0 + q0:c0 + q1] if last else nxt[q0:q1])
+        back = [max(-s, 0) for s in st]
+        for j in range(1, max(back) + 1):                                 # inverse step j: from frame f - j + 1 to f - j
+            src, nxt = ping[(j - 1) % 2], ping[j % 2]
+            for r0, r1 in tracks._runs(back, 0, B, j - 1):
+                for q0, q1, last in _segments([s == j for s in back], r0, r1):
+                    ops.invert_step(model._mlp, src[q0:q1], None if ts is None else ts[q0:q1], -j * time_step, out_scale,
+                                    n_iter=n_iter, out=out[c0 + q0:c0 + q1] if last else nxt[q0:q1], scratch=sf[q0:q1])
     return out
 
 
 def render(model, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
-           **splat_params):
+           backward=False, n_iter=4, **splat_params):
     """Model.render: see there."""
     opt = model.opt
     if advect and opt.use_cnn:
@@ -158,7 +172,9 @@ def render(model, store, target, sources, cam_c2w=None, K=None, depth=None, adve
         raise TypeError('render: unknown splat parameters %s (known: %s)' % (sorted(unknown), ', '.join(sorted(ops.SPLAT_DEFAULTS))))
     splat_params.setdefault('value_bound', 1.0)
     N, H, W = store.cat.n_frames, store.H, store.W
-    frames, view, steps = render_plan(N, target, sources, advect)
+    frames, view, steps = render_plan(N, target, sources, advect, backward=bool(backward))
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 1:
+        raise ValueError('render: n_iter must be an integer >= 1, got %r' % (n_iter,))
     target = [int(g) for g in _as_list(target)]
     V = len(target)
     if chunk is None:
@@ -177,7 +193,7 @@ def render(model, store, target, sources, cam_c2w=None, K=None, depth=None, adve
         raise ValueError('render: valid must be a GPU uint8 tensor [%d,%d,%d]' % (N, H, W))
     model.eval()
     with torch.no_grad():
-        points = advect_points(model, store, depth, frames, steps, int(chunk))
+        points = advect_points(model, store, depth, frames, steps, int(chunk), n_iter=int(n_iter))
         # the sources' colours and masks, in the order of the points (one more launch of the store's gather)
         S = len(frames)
         colours = torch.empty(S, 3, H, W, device=dev)

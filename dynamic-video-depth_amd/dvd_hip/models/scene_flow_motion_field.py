@@ -515,7 +515,7 @@ class Model(NetInterface):
         runs it (eval mode, no autograd state), so the result is that path's 'depth', frame by frame, bit for bit."""
         return tracks.video_depth(self, frames)
 
-    def track(self, store, start, n_steps, depth=None, chunk=None):
+    def track(self, store, start, n_steps, depth=None, chunk=None, n_back=0, n_iter=4):
         """Where the pixels of the frames `start` are 1 .. n_steps frames later: the scene-flow MLP integrated by Euler steps
         (forward_sf_net_multi_step, :360-367) from the un-projected refined depth, and every step projected into the camera of
         its target frame.  store: the video's FrameStore; depth: [N,1,H,W] refined depth (default: video_depth of the store).
@@ -525,18 +525,25 @@ class Model(NetInterface):
           the camera and within the image;  steps_valid int32 [B]  steps with a target frame -- rows past it are zero.
         chunk: start frames per pass of the chain (default: 8 GB of world points); the result does not depend on it.  The
         un-masked field drives the chain, as in training (--use_motion_seg only masks the flow handed to the warp);
-        --use_cnn raises NotImplementedError."""
-        return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk)
+        --use_cnn raises NotImplementedError.
+        n_back >= 1 makes the tracks two-sided: the field is also run backwards, each Euler step inverted by n_iter fixed-point
+        iterations (ops.invert_step).  Then T1 = n_back + 1 + n_steps, row n_back is the start frame, row j is
+        frame start + j - n_back (rows before frame 0 are zero), n_steps = 0 is allowed, and three keys are added: origin
+        (= n_back, a Python int), steps_valid_back int32 [B] (= min(n_back, start)) and resid fp32 [n_back,B] -- per backward
+        step j (row j - 1) the largest move of a point in the last iteration, 0 where there is no frame."""
+        return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk, n_back=n_back, n_iter=n_iter)
 
     def render(self, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
-               **splat_params):
+               backward=False, n_iter=4, **splat_params):
         """The video re-rendered from its own geometry and motion (models/render.py): for every view v the frames sources[v],
         un-projected with their refined depth, pushed along the scene-flow field to the time of frame target[v] (target[v] - f
         Euler steps, as in `track`) and splatted into one image with a soft z-buffer (ops.splat, csrc/splat.hip).
           target   V frame indices: the time of each view and, by default, its camera (rows of store.tables)
           cam_c2w [V,4,4], K [V,3,3]  (either or both; host arrays) novel cameras: camera-to-world poses / intrinsics, turned
                    into table rows by the store's own code
-          sources  V lists of frame indices; with advect none later than its target
+          sources  V lists of frame indices; with advect none later than its target, unless backward
+          backward True lets a source f be later than its target g: it is carried back by f - g inverse Euler steps of
+                   n_iter fixed-point iterations each (ops.invert_step), so a view is filled from both sides
           depth    [N,1,H,W] refined depth (default: video_depth of the store);  valid: optional uint8 [N,H,W], 0 drops a pixel
           advect   False holds time: the frames are drawn as they are (a static scene; the only mode under --use_cnn, where
                    True raises NotImplementedError)
@@ -545,7 +552,7 @@ class Model(NetInterface):
         Returns device tensors: image [V,3,H,W], depth [V,1,H,W] (the nearest surface, 0 where nothing landed), weight
         [V,1,H,W] (summed bilinear weight) and hit uint8 [V,H,W].  Bitwise reproducible; nothing synchronises with the device."""
         return render.render(self, store, target, sources, cam_c2w=cam_c2w, K=K, depth=depth, advect=advect, chunk=chunk,
-                             valid=valid, **splat_params)
+                             valid=valid, backward=backward, n_iter=n_iter, **splat_params)
 
     def evaluate(self, store, start=None, n_steps=None, depth=None, chunk=None, maps=False, z_tol=0.05):
         """How consistent are the refined depth, the scene-flow field, the cameras and the optical flow? (models/evaluate.py)

@@ -131,7 +131,7 @@ def _track_args(what, points, start, tables, planar, host_start):
 
 
 def track_project(points, start, tables, depth_all=None, out=None, planar=True, displacement=False, host_start=None,
-                  want=('z', 'inside')):
+                  want=('z', 'inside'), k0=0):
     """World points into the cameras of frames start[b] + k (dvd_track_project, csrc/track.hip) -> dict of uv [T1,B,H,W,2], z
     [T1,B,H,W], inside uint8 [T1,B,H,W] and, with depth_all [N,1,H,W], depth_at [T1,B,H,W].
       points   [T1,B,3,H,W] (planar: a slab of the scene-flow MLP's p_next rows) or [T1,B,H,W,3]
@@ -140,8 +140,13 @@ def track_project(points, start, tables, depth_all=None, out=None, planar=True, 
       tables   {'R': [N,3,3] world->camera, 't': [N,3], 'K_T': [N,3,3]} -- FrameStore.tables has them under these names
       out      optional dict of preallocated outputs;  want: which of the optional 'z' / 'inside' to compute
       displacement  uv minus the pixel's own (x, y): project_ptcld's return value
+      k0       row offset: row k looks up frame start[b] + k + k0 (dvd_track_project_from; -n_back for a two-sided slab whose
+               row n_back is the start frame); frames before the video give zeros like frames past its end
     Frames past the end of the tables give zeros.  Everything is checked on the host before the launch."""
     what = 'track_project'
+    if isinstance(k0, bool) or int(k0) != k0 or abs(int(k0)) >= 1 << 30:
+        raise RuntimeError('%s: k0 must be an integer row offset, got %r' % (what, k0))
+    k0 = int(k0)
     points, start, (R, t, K_T), T1, B, H, W, N = _track_args(what, points, start, tables, planar, host_start)
     dev = points.device
     if depth_all is not None:
@@ -164,10 +169,89 @@ def track_project(points, start, tables, depth_all=None, out=None, planar=True, 
         elif not (torch.is_tensor(o) and o.device == dev and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
             raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the points' % (what, k, dtype, shape))
         res[k] = o
-    _lib.check(_lib.load().dvd_track_project(_p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N,
-                                             _p(res['uv']), int(bool(displacement)), _p(res.get('z')), _p(res.get('depth_at')),
-                                             _p(res.get('inside')), T1, B, H, W, _stream()), 'dvd_track_project')
+    args = (_p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N, _p(res['uv']),
+            int(bool(displacement)), _p(res.get('z')), _p(res.get('depth_at')), _p(res.get('inside')), T1, B, H, W)
+    if k0 != 0:
+        _lib.check(_lib.load().dvd_track_project_from(*(args + (k0, _stream()))), 'dvd_track_project_from')
+    else:
+        _lib.check(_lib.load().dvd_track_project(*(args + (_stream(),))), 'dvd_track_project')
     return res
+
+
+def _like(what, name, t, ref):
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == ref.device and t.dtype == torch.float32 and t.shape == ref.shape
+            and t.is_contiguous()):
+        raise RuntimeError('%s: %s must be a contiguous float32 GPU tensor %s on the device of p' % (what, name, tuple(ref.shape)))
+    return t
+
+
+def _resid_ok(what, resid, B, dev):
+    if resid is not None and not (torch.is_tensor(resid) and resid.device == dev and resid.dtype == torch.float32 and
+                                  tuple(resid.shape) == (B,) and resid.is_contiguous()):
+        raise RuntimeError('%s: resid must be a contiguous float32 tensor [%d] on the device of p' % (what, B))
+
+
+def invert_update(p, sf, y_old, out=None, resid=None):
+    """One fixed-point update of the inverse Euler step (dvd_track_invert_update, csrc/invert.hip): out = p - sf, and resid[b]
+    = max(resid[b], max |out - y_old| of image b) -- the caller zeroes resid; a NaN difference counts as +Inf.
+      p, sf, y_old  [B,3,H,W] contiguous fp32 on one GPU; y_old may be p or out
+      out      optional destination [B,3,H,W] (it may be y_old; not p or sf);  resid: optional fp32 [B]
+    Everything is checked on the host before the launch."""
+    what = 'invert_update'
+    if not (torch.is_tensor(p) and p.is_cuda):
+        raise RuntimeError('p must be a GPU tensor (dvd_hip has no CPU path)')
+    if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 3 or p.numel() == 0 or not p.is_contiguous():
+        raise RuntimeError('%s: p must be a contiguous float32 tensor [B,3,H,W], got %s %s' % (what, p.dtype, tuple(p.shape)))
+    B, _, H, W = (int(v) for v in p.shape)
+    if B > 65535 or H * W >= 1 << 30:
+        raise RuntimeError('%s: at most 65535 images of fewer than 2^30 pixels per launch, got %d of %d x %d' % (what, B, H, W))
+    sf, y_old = _like(what, 'sf', sf, p), _like(what, 'y_old', y_old, p)
+    if out is None:
+        out = torch.empty_like(p)
+    _like(what, 'out', out, p)
+    if out.data_ptr() in (p.data_ptr(), sf.data_ptr()) and out.data_ptr() != y_old.data_ptr():
+        raise RuntimeError('%s: out may alias y_old only' % what)
+    _resid_ok(what, resid, B, p.device)
+    _lib.check(_lib.load().dvd_track_invert_update(_p(p), _p(sf), _p(y_old), _p(out), _p(resid), B, H * W, _stream()),
+               'dvd_track_invert_update')
+    return out
+
+
+def invert_step(mlp, p, t, t_offset, out_scale, n_iter=4, out=None, resid=None, scratch=None):
+    """The point y that one Euler step of the scene-flow field carries to p: y + out_scale * f(y, t + t_offset) = p, by n_iter
+    fixed-point iterations y <- p - out_scale * f(y, t + t_offset) from y = p.  The step is a near-identity map (out_scale =
+    1 / sf_mag_div), so the iteration contracts by a few per cent per round; n_iter = 4 is below one fp32
+    ulp of the points on the fields measured there.  Costs n_iter stash-free forwards of the MLP kernels (sf_out = scratch),
+    each followed by one invert_update; no torch arithmetic, nothing is read back.
+      mlp      a packed SceneFlowMLPKernels;  p [B,3,H,W], t [B,1,H,W] or None as its forward takes them
+      out      optional destination [B,3,H,W] (not p);  scratch: optional [B,3,H,W] that receives the last sf
+      resid    optional fp32 [B]: zeroed here, then max |y_n - y_(n-1)| of the LAST iteration per image
+    Returns out."""
+    what = 'invert_step'
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or n_iter < 1:
+        raise ValueError('%s: n_iter must be an integer >= 1, got %r' % (what, n_iter))
+    if not (torch.is_tensor(p) and p.is_cuda):
+        raise RuntimeError('p must be a GPU tensor (dvd_hip has no CPU path)')
+    if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 3 or p.numel() == 0 or not p.is_contiguous():
+        raise RuntimeError('%s: p must be a contiguous float32 tensor [B,3,H,W], got %s %s' % (what, p.dtype, tuple(p.shape)))
+    if out is None:
+        out = torch.empty_like(p)
+    if scratch is None:
+        scratch = torch.empty_like(p)
+    _like(what, 'out', out, p)
+    _like(what, 'scratch', scratch, p)
+    if len({p.data_ptr(), out.data_ptr(), scratch.data_ptr()}) != 3:
+        raise RuntimeError('%s: p, out and scratch must be three buffers' % what)
+    _resid_ok(what, resid, int(p.shape[0]), p.device)
+    y = p
+    for i in range(int(n_iter)):
+        last = i == int(n_iter) - 1
+        mlp.forward(y, t, t_offset=t_offset, out_scale=out_scale, sf_out=scratch)
+        if last and resid is not None:
+            resid.zero_()
+        invert_update(p, scratch, y, out=out, resid=resid if last else None)
+        y = out
+    return out
 
 
 def project_backward(g_uv, points, start, tables, planar=True, out=None, accumulate=False, host_start=None):

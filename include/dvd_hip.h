@@ -775,6 +775,26 @@ int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, c
                     const float* t, const float* K_T, int N, float* g_points, int accumulate, int T1, int B, int H, int W,
                     dvd_stream_t stream);
 
+/* Backward-in-time advection: two-sided tracks (additions within ABI 8; csrc/invert.hip, csrc/track.hip, models/tracks.py).
+ * One Euler step of the chain, x -> x + s f(x, t), is a near-identity map; the point y it carries to p is the fixed point of
+ * y <- p - s f(y, t).  dvd_sf_mlp_fwd delivers sf = s f(y_old, t) into its sf_out; dvd_track_invert_update forms the next
+ * iterate and measures how far it moved:
+ *   p, sf, y_old, y_out  [B, 3, H, W] fp32 (planar);  y_out = p - sf
+ *   resid      [B] or NULL: resid[b] = max(resid[b], max over image b of |y_out - y_old|) -- the caller zeroes it; a NaN
+ *              difference counts as +Inf, as with dvd_amax; a max of non-negative floats as unsigned integers, so it does
+ *              not depend on the order of the waves
+ * y_old may alias p or y_out (every element is read and written by one thread).  16-byte accesses where HW = H * W is a
+ * multiple of 4 and the four bases are 16-byte aligned, one value per thread otherwise.  B <= 65535, HW < 2^30: DVD_EINVAL
+ * before any launch otherwise.  Bytes are counted under DVD_BYTES_GEOMETRY.
+ * dvd_track_project_from is dvd_track_project with a row offset: image b of row k is projected into frame
+ * g = start[b] + k + k0, and every output is 0 where g < 0 or g >= N (a start frame inside the video keeps the rows that have
+ * a frame although start[b] + k0 < 0).  k0 = 0 is dvd_track_project, bit for bit. */
+int dvd_track_invert_update(const float* p, const float* sf, const float* y_old, float* y_out, float* resid, int B, int HW,
+                            dvd_stream_t stream);
+int dvd_track_project_from(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                           const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
+                           float* depth_at, unsigned char* inside, int T1, int B, int H, int W, int k0, dvd_stream_t stream);
+
 /* Forward splat of world points into target cameras with a soft z-buffer (additions within ABI 8; csrc/splat.hip,
  * models/render.py): the scatter that goes with dvd_track_project's gather.  It draws a frame, pushed along the scene-flow
  * field by the Euler chain of Model.forward_sf_net_multi_step (models/scene_flow_motion_field.py:360-367), in the camera of

@@ -9,7 +9,11 @@ stamped with build.source_digest(('track.hip',)).
                every depth map of the video read once for the gather -- over that time, next to the 8 TB/s HBM3E peak; once
                through ops.track_project (with the wrapper's validation) and once as back-to-back calls of the C entry
 
-All three are device-event times after a warm-up.  The feature has no counterpart before it, so no figure here is a threshold.
+  back         (--n_back K) the chain run backwards from every frame: ms per (frame . backward step) of tracks.integrate_back
+               (n_iter stash-free MLP forwards + n_iter dvd_track_invert_update launches per step), and the update kernel alone
+               over all frames -- 48 B per point (three planes of three values read, one written) over its time
+
+All of them are device-event times after a warm-up.  The feature has no counterpart before it, so no figure here is a threshold.
 
     python tools/bench_tracks.py --out profiles/tracks.json
 
@@ -46,6 +50,34 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def bench_back(a, model, opt, tracks, ops, p0, ts, start, chunk):
+    """The backward half: tracks.integrate_back from the un-projected frames p0 [N,3,H,W], and one update launch on its own."""
+    N, _, H, W = p0.shape
+    valid_back = tracks.track_plan_back(N, start, a.n_back)
+    slab = torch.zeros(a.n_back + 1, N, 3, H, W, device=p0.device)
+    slab[a.n_back].copy_(p0)
+    resid = torch.zeros(a.n_back, N, device=p0.device)
+
+    def run_back():
+        tracks.integrate_back(model._mlp, slab, ts if opt.time_dependent else None, valid_back, 1.0 / N, 1.0 / opt.sf_mag_div,
+                              chunk, n_iter=a.n_iter, resid=resid)
+    back_ms = timed(run_back, a.reps)
+    sf, y = torch.zeros_like(p0), p0.clone()
+    r = torch.zeros(N, device=p0.device)
+
+    def run_update():
+        ops.invert_update(p0, sf, y, out=y, resid=r)          # the iterate updated in place: every round but the first
+    update_ms = timed(run_update, max(a.reps, 10))
+    nbytes = 48.0 * N * H * W
+    frame_steps = sum(valid_back)
+    return {'n_back': a.n_back, 'n_iter': a.n_iter, 'ms_total': back_ms, 'frame_steps': frame_steps,
+            'ms_per_frame_step': back_ms / frame_steps, 'resid_max': float(resid.max()),
+            'update': {'ms': update_ms, 'points': N * H * W, 'MB_algorithmic': nbytes / 1e6, 'GBps': nbytes / update_ms / 1e6,
+                       'frac_of_hbm_peak': nbytes / update_ms / 1e6 / HBM_PEAK_GBPS,
+                       'bytes_model': '36 B read + 12 B written per point (p, sf and the iterate read, the iterate written in place)',
+                       'timing_includes': 'the host wrapper (validation) of every launch'}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=80)
@@ -55,6 +87,8 @@ def main():
     ap.add_argument('--depth', choices=('midas', 'hourglass'), default='midas')
     ap.add_argument('--depth_batch', type=int, default=8, help='frames per batch of the validation view')
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--n_back', type=int, default=0, help='also time this many backward steps from every frame (0: not at all)')
+    ap.add_argument('--n_iter', type=int, default=4, help='fixed-point iterations per backward step')
     ap.add_argument('--out', type=str, default=None)
     a = ap.parse_args()
     from dvd_hip import build, ops
@@ -127,6 +161,8 @@ def main():
                        'frac_of_hbm_peak_launch_only': nbytes / launch_ms / 1e6 / HBM_PEAK_GBPS,
                        'inside_fraction': float(out['inside'].float().mean())},
            'hbm_peak_allocated_GB': torch.cuda.max_memory_allocated(device) / 2 ** 30}
+    if a.n_back > 0:
+        res['back'] = bench_back(a, model, opt, tracks, ops, points[0], ts, start, chunk)
     line = json.dumps(res)
     print(line)
     if a.out:
