@@ -240,6 +240,9 @@ SIGNATURES = {
     'dvd_track_invert_update': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     'dvd_track_project_from': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int] + [c_void_p] * 3 +
                                [c_int] * 5 + [c_void_p]),
+    # geometry-aware temporal depth filter along two-sided tracks (csrc/track_filter.hip; an addition within ABI 8)
+    'dvd_track_filter': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_float, c_float] + [c_void_p] * 4 +
+                         [c_int] * 5 + [c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

@@ -49,6 +49,7 @@ SOURCES = [
     ('select.hip', ['-ffp-contract=off']),
     ('depth_score.hip', ['-ffp-contract=off']),
     ('invert.hip', ['-ffp-contract=off']),
+    ('track_filter.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -5,7 +5,7 @@
 // and, for the depth sample, BackwardWarp (:289-297) fed with that module's displacement field (u - x, v - y):
 // F.grid_sample(depth, (x, y) + displacement, bilinear, padding 'border', align_corners=True) -- the coordinate chain
 // (sample_coord) and the tap arithmetic (bilinear) are those of the fused warp+loss kernel (warp_pixel.h), as in
-// dvd_flow_warp_fwd.  The cameras are rows of per-frame tables: image b of step k looks up frame start[b] + k, so ONE launch
+// dvd_flow_warp_fwd; one point into one camera is project_sample (track_sample.h), shared with csrc/track_filter.hip.  The cameras are rows of per-frame tables: image b of step k looks up frame start[b] + k, so ONE launch
 // projects every step of an integrated trajectory (models/tracks.py); a frame past the end of the tables writes zeros and
 // reads nothing.  dvd_track_project_from adds a row offset k0 (frame start[b] + k + k0; negative for a slab that also holds
 // the rows BEFORE the start frame, csrc/invert.hip) and gives zeros on either side of the video.  dvd_project_bwd is the 2x3
@@ -17,8 +17,7 @@
 // one pixel per thread otherwise.  Same fp32 operation order as torch's CPU matmul (dvd_common.h), built with
 // -ffp-contract=off; the division is the compiler's IEEE division (z is not bounded away from 0 here).
 
-#include "track_cam.h"
-#include "warp_pixel.h"
+#include "track_sample.h"
 
 namespace dvd {
 
@@ -31,9 +30,9 @@ struct TrackArgs {
   unsigned char* inside;      // [T1,B,H,W] or null
   const float* g_uv;          // backward: [T1,B,H,W,2]
   float* g_points;            // backward: the layout of points
-  int B, N, H, W, HW, displacement, accumulate;
+  int B, N, HW, displacement, accumulate;
   int k0;                     // row k looks up frame start[b] + k + k0 (0 for every entry but dvd_track_project_from)
-  float half_w, half_h, wmax, hmax;
+  TrackView view;             // the image size and the constants of the sampling chain (track_sample.h)
 };
 
 // the table row of image b at step k, or -1 where the video has ended or not begun (or the start is not a frame at all)
@@ -63,35 +62,17 @@ __global__ __launch_bounds__(256) void track_project_kernel(const TrackArgs a) {
     load_track_cam(a.R, a.t, a.K, g, c);
     float P[3][PX];
     load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
-    const int y = p0 / a.W, x = p0 - y * a.W;
+    const int y = p0 / a.view.W, x = p0 - y * a.view.W;
     const float yf = (float)y;
     const float* dg = a.depth_all ? a.depth_all + (size_t)g * a.HW : nullptr;
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
-      const float xf = (float)(x + i);
-      float I0, I1, I2;
-      project_point(c, P[0][i], P[1][i], P[2][i], I0, I1, I2);
-      const float den = I2 + 1e-8f;
-      const float ui = I0 / den, vi = I1 / den;
-      const float dx = ui - xf, dy = vi - yf;      // the module's displacement field
-      const bool front = I2 > 0.0f;
-      in[i] = (front && ui >= 0.0f && ui <= a.wmax && vi >= 0.0f && vi <= a.hmax) ? 1u : 0u;
-      if (dg && front) {
-        // always inside [0, W-1] x [0, H-1]: sample_coord clamps, and its fmaxf / fminf turn a NaN into 0
-        const float ix = sample_coord(xf, dx, a.half_w, a.wmax);
-        const float iy = sample_coord(yf, dy, a.half_h, a.hmax);
-        const float x0f = floorf(ix), y0f = floorf(iy);
-        const float ww = ix - x0f, we = 1.0f - ww, wn = iy - y0f, ws = 1.0f - wn;
-        const int x0 = (int)x0f, y0 = (int)y0f;
-        const bool in_e = (x0 + 1) < a.W, in_s = (y0 + 1) < a.H;
-        const int o = y0 * a.W + x0;
-        const float dnw = dg[o], dne = in_e ? dg[o + 1] : 0.0f, dsw = in_s ? dg[o + a.W] : 0.0f,
-                    dse = (in_e && in_s) ? dg[o + a.W + 1] : 0.0f;
-        d[i] = bilinear(dnw, dne, dsw, dse, ws * we, ws * ww, wn * we, wn * ww);
-      }
-      u[i] = a.displacement ? dx : ui;
-      v[i] = a.displacement ? dy : vi;
-      zz[i] = I2;
+      const TrackHit h = project_sample(c, dg, a.view, P[0][i], P[1][i], P[2][i], (float)(x + i), yf);
+      in[i] = h.in;
+      d[i] = h.d;
+      u[i] = a.displacement ? h.dx : h.u;
+      v[i] = a.displacement ? h.dy : h.v;
+      zz[i] = h.z;
     }
   }
   if (PX == 4) {
@@ -192,14 +173,6 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
   }
 }
 
-static bool track_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int track_shape_ok(const char* who, int T1, int B, int N, int H, int W) {
-  DVD_REQUIRE(T1 > 0 && T1 <= 65535 && B > 0 && B <= 65535 && N > 0, "%s: bad sizes T1=%d B=%d N=%d", who, T1, B, N);
-  DVD_REQUIRE(H >= 2 && W >= 2 && (long long)H * W < (1LL << 30), "%s: bad image size H=%d W=%d", who, H, W);
-  return DVD_OK;
-}
-
 static int track_project_launch(const float* points, int points_planar, const int* start, const float* R, const float* t,
                                 const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
                                 float* depth_at, unsigned char* inside, int T1, int B, int H, int W, int k0,
@@ -210,8 +183,8 @@ static int track_project_launch(const float* points, int points_planar, const in
   TrackArgs a = {};
   a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.depth_all = depth_all;
   a.uv = uv, a.z = z, a.depth_at = depth_all ? depth_at : nullptr, a.inside = inside;
-  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.displacement = displacement, a.k0 = k0;
-  a.half_w = (float)((W - 1) / 2.0), a.half_h = (float)((H - 1) / 2.0), a.wmax = (float)(W - 1), a.hmax = (float)(H - 1);
+  a.B = B, a.N = N, a.HW = H * W, a.displacement = displacement, a.k0 = k0;
+  a.view = track_view(H, W);
   const double pts = (double)T1 * B * a.HW;
   bytes_add(DVD_BYTES_GEOMETRY, pts * (12.0 + 8.0 + (z ? 4.0 : 0.0) + (inside ? 1.0 : 0.0) + (depth_all ? 4.0 : 0.0)) +
                                     (depth_all ? 4.0 * (double)(N < T1 + B ? N : T1 + B) * a.HW : 0.0));
@@ -259,7 +232,7 @@ int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, c
   if (int st = track_shape_ok("project_bwd", T1, B, N, H, W)) return st;
   TrackArgs a = {};
   a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.g_uv = g_uv, a.g_points = g_points;
-  a.B = B, a.N = N, a.H = H, a.W = W, a.HW = H * W, a.accumulate = accumulate;
+  a.B = B, a.N = N, a.HW = H * W, a.accumulate = accumulate;
   bytes_add(DVD_BYTES_GEOMETRY, (double)T1 * B * a.HW * (accumulate ? 44.0 : 32.0));
   const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(g_uv) && track_aligned16(g_points);
   const int px = v4 ? 4 : 1;

@@ -51,6 +51,7 @@ from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
 from . import evaluate, frame_union, render, score_depth, sf_step, tracks
+from . import filter as depth_filter
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
 from .sf_step import gap_plan, pairs_per_chunk      # noqa: F401 (re-exported)
@@ -587,6 +588,29 @@ class Model(NetInterface):
           maps, counted  (maps=True) float32 [N,3,H,W]: abs_rel, sq, l per pixel, and uint8 [N,H,W]: 1 where the pixel counts
         Bitwise reproducible; nothing synchronises with the device."""
         return score_depth.score_depth(self, store, depth=depth, gt=gt, align=align, regions=regions, mask=mask, maps=maps)
+
+    def filter_depth(self, store, frames=None, radius=4, weights='gauss', sigma=None, mode='mean', tol=0.1, z_near=1e-3,
+                     depth=None, chunk=None, n_iter=4, passes=1):
+        """The refined depth made consistent over time (models/filter.py): every pixel of the frames `frames` (default: all)
+        follows its own two-sided track (as `track` with n_back = n_steps = radius, 1 <= radius <= 16) into the neighbouring
+        frames, reads the depth they claim where it lands, and one fused kernel (ops.track_filter, csrc/track_filter.hip) drops
+        the neighbours in which the point is outside, occluded or in gross disagreement (z <= D (1 + tol), D <= z (1 + tol),
+        z >= z_near) and fuses the ratios D / z of the rest with the pixel's own (ratio 1).
+          weights  'gauss' (exp(-j^2 / (2 sigma^2)) at row distance j, sigma default radius / 2), 'box', or 2 radius + 1 values
+          mode     'mean' (weighted) or 'median';  depth: [N,1,H,W] refined depth (default: video_depth of the store)
+          chunk    frames per pass (default: 8 GB of world points); the result does not depend on it, and only one chunk's slab
+                   of points is alive at a time;  n_iter: fixed-point iterations of a backward step, as in `track`
+          passes   k > 1 filters k times, each pass reading the depth the one before wrote (frames must be None)
+        The ratio is taken along the neighbour camera's ray and applied along the frame's own -- the usual approximation for
+        small disagreements; tol = 0.1 and radius = 4 are untuned defaults.  Returns device tensors (B = len(frames)):
+          depth [B,1,H,W]  the fused depth (a pixel whose depth is not > 0 keeps it);  ratio [B,1,H,W]  depth / input depth
+          (the product over the passes);  count uint8 [B,H,W]  rows that counted, the frame's own included (0 where the depth
+          is not > 0);  spread [B,1,H,W]  largest minus smallest counting ratio (count, spread: of the last pass);
+          steps_valid, steps_valid_back int32 [B]  rows of the window that have a frame after / before.
+        Feeds `evaluate(depth=..)` and `score_depth(depth=..)` as it is.  Bitwise reproducible; nothing synchronises with the
+        device.  --use_cnn raises NotImplementedError."""
+        return depth_filter.filter_depth(self, store, frames=frames, radius=radius, weights=weights, sigma=sigma, mode=mode, tol=tol,
+                                   z_near=z_near, depth=depth, chunk=chunk, n_iter=n_iter, passes=passes)
 
     def _train_pred(self):
         """The reference's train-time `pred` dict (:243-264 + `sf_loss_pp` of :308), materialised on demand from the

@@ -178,6 +178,81 @@ def track_project(points, start, tables, depth_all=None, out=None, planar=True, 
     return res
 
 
+FILTER_MAX_ROWS = 33        # kFilterMaxRows of csrc/track_filter.hip: a window of at most 16 frames on either side
+FILTER_MODES = {'mean': 0, 'median': 1}
+
+
+def track_filter(points, start, tables, depth_all, weights, k0=0, mode='mean', tol=0.1, z_near=1e-3, planar=True, out=None,
+                 host_start=None, want=('ratio', 'count', 'spread')):
+    """Every pixel's depth fused along its own track (dvd_track_filter, csrc/track_filter.hip) -> dict of depth [B,1,H,W] and,
+    as `want` names them, ratio [B,1,H,W], count uint8 [B,H,W], spread [B,1,H,W].
+      points, start, tables, depth_all, k0, planar, host_start   as track_project takes them; row -k0 of the slab is the start
+               frame itself and must be one of its T1 <= 33 rows; depth_all [N,1,H,W] is required
+      weights  a host sequence of T1 finite values >= 0 with weights[-k0] > 0 (uploaded here); not used by the median
+      mode     'mean': the weighted mean of the counting rows' ratios D / z;  'median': their median
+      tol      a row counts where z <= D (1 + tol) and D <= z (1 + tol) (and the point is inside, z >= z_near, D > 0)
+      out      optional dict of preallocated outputs
+    depth = depth_all[start] * ratio; a pixel whose own depth is not > 0 keeps it (ratio 1, count 0, spread 0).  Everything
+    is checked on the host before the launch."""
+    import math
+    import numpy as np
+    what = 'track_filter'
+    if isinstance(k0, bool) or int(k0) != k0 or abs(int(k0)) >= 1 << 30:
+        raise RuntimeError('%s: k0 must be an integer row offset, got %r' % (what, k0))
+    k0 = int(k0)
+    if mode not in FILTER_MODES:
+        raise RuntimeError('%s: mode must be one of %s, got %r' % (what, ', '.join(sorted(FILTER_MODES)), mode))
+    for name, v in (('tol', tol), ('z_near', z_near)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+            raise RuntimeError('%s: %s must be a finite number >= 0, got %r' % (what, name, v))
+    if any(k not in ('ratio', 'count', 'spread') for k in want):
+        raise RuntimeError("%s: want may name 'ratio', 'count' and 'spread', got %r" % (what, tuple(want)))
+    # the weights first: they are host data, so a bad list is refused before a tensor is looked at
+    try:
+        w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise RuntimeError('%s: weights must be a sequence of numbers, got %r' % (what, weights))
+    if w.ndim != 1 or not 1 <= w.size <= FILTER_MAX_ROWS:
+        raise RuntimeError('%s: weights must hold one value per row, 1 .. %d of them, got shape %s' % (what, FILTER_MAX_ROWS, w.shape))
+    with np.errstate(over='ignore'):
+        w32 = w.astype(np.float32)
+    if not np.all(np.isfinite(w32)) or np.any(w < 0):              # (a NaN stays one; a value past fp32's range turns Inf)
+        raise RuntimeError('%s: weights must be finite values >= 0, got %r' % (what, weights))
+    if not 0 <= -k0 < w.size:
+        raise RuntimeError('%s: k0=%d puts the start frame in row %d, outside the %d rows of the weights' % (what, k0, -k0, w.size))
+    w = np.ascontiguousarray(w32)
+    if not w[-k0] > 0:
+        raise RuntimeError("%s: the start frame's own weight, weights[%d], must be > 0, got %r" % (what, -k0, float(w[-k0])))
+    points, start, (R, t, K_T), T1, B, H, W, N = _track_args(what, points, start, tables, planar, host_start)
+    dev = points.device
+    if T1 != w.size:
+        raise RuntimeError('%s: %d weights for a slab of %d rows (at most %d)' % (what, w.size, T1, FILTER_MAX_ROWS))
+    if depth_all is None:
+        raise RuntimeError('%s: depth_all is required' % what)
+    depth_all = _dev32(depth_all, 'depth_all')
+    if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
+        raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
+            what, N, H, W, tuple(depth_all.shape)))
+    wdev = torch.from_numpy(w).to(dev)
+    shapes = {'depth': ((B, 1, H, W), torch.float32)}
+    for k in ('ratio', 'count', 'spread'):
+        if k in want:
+            shapes[k] = ((B, H, W), torch.uint8) if k == 'count' else ((B, 1, H, W), torch.float32)
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        o = out.get(k) if out is not None else None
+        if o is None:
+            o = torch.empty(shape, device=dev, dtype=dtype)
+        elif not (torch.is_tensor(o) and o.device == dev and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
+            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the points' % (what, k, dtype, shape))
+        res[k] = o
+    _lib.check(_lib.load().dvd_track_filter(
+        _p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N, _p(wdev), FILTER_MODES[mode],
+        float(tol), float(z_near), _p(res['depth']), _p(res.get('ratio')), _p(res.get('count')), _p(res.get('spread')),
+        T1, B, H, W, k0, _stream()), 'dvd_track_filter')
+    return res
+
+
 def _like(what, name, t, ref):
     if not (torch.is_tensor(t) and t.is_cuda and t.device == ref.device and t.dtype == torch.float32 and t.shape == ref.shape
             and t.is_contiguous()):
@@ -894,7 +969,7 @@ BYTE_CLASS_KERNELS = {
                                                   'head1x1_', 'cast_scale_kernel'),
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
                                                    'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
-                                                   'depth_score_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'depth_score_kernel', 'track_filter_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

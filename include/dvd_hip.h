@@ -795,6 +795,30 @@ int dvd_track_project_from(const float* points, int points_planar, const int* st
                            const float* K_T, const float* depth_all, int N, float* uv, int displacement, float* z,
                            float* depth_at, unsigned char* inside, int T1, int B, int H, int W, int k0, dvd_stream_t stream);
 
+/* Geometry-aware temporal depth filter along two-sided tracks (an addition within ABI 8; csrc/track_filter.hip,
+ * models/filter.py).  points, start, the tables, depth_all (required here) and k0 are dvd_track_project_from's: row k of image b
+ * is the world point of every pixel of frame start[b] in frame g = start[b] + k + k0; row o = -k0 is the start frame itself
+ * (0 <= o < T1 <= 33).  Per pixel p of image b, with d0 = depth_all[start[b]][p]:
+ *   every row k != o whose frame exists is projected and sampled exactly as dvd_track_project_from does it (the same z,
+ *   depth_at = D and inside, bit for bit) and COUNTS iff  inside && z >= z_near && D > 0 && z <= D * (1 + tol) &&
+ *   D <= z * (1 + tol);  its sample is r = D / z.  Row o always counts with r = 1.
+ *   mode 0   ratio = (sum of weights[k] * r) / (sum of weights[k]) over the counting rows in ascending k, every multiply and
+ *            add a separate fp32 operation;  weights: device fp32 [T1], >= 0, weights[o] > 0 (the caller's duty)
+ *   mode 1   ratio = the median of the counting samples ((a + b) * 0.5f of the two middle ones for an even count); weights
+ *            is not read but must not be NULL
+ *   depth_out [B,1,H,W] = d0 * ratio;  ratio [B,1,H,W];  count uint8 [B,H,W] = counting rows, 1 .. 33;  spread [B,1,H,W] =
+ *            largest minus smallest counting r.  ratio, count, spread may be NULL.
+ *   !(d0 > 0), NaN included:  depth_out = d0, ratio = 1, count = 0, spread = 0.
+ * The ratio is taken along the target camera's ray and applied along the start camera's.  No atomics, one writer per output
+ * element, plain vector stores: the same inputs give the same bits.  16-byte accesses where W is a multiple of 4 and the
+ * bases are 16-byte aligned, one pixel per thread otherwise; the median keeps its samples in LDS (T1 * 1 KiB per block).
+ * DVD_EINVAL before any launch for a null pointer, T1 outside 1 .. 33, o outside the slab, a mode other than 0 / 1, tol or
+ * z_near negative or not finite, and dvd_track_project's shape rules.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_track_filter(const float* points, int points_planar, const int* start, const float* R, const float* t,
+                     const float* K_T, const float* depth_all, int N, const float* weights, int mode, float tol, float z_near,
+                     float* depth_out, float* ratio, unsigned char* count, float* spread, int T1, int B, int H, int W, int k0,
+                     dvd_stream_t stream);
+
 /* Forward splat of world points into target cameras with a soft z-buffer (additions within ABI 8; csrc/splat.hip,
  * models/render.py): the scatter that goes with dvd_track_project's gather.  It draws a frame, pushed along the scene-flow
  * field by the Euler chain of Model.forward_sf_net_multi_step (models/scene_flow_motion_field.py:360-367), in the camera of
