@@ -243,6 +243,9 @@ SIGNATURES = {
     # geometry-aware temporal depth filter along two-sided tracks (csrc/track_filter.hip; an addition within ABI 8)
     'dvd_track_filter': (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_float, c_float] + [c_void_p] * 4 +
                          [c_int] * 5 + [c_void_p]),
+    # triangulated depth and epipolar motion cue from stored flow and cameras (csrc/triangulate.hip; an addition within ABI 8)
+    'dvd_triangulate': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_longlong] + [c_void_p] * 4 +
+                        [c_int, c_int, c_float, c_float, c_float, c_int] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

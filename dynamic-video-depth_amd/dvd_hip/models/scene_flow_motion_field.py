@@ -580,7 +580,7 @@ class Model(NetInterface):
         depth: [N,1,H,W] (default: video_depth of the store); gt: [N,1,H,W] (default: store.depth_mvs); align: 'none' (scale
         1), 'median_frame' (per frame the median of gt / depth over its countable pixels) or 'median_video' (one median over
         the countable pixels of all frames) -- exact medians from ops.ratio_median (csrc/select.hip); regions: split by the
-        store's motion segmentation where it has one; mask: uint8 [N,H,W], non-zero = allowed.  A pixel counts iff gt > 1e-2,
+        store's motion segmentation where it has one; mask: uint8 or bool [N,H,W], non-zero = allowed.  A pixel counts iff gt > 1e-2,
         depth > 0, the scaled depth is finite and the mask allows it.  Returns device tensors (rows: all / static / dynamic):
           sums int64 [N,3,9], shift   the kernel's exact sums (ops.SCORE_SUMS; values * 2^shift);  scale fp32 [N];  n int64 [N,3]
           abs_rel, sq_rel, rmse, rmse_log, silog, d1, d2, d3  float64 [N,3], NaN where n = 0 (silog = mean l^2 - mean(l)^2)

@@ -65,8 +65,10 @@ def score_depth(model, store, depth=None, gt=None, align='median_video', regions
     for name, t in (('depth', depth), ('gt', gt)):
         if tuple(t.shape) != (N, 1, H, W):
             raise ValueError('score_depth: %s must be [%d,1,%d,%d], got %s' % (name, N, H, W, tuple(t.shape)))
+    if torch.is_tensor(mask) and mask.dtype == torch.bool:       # (preprocess.triangulate_depth's 'static': the same bytes, 0 / 1)
+        mask = mask.view(torch.uint8)
     if mask is not None and not (torch.is_tensor(mask) and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W)):
-        raise ValueError('score_depth: mask must be a uint8 tensor [%d,%d,%d]' % (N, H, W))
+        raise ValueError('score_depth: mask must be a uint8 or bool tensor [%d,%d,%d]' % (N, H, W))
     seg = store.motion_seg if regions else None
     with torch.no_grad():
         scale = align_scale(depth, gt, align, mask=mask)

@@ -253,6 +253,115 @@ def track_filter(points, start, tables, depth_all, weights, k0=0, mode='mean', t
     return res
 
 
+TRI_MAX_OBS = 32            # kTriMaxObs of csrc/triangulate.hip
+TRI_TABLES = ('R', 't', 'K_T', 'K_inv_T')
+TRI_SIN2_MIN = 7.615242e-05  # sin^2 of 0.5 degrees
+TRI_OUT = (('depth', torch.float32, True), ('count', torch.uint8, False), ('usable', torch.uint8, False),
+           ('epi', torch.float32, True), ('spread', torch.float32, True))
+
+
+def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='median', epi_tol=1.0, sin2_min=TRI_SIN2_MIN,
+                z_near=1e-3, min_count=2, out=None):
+    """Depth triangulated from stored flow and cameras, fused per pixel over a frame's observations (dvd_triangulate,
+    csrc/triangulate.hip) -> dict of depth, epi, spread [B,1,H,W] fp32 and count, usable [B,H,W] uint8.
+      flow_1_2, flow_2_1   [P,H,W,2] fp32;  mask_1, mask_2  [P,H,W] uint8, 0 = valid  (a FrameStore's tensors)
+      obs      [B,M,3] integral rows (pair, other frame, dir), M <= 32, pair = -1 padding: a host array / sequence / CPU tensor
+               (preprocess.triangulate_plan builds it; uploaded here).  dir 0 reads flow_1_2 with mask_2, dir 1 flow_2_1 with mask_1
+      frames   B query frame ids on the host
+      tables   {'R': [N,3,3] camera to world, 't': [N,3], 'K_T': [N,3,3], 'K_inv_T': [N,3,3]} -- FrameStore.tables has them
+      mode     'mean' (weights sin2) or 'median' of the consistent observations' depth
+      epi_tol  px; sin2_min in (0, 1]: the least squared sine of the parallax angle; z_near; min_count in 1 .. 255
+      out      optional dict of preallocated outputs
+    include/dvd_hip.h has the formulae and the gates.  Everything is checked on the host before the launch, and nothing
+    synchronises with the device."""
+    import math
+    import numpy as np
+    what = 'triangulate'
+    if mode not in FILTER_MODES:
+        raise RuntimeError('%s: mode must be one of %s, got %r' % (what, ', '.join(sorted(FILTER_MODES)), mode))
+    for name, v, lo_open, hi in (('epi_tol', epi_tol, False, None), ('sin2_min', sin2_min, True, 1.0), ('z_near', z_near, False, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0 or \
+                (lo_open and not v > 0) or (hi is not None and v > hi) or not math.isfinite(np.float32(v)):
+            raise RuntimeError('%s: %s must be a finite number %s, got %r' % (what, name, 'in (0, 1]' if lo_open else '>= 0', v))
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= min_count <= 255:
+        raise RuntimeError('%s: min_count must be an integer in 1 .. 255, got %r' % (what, min_count))
+    # the host data first: a bad table is refused before a tensor is looked at
+    try:
+        o = np.asarray(obs.cpu() if torch.is_tensor(obs) else obs)
+        fr = np.asarray(frames.cpu() if torch.is_tensor(frames) else frames)
+    except (TypeError, ValueError):
+        raise RuntimeError('%s: obs and frames must be host arrays of integers' % what)
+    if fr.dtype.kind not in 'iu' or fr.ndim != 1 or fr.size == 0:
+        raise RuntimeError('%s: frames must hold at least one integral frame id, got %s %s' % (what, fr.dtype, fr.shape))
+    B = int(fr.size)
+    if B > 65535:
+        raise RuntimeError('%s: at most 65535 frames per launch, got %d' % (what, B))
+    if o.size == 0 and o.ndim <= 3:
+        o = np.zeros((B, 0, 3), np.int32)
+    if o.dtype.kind not in 'iu' or o.ndim != 3 or o.shape[0] != B or o.shape[2] != 3:
+        raise RuntimeError('%s: obs must be integral [%d,M,3] rows (pair, frame, dir), got %s %s' % (what, B, o.dtype, o.shape))
+    M = int(o.shape[1])
+    if M > TRI_MAX_OBS:
+        raise RuntimeError('%s: obs holds M=%d observations per frame, at most %d' % (what, M, TRI_MAX_OBS))
+    f12 = _dev32(flow_1_2, 'flow_1_2')
+    dev = f12.device
+    if f12.dim() != 4 or f12.shape[3] != 2 or f12.shape[1] < 1 or f12.shape[2] < 1:
+        raise RuntimeError('%s: flow_1_2 must be [P,H,W,2], got %s' % (what, tuple(f12.shape)))
+    P, H, W = (int(v) for v in f12.shape[:3])
+    if H * W >= 1 << 30:
+        raise RuntimeError('%s: images of %d x %d: H * W must stay below 2^30' % (what, H, W))
+    if not (torch.is_tensor(flow_2_1) and flow_2_1.is_cuda and flow_2_1.device == dev and flow_2_1.dtype == torch.float32 and
+            flow_2_1.shape == f12.shape and flow_2_1.is_contiguous() and flow_1_2.is_contiguous()):
+        raise RuntimeError('%s: flow_1_2 and flow_2_1 must be contiguous float32 GPU tensors %s on one device' % (what, tuple(f12.shape)))
+    for name, m in (('mask_1', mask_1), ('mask_2', mask_2)):
+        if not (torch.is_tensor(m) and m.device == dev and m.dtype == torch.uint8 and tuple(m.shape) == (P, H, W) and m.is_contiguous()):
+            raise RuntimeError('%s: %s must be a contiguous uint8 tensor %s on the device of the flows' % (what, name, (P, H, W)))
+    tabs = []
+    for k in TRI_TABLES:
+        if k not in tables:
+            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRI_TABLES)))
+        tab = _dev32(tables[k], 'table ' + k)
+        if tab.device != dev:
+            raise RuntimeError('%s: table %s and the flows are on different devices' % (what, k))
+        tabs.append(tab)
+    N = int(tabs[0].shape[0]) if tabs[0].dim() > 0 else 0
+    for k, tab, per in zip(TRI_TABLES, tabs, (9, 3, 9, 9)):
+        if N <= 0 or tab.dim() < 2 or tab.shape[0] != N or tab.numel() != N * per:
+            raise RuntimeError('%s: table %s must hold %d values for each of %d frames, got %s' % (what, k, per, N, tuple(tab.shape)))
+    if int(fr.min()) < 0 or int(fr.max()) >= N:
+        raise RuntimeError('%s: frames span [%d, %d], outside the %d frames of the tables' % (what, int(fr.min()), int(fr.max()), N))
+    live = o[..., 0] >= 0
+    if M:
+        if int(o[..., 0].min()) < -1 or int(o[..., 0].max()) >= P:
+            raise RuntimeError('%s: obs names pairs in [%d, %d], outside -1 (padding) .. %d' % (
+                what, int(o[..., 0].min()), int(o[..., 0].max()), P - 1))
+        if live.any() and (int(o[..., 1][live].min()) < 0 or int(o[..., 1][live].max()) >= N):
+            raise RuntimeError('%s: obs names frames in [%d, %d], outside the %d frames of the tables' % (
+                what, int(o[..., 1][live].min()), int(o[..., 1][live].max()), N))
+        if live.any() and not np.isin(o[..., 2][live], (0, 1)).all():
+            raise RuntimeError('%s: the dir column of obs must be 0 (flow_1_2) or 1 (flow_2_1)' % what)
+    res = {}
+    for k, dtype, chan in TRI_OUT:
+        shape = (B, 1, H, W) if chan else (B, H, W)
+        t_ = out.get(k) if out is not None else None
+        if t_ is None:
+            t_ = torch.empty(shape, device=dev, dtype=dtype)
+        elif not (torch.is_tensor(t_) and t_.device == dev and t_.dtype == dtype and tuple(t_.shape) == shape and t_.is_contiguous()):
+            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the flows' % (what, k, dtype, shape))
+        res[k] = t_
+    # the frame ids and the table in ONE upload from pinned memory, enqueued on the current stream: a copy from pageable memory
+    # would make the host wait for the stream
+    host = torch.from_numpy(np.concatenate([fr.astype(np.int32), o.astype(np.int32).ravel()])).pin_memory()
+    both = host.to(dev, non_blocking=True)
+    fr_dev, obs_dev = both[:B], (both[B:] if M else None)
+    _lib.check(_lib.load().dvd_triangulate(
+        _p(f12), _p(flow_2_1), _p(mask_1), _p(mask_2), P, _p(obs_dev), _p(fr_dev), int(live.sum()), _p(tabs[0]), _p(tabs[1]),
+        _p(tabs[2]), _p(tabs[3]), N, FILTER_MODES[mode], float(epi_tol), float(sin2_min), float(z_near), int(min_count),
+        _p(res['depth']), _p(res['count']), _p(res['usable']), _p(res['epi']), _p(res['spread']), M, B, H, W, _stream()),
+        'dvd_triangulate')
+    return res
+
+
 def _like(what, name, t, ref):
     if not (torch.is_tensor(t) and t.is_cuda and t.device == ref.device and t.dtype == torch.float32 and t.shape == ref.shape
             and t.is_contiguous()):
@@ -969,7 +1078,7 @@ BYTE_CLASS_KERNELS = {
                                                   'head1x1_', 'cast_scale_kernel'),
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
                                                    'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
-                                                   'depth_score_kernel', 'track_filter_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'depth_score_kernel', 'track_filter_kernel', 'triangulate_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

@@ -49,6 +49,82 @@ def calibrate_scale(depth_nn, depth_mvs, thresh=1e-3):
     return scales, np.mean(scales.cpu().numpy())
 
 
+def triangulate_plan(pairs, n_frames, frames=None, gaps=None):
+    """The observation table of ops.triangulate from `Catalogue.pairs` (host only) -> (frames int32 [B], obs int32 [B,M,3]).
+    Per query frame, every stored pair (f_1, f_2) that contains it -- restricted to |f_2 - f_1| in `gaps` if given -- as a row
+    (pair index, the other frame, dir): dir 0 where the frame is the pair's first (flow_1_2 leaves it), 1 where it is the second
+    (flow_2_1).  Rows are ordered by |gap| ascending, forward before backward, then by pair index, and padded with -1 to the
+    longest row (M = 0 if no frame has a pair).  frames=None: all of them."""
+    import numpy as np
+    from . import ops
+    n_frames = int(n_frames)
+    if frames is None:
+        frames = range(n_frames)
+    frames = [int(f) for f in frames]
+    if not frames or min(frames) < 0 or max(frames) >= n_frames:
+        raise ValueError('triangulate_plan: frames must name at least one of the %d frames, got %r' % (n_frames, frames))
+    keep = None if gaps is None else set(abs(int(g)) for g in gaps)
+    if keep is not None and (not keep or min(keep) < 1):
+        raise ValueError('triangulate_plan: gaps must be non-zero frame distances, got %r' % (gaps,))
+    per = {f: [] for f in set(frames)}
+    for j, (a, b) in enumerate(pairs):
+        a, b = int(a), int(b)
+        if a == b or not (0 <= a < n_frames and 0 <= b < n_frames):
+            raise ValueError('triangulate_plan: pair %d is (%d, %d) in a video of %d frames' % (j, a, b, n_frames))
+        if keep is not None and abs(b - a) not in keep:
+            continue
+        if a in per:
+            per[a].append((abs(b - a), 0, j, b))
+        if b in per:
+            per[b].append((abs(b - a), 1, j, a))
+    M = max(len(v) for v in per.values())
+    if M > ops.TRI_MAX_OBS:
+        f = max(per, key=lambda k: len(per[k]))
+        raise ValueError('triangulate_plan: frame %d has %d observations, at most %d (restrict `gaps`)' % (f, M, ops.TRI_MAX_OBS))
+    obs = np.full((len(frames), M, 3), -1, dtype=np.int32)
+    for i, f in enumerate(frames):
+        for m, (_, d, j, other) in enumerate(sorted(per[f])):
+            obs[i, m] = (j, other, d)
+    return np.array(frames, dtype=np.int32), obs
+
+
+def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0, min_parallax_deg=0.5, z_near=1e-3, min_count=2,
+                      tables=None, chunk=None):
+    """A depth map that does not depend on the network, a confidence for it and a motion cue, from a FrameStore's flows,
+    occlusion masks and cameras (ops.triangulate, csrc/triangulate.hip; the table of triangulate_plan over store.cat.pairs).
+    -> dict on the device, for the B requested frames (None: all):
+      depth [B,1,H,W]   the consistent observations' triangulated depth fused by `mode`; 0 where fewer than min_count agree
+      count, usable     uint8 [B,H,W]: consistent observations, and those with a valid flow and enough parallax
+      epi [B,1,H,W]     mean epipolar distance of the usable observations in pixels (-1 without one)
+      spread [B,1,H,W]  (max - min) of the consistent depths over the fused one
+      static, moving    bool [B,H,W]: count >= min_count;  usable >= min_count and no consistent observation
+      frames            the frame ids, int32 on the host
+    min_parallax_deg: an observation whose rays meet under a smaller angle is not used.  tables: cameras other than the store's
+    (e.g. at another scale).  chunk: frames per launch (None: one launch); it does not change a bit."""
+    import math
+    import numpy as np
+    from . import ops
+    if isinstance(min_parallax_deg, bool) or not isinstance(min_parallax_deg, (int, float)) or not 0 < min_parallax_deg <= 90:
+        raise ValueError('triangulate_depth: min_parallax_deg must be in (0, 90], got %r' % (min_parallax_deg,))
+    if chunk is not None and (isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1):
+        raise ValueError('triangulate_depth: chunk must be a positive number of frames, got %r' % (chunk,))
+    fr, obs = triangulate_plan(store.cat.pairs, store.cat.n_frames, frames, gaps)
+    B, H, W, dev = len(fr), store.H, store.W, store.device
+    chunk = min(B, 65535) if chunk is None else min(int(chunk), 65535)
+    sin2_min = float(np.float32(math.sin(math.radians(min_parallax_deg)) ** 2))
+    tables = store.tables if tables is None else tables
+    res = {k: torch.empty((B, 1, H, W) if chan else (B, H, W), device=dev, dtype=dtype) for k, dtype, chan in ops.TRI_OUT}
+    for b0 in range(0, B, chunk):
+        b1 = min(b0 + chunk, B)
+        ops.triangulate(store.flow_1_2, store.flow_2_1, store.mask_1, store.mask_2, obs[b0:b1], fr[b0:b1], tables, mode=mode,
+                        epi_tol=epi_tol, sin2_min=sin2_min, z_near=z_near, min_count=min_count,
+                        out={k: v[b0:b1] for k, v in res.items()})
+    res['frames'] = fr
+    res['static'] = res['count'] >= min_count
+    res['moving'] = (res['usable'] >= min_count) & (res['count'] == 0)
+    return res
+
+
 def scale_poses(w2c, s):
     """World-to-camera matrices [N,4,4] -> camera-to-world fp32 [N,4,4] at the calibrated scale, the reference's three
     statements per frame (generate_frame_midas.py:180-183): `T[:3, 3] *= s`, `np.linalg.inv(T)`, `.astype(np.float32)`.  Host

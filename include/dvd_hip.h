@@ -819,6 +819,42 @@ int dvd_track_filter(const float* points, int points_planar, const int* start, c
                      float* depth_out, float* ratio, unsigned char* count, float* spread, int T1, int B, int H, int W, int k0,
                      dvd_stream_t stream);
 
+/* Triangulated depth and epipolar motion cue from stored flow and cameras (an addition within ABI 8; csrc/triangulate.hip,
+ * preprocess.triangulate_depth).  For query frame a = frames[b] and pixel x = (u, v, 1), row b of the observation table
+ *   obs      int32 [B, M, 3], rows (pair, other frame, dir), M <= 32; pair = -1 is padding and may stand anywhere in a row
+ *   dir 0    reads flow_1_2[pair] with mask_2[pair] (a is the pair's first frame)
+ *   dir != 0 reads flow_2_1[pair] with mask_1[pair] (a is the pair's second frame)
+ *   flows    fp32 [P, H, W, 2];  masks uint8 [P, H, W], 0 = valid;  frames int32 [B]
+ *   R, t, K_T, K_inv_T   the per-frame tables [N,3,3], [N,3], [N,3,3], [N,3,3]: R camera to world (row-major), t the camera
+ *            centre, K_T and K_inv_T the transposed intrinsics and their inverse
+ * is walked in ascending order.  Per observation, with b the other frame, every multiply and add a separate fp32 operation,
+ * every three-term sum as (p0 + p1) + p2, divisions and the square root IEEE:
+ *   x' = x + flow;  d1 = R_a (K_a^-1 x);  d2 = R_b (K_b^-1 x');  bl = t_b - t_a
+ *   A = d1.d1, Bq = d1.d2, C = d2.d2, E = d1.bl, F = d2.bl, den = A C - Bq Bq
+ *   s1 = (E C - Bq F) / den (the planar depth in frame a),  s2 = (Bq E - A F) / den,  sin2 = den / (A C)
+ *   h0 = K_b (R_b^T (t_a - t_b)),  h1 = K_b (R_b^T d1),  l = h0 x h1,
+ *   e = |(l0 x'0 + l1 x'1) + l2| / sqrt(l0 l0 + l1 l1) (epipolar distance in pixels), replaced by 1e30 unless e <= 1e30
+ *   usable      mask byte == 0 && 0 <= x'0 <= W-1 && 0 <= x'1 <= H-1 && sin2 >= sin2_min
+ *   consistent  usable && e <= epi_tol && z_near <= s1 <= 1e30 && z_near <= s2 <= 1e30
+ * (a NaN fails every comparison).  Outputs per query pixel:
+ *   depth  [B,1,H,W]  mode 0: (sum of sin2 * s1) / (sum of sin2) over the consistent observations;  mode 1: their exact
+ *                     median, (lo + hi) * 0.5f of the two middle ones for an even count;  0 where count < min_count
+ *   count, usable  uint8 [B,H,W]  the number of consistent and of usable observations
+ *   epi    [B,1,H,W]  (sum of e over the usable observations) / usable;  -1 where usable == 0
+ *   spread [B,1,H,W]  (largest - smallest consistent s1) / depth, at most 1e30;  0 where depth == 0
+ * No output ever holds a NaN or an Inf.  The kernel reads only the query pixel's own element of each flow and mask (nothing
+ * is gathered at x'), and skips a row whose pair is outside 0 .. P-1 or whose frame is outside 0 .. N-1; a query frame
+ * outside 0 .. N-1 gives depth = spread = 0, epi = -1, count = usable = 0.  live_rows: the number of rows with pair >= 0 over
+ * the B frames (byte accounting only).  One thread per pixel, grid (ceil(H W / 256), B); the median keeps its samples in LDS
+ * (M * 1 KiB per block).  DVD_EINVAL before any launch for a null pointer, M outside 0 .. 32, B outside 1 .. 65535,
+ * H * W >= 2^30, a mode other than 0 / 1, epi_tol or z_near negative or not finite, sin2_min outside (0, 1], min_count outside
+ * 1 .. 255.  Bytes are counted under DVD_BYTES_GEOMETRY: H W (9 live_rows + 14 B). */
+int dvd_triangulate(const float* flow_1_2, const float* flow_2_1, const unsigned char* mask_1, const unsigned char* mask_2, int P,
+                    const int* obs, const int* frames, long long live_rows, const float* R, const float* t, const float* K_T,
+                    const float* K_inv_T, int N, int mode, float epi_tol, float sin2_min, float z_near, int min_count,
+                    float* depth, unsigned char* count, unsigned char* usable, float* epi, float* spread, int M, int B, int H,
+                    int W, dvd_stream_t stream);
+
 /* Forward splat of world points into target cameras with a soft z-buffer (additions within ABI 8; csrc/splat.hip,
  * models/render.py): the scatter that goes with dvd_track_project's gather.  It draws a frame, pushed along the scene-flow
  * field by the Euler chain of Model.forward_sf_net_multi_step (models/scene_flow_motion_field.py:360-367), in the camera of
