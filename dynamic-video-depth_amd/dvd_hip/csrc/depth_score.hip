@@ -23,9 +23,8 @@
 // threads of its frame, grid-stride, before it reduces (27 64-bit wave reductions per block with seg are the cost to amortise).
 
 #include <float.h>
-#include <stdint.h>
 
-#include "dvd_common.h"
+#include "dvd_post.h"
 
 namespace dvd {
 
@@ -47,60 +46,24 @@ struct ScoreArgs {
   double scale2;                             // 2^shift
 };
 
-__device__ __forceinline__ long long score_fixed(float x, double scale) { return llrint((double)x * scale); }
-
-__device__ __forceinline__ long long score_wave_sum(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;
-}
-
-template <int PX>
-__device__ __forceinline__ void score_load(const float* src, float v[PX]) {
-  if (PX == 4)
-    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(src);
-  else
-    v[0] = src[0];
-}
-
-template <int PX>
-__device__ __forceinline__ void score_store(float* dst, const float v[PX]) {
-  if (PX == 4)
-    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    dst[0] = v[0];
-}
-
-template <int PX>
-__device__ __forceinline__ void score_load_bytes(const unsigned char* src, unsigned int v[PX]) {
-  if (PX == 4) {
-    const unsigned int m4 = *reinterpret_cast<const unsigned int*>(src);
-    v[0] = m4 & 255u, v[1] = (m4 >> 8) & 255u, v[2] = (m4 >> 16) & 255u, v[3] = m4 >> 24;
-  } else {
-    v[0] = src[0];
-  }
-}
-
 template <int PX, bool SEG, bool MASK, bool MAPS>
 __global__ __launch_bounds__(256) void depth_score_kernel(const ScoreArgs a) {
   constexpr int R = SEG ? kScoreRegions : 1;
   constexpr int kStatic = SEG ? 1 : 0, kDynamic = SEG ? 2 : 0;      // (rows that exist only with seg)
   const int n = blockIdx.y;
-  long long acc[R][kScoreSums];
+  long long acc[R * kScoreSums];      // [region][word]
 #pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int k = 0; k < kScoreSums; ++k) acc[r][k] = 0;
+  for (int k = 0; k < R * kScoreSums; ++k) acc[k] = 0;
   const float sc = a.scale[n];
   // a block walks up to kScoreTrips strips of its frame, so that the reduction below is paid once per 4096 (1024) pixels
   for (int p0 = (blockIdx.x * 256 + threadIdx.x) * PX; p0 < a.HW; p0 += gridDim.x * 256 * PX) {
     const size_t o = (size_t)n * a.HW + p0;
     float p[PX], g[PX], sg[PX], m_abs[PX], m_sq[PX], m_l[PX];
     unsigned int mk[PX], cnt[PX];
-    score_load<PX>(a.pred + o, p);
-    score_load<PX>(a.gt + o, g);
-    if (SEG) score_load<PX>(a.seg + o, sg);
-    if (MASK) score_load_bytes<PX>(a.mask + o, mk);
+    ldpx<PX>(a.pred + o, p);
+    ldpx<PX>(a.gt + o, g);
+    if (SEG) ldpx<PX>(a.seg + o, sg);
+    if (MASK) ldpx_bytes<PX>(a.mask + o, mk);
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
       const float q = sc * p[i];
@@ -118,59 +81,35 @@ __global__ __launch_bounds__(256) void depth_score_kernel(const ScoreArgs a) {
       const float ratio = fmaxf(q / g[i], g[i] / q);
       long long t[kScoreSums];
       t[0] = 1;
-      t[1] = score_fixed(abs_rel, a.scale2);
-      t[2] = score_fixed(sq_rel, a.scale2);
-      t[3] = score_fixed(sq, a.scale2);
-      t[4] = score_fixed(l2, a.scale2);
-      t[5] = score_fixed(l, a.scale2);
+      t[1] = fixed_q(abs_rel, a.scale2);
+      t[2] = fixed_q(sq_rel, a.scale2);
+      t[3] = fixed_q(sq, a.scale2);
+      t[4] = fixed_q(l2, a.scale2);
+      t[5] = fixed_q(l, a.scale2);
       t[6] = ratio < 1.25f ? 1 : 0;
       t[7] = ratio < 1.5625f ? 1 : 0;
       t[8] = ratio < 1.953125f ? 1 : 0;
       m_abs[i] = abs_rel, m_sq[i] = sq, m_l[i] = l;
 #pragma unroll
-      for (int k = 0; k < kScoreSums; ++k) acc[0][k] += t[k];
+      for (int k = 0; k < kScoreSums; ++k) acc[k] += t[k];
       if (SEG) {
         const bool stat = sg[i] <= 0.5f, dyn = sg[i] > 0.5f;      // a NaN is neither
 #pragma unroll
         for (int k = 0; k < kScoreSums; ++k) {
-          acc[kStatic][k] += stat ? t[k] : 0;
-          acc[kDynamic][k] += dyn ? t[k] : 0;
+          acc[kStatic * kScoreSums + k] += stat ? t[k] : 0;
+          acc[kDynamic * kScoreSums + k] += dyn ? t[k] : 0;
         }
       }
     }
     if (MAPS) {
       float* m = a.maps + (size_t)n * 3 * a.HW + p0;
-      score_store<PX>(m, m_abs);
-      score_store<PX>(m + a.HW, m_sq);
-      score_store<PX>(m + 2 * (size_t)a.HW, m_l);
-      if (PX == 4)
-        *reinterpret_cast<unsigned int*>(a.counted + o) = cnt[0] | (cnt[1] << 8) | (cnt[2] << 16) | (cnt[3] << 24);
-      else
-        a.counted[o] = (unsigned char)cnt[0];
+      stpx<PX>(m, m_abs);
+      stpx<PX>(m + a.HW, m_sq);
+      stpx<PX>(m + 2 * (size_t)a.HW, m_l);
+      stpx_bytes<PX>(a.counted + o, cnt);
     }
   }
-  __shared__ long long red[4][R * kScoreSums];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int k = 0; k < kScoreSums; ++k) {
-      const long long v = score_wave_sum(acc[r][k]);
-      if (lane == 0) red[wave][r * kScoreSums + k] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < R * kScoreSums) {
-    const long long v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    if (v != 0) atomicAdd(a.sums + (size_t)n * kScoreRegions * kScoreSums + threadIdx.x, (unsigned long long)v);
-  }
-}
-
-static bool score_aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-static int score_ceil_log2(long long n) {
-  int k = 0;
-  while ((1LL << k) < n) ++k;
-  return k;
+  block_add_i64<R * kScoreSums>(acc, a.sums + (size_t)n * kScoreRegions * kScoreSums);
 }
 
 template <int PX, bool SEG, bool MASK>
@@ -208,18 +147,18 @@ int dvd_depth_score(const float* pred, const float* gt, const float* scale, cons
   DVD_REQUIRE(HW < (1LL << 30) && (long long)N * HW < (1LL << 40), "depth_score: image too large N=%d H=%d W=%d", N, H, W);
   DVD_REQUIRE(g_min >= 0.0f && g_min <= FLT_MAX, "depth_score: g_min=%g must be finite and >= 0", (double)g_min);
   // N * H * W terms of at most 2^10 * 2^shift each can meet in one pooled sum: they must stay below 2^62
-  DVD_REQUIRE(shift >= 1 && shift <= 32 && shift + kScoreCapLog2 + score_ceil_log2((long long)N * HW) <= 62,
+  DVD_REQUIRE(shift >= 1 && shift <= 32 && shift + kScoreCapLog2 + ceil_log2((long long)N * HW) <= 62,
               "depth_score: shift=%d outside 1 .. min(32, 62 - 10 - ceil_log2(N * H * W)) for N=%d H=%d W=%d", shift, N, H, W);
-  DVD_REQUIRE(score_aligned(pred, 4) && score_aligned(gt, 4) && score_aligned(scale, 4) && score_aligned(seg, 4) &&
-                  score_aligned(maps, 4) && score_aligned(sums, 8),
+  DVD_REQUIRE(aligned_to(pred, 4) && aligned_to(gt, 4) && aligned_to(scale, 4) && aligned_to(seg, 4) &&
+                  aligned_to(maps, 4) && aligned_to(sums, 8),
               "depth_score: misaligned pointer (floats: 4 bytes; sums: 8 bytes)");
   ScoreArgs a = {};
   a.pred = pred, a.gt = gt, a.scale = scale, a.seg = seg, a.mask = mask;
   a.sums = reinterpret_cast<unsigned long long*>(sums), a.maps = maps, a.counted = counted;
   a.HW = (int)HW, a.g_min = g_min, a.scale2 = (double)(1ULL << shift);
   bytes_add(DVD_BYTES_GEOMETRY, (double)N * HW * (8.0 + (seg ? 4.0 : 0.0) + (mask ? 1.0 : 0.0) + (maps ? 13.0 : 0.0)));
-  const bool v4 = (W % 4 == 0) && score_aligned(pred, 16) && score_aligned(gt, 16) && score_aligned(seg, 16) &&
-                  score_aligned(mask, 4) && score_aligned(maps, 16) && score_aligned(counted, 4);
+  const bool v4 = (W % 4 == 0) && aligned_to(pred, 16) && aligned_to(gt, 16) && aligned_to(seg, 16) &&
+                  aligned_to(mask, 4) && aligned_to(maps, 16) && aligned_to(counted, 4);
   const int px = v4 ? 4 : 1;
   const long long strips = (HW + 256 * px - 1) / (256 * px);
   dim3 grid((unsigned)((strips + kScoreTrips - 1) / kScoreTrips), (unsigned)N);

@@ -1,9 +1,9 @@
 // A finished optimisation scored along its tracks: how well do depth, scene flow, cameras and optical flow agree? (gfx950)
 //
 // Row r of image b holds the world points of frame source[b]'s pixels, integrated along the scene-flow field to the time of
-// frame g = source[b] + k_first + r (models/tracks.py).  Every point is projected into the camera of g exactly as
-// dvd_track_project projects it (project_point of track_cam.h, sample_coord / bilinear of warp_pixel.h, -ffp-contract=off: the
-// same point and table row give the same u, v, z and the same taps, bit for bit) and compared with what frame g holds there:
+// frame g = source[b] + k_first + r (models/tracks.py).  Every point is projected into the camera of g by the functions
+// dvd_track_project projects it with (track_project, track_taps, tap_sample of track_sample.h, -ffp-contract=off: the same
+// point and table row give the same u, v, z and the same taps, bit for bit) and compared with what frame g holds there:
 //     inside    z > 0 && 0 <= u <= W - 1 && 0 <= v <= H - 1
 //     d         depth_all[g] at (u, v), bilinear, border                               (where inside)
 //     occluded  z > d * (1 + z_tol)            seen = inside && !occluded
@@ -23,8 +23,7 @@
 
 #include <float.h>
 
-#include "track_cam.h"
-#include "warp_pixel.h"
+#include "track_sample.h"
 
 namespace dvd {
 
@@ -44,34 +43,11 @@ struct EvalArgs {
   unsigned long long* sums;     // [T,B,6], step stride sums_stride
   float* maps;                  // [T,B,3,H,W], step stride maps_stride, or null
   long long sums_stride, maps_stride;
-  int B, N, P, H, W, HW, k_first;
-  float tol, d_min, half_w, half_h, wmax, hmax;
+  int B, N, P, HW, k_first;
+  float tol, d_min;
+  TrackView view;               // the image size and the constants of the sampling chain (track_sample.h)
   double scale;                 // 2^shift
 };
-
-__device__ __forceinline__ long long eval_fixed(float x, double scale) { return llrint((double)x * scale); }
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;
-}
-
-template <int PX>
-__device__ __forceinline__ void eval_store(float* dst, const float v[PX]) {
-  if (PX == 4)
-    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-  else
-    dst[0] = v[0];
-}
-
-template <int PX>
-__device__ __forceinline__ void eval_load(const float* src, float v[PX]) {
-  if (PX == 4)
-    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(src);
-  else
-    v[0] = src[0];
-}
 
 template <int PX, bool FLOW, bool MAPS>
 __global__ __launch_bounds__(256) void eval_tracks_kernel(const EvalArgs a) {
@@ -93,15 +69,15 @@ __global__ __launch_bounds__(256) void eval_tracks_kernel(const EvalArgs a) {
     const size_t img = (size_t)r * a.B + b;
     float P[3][PX];
     load_points<PX, true>(a.points, img, p0, a.HW, P);
-    const int y = p0 / a.W, x = p0 - y * a.W;
+    const int y = p0 / a.view.W, x = p0 - y * a.view.W;
     const float yf = (float)y;
     const float* dg = a.depth_all + (size_t)g * a.HW;
     const float* cg = a.img_all + (size_t)g * 3 * a.HW;
     const float* own = a.img_all + (size_t)s * 3 * a.HW + p0;
     float o0[PX], o1[PX], o2[PX];
-    eval_load<PX>(own, o0);
-    eval_load<PX>(own + a.HW, o1);
-    eval_load<PX>(own + 2 * (size_t)a.HW, o2);
+    ldpx<PX>(own, o0);
+    ldpx<PX>(own + a.HW, o1);
+    ldpx<PX>(own + 2 * (size_t)a.HW, o2);
     // the row of this (step, image) in the flow tensors, or -1; a row the tensors do not have counts as none
     int row = -1;
     if (FLOW) {
@@ -115,92 +91,50 @@ __global__ __launch_bounds__(256) void eval_tracks_kernel(const EvalArgs a) {
     if (FLOW && row >= 0) {
       const size_t fp = (size_t)row * a.HW + p0;
       if (PX == 4) {
-        *reinterpret_cast<float4*>(fl) = *reinterpret_cast<const float4*>(a.flow + 2 * fp);
-        *reinterpret_cast<float4*>(fl + 4) = *reinterpret_cast<const float4*>(a.flow + 2 * fp + 4);
-        const unsigned int m4 = *reinterpret_cast<const unsigned int*>(a.mask + fp);
-        mk[0] = m4 & 255u, mk[1] = (m4 >> 8) & 255u, mk[2] = (m4 >> 16) & 255u, mk[3] = m4 >> 24;
+        ldpx<4>(a.flow + 2 * fp, fl);
+        ldpx<4>(a.flow + 2 * fp + 4, fl + 4);
       } else {
         fl[0] = a.flow[2 * fp], fl[1] = a.flow[2 * fp + 1];
-        mk[0] = a.mask[fp];
       }
+      ldpx_bytes<PX>(a.mask + fp, mk);
     }
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
       const float xf = (float)(x + i);
-      float I0, I1, I2;
-      project_point(c, P[0][i], P[1][i], P[2][i], I0, I1, I2);
-      const float den = I2 + 1e-8f;
-      const float ui = I0 / den, vi = I1 / den;
-      const float dx = ui - xf, dy = vi - yf;      // the displacement field of the projection
-      const bool front = I2 > 0.0f;
-      const bool inside = front && ui >= 0.0f && ui <= a.wmax && vi >= 0.0f && vi <= a.hmax;
-      if (inside) {
-        // always inside [0, W-1] x [0, H-1]: sample_coord clamps, and its fmaxf / fminf turn a NaN into 0
-        const float ix = sample_coord(xf, dx, a.half_w, a.wmax);
-        const float iy = sample_coord(yf, dy, a.half_h, a.hmax);
-        const float x0f = floorf(ix), y0f = floorf(iy);
-        const float ww = ix - x0f, we = 1.0f - ww, wn = iy - y0f, ws = 1.0f - wn;
-        const int x0 = (int)x0f, y0 = (int)y0f;
-        const bool in_e = (x0 + 1) < a.W, in_s = (y0 + 1) < a.H;
-        const int o = y0 * a.W + x0;
-        const int oe = in_e ? o + 1 : o, os = in_s ? o + a.W : o, ose = in_s ? oe + a.W : oe;   // (addresses only)
-        const float w_nw = ws * we, w_ne = ws * ww, w_sw = wn * we, w_se = wn * ww;
-        const float d = bilinear(dg[o], in_e ? dg[oe] : 0.0f, in_s ? dg[os] : 0.0f, (in_e && in_s) ? dg[ose] : 0.0f, w_nw, w_ne,
-                                 w_sw, w_se);
-        const bool occluded = I2 > d * a.tol;
+      const TrackProj h = track_project(c, a.view, P[0][i], P[1][i], P[2][i], xf, yf);
+      if (h.in) {
+        const TrackTaps tp = track_taps(a.view, xf, yf, h.dx, h.dy);      // one tap set for the depth and the three colours
+        const float d = tap_sample(dg, tp);
+        const bool occluded = h.z > d * a.tol;
         acc[0] += 1;
         if (occluded) {
           acc[1] += 1;
         } else {
-          rel[i] = fminf(fabsf(I2 - d) / fmaxf(d, a.d_min), 1.0f);
+          rel[i] = fminf(fabsf(h.z - d) / fmaxf(d, a.d_min), 1.0f);
           float col[3];
 #pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            const float* cc = cg + (size_t)ch * a.HW;
-            col[ch] = bilinear(cc[o], in_e ? cc[oe] : 0.0f, in_s ? cc[os] : 0.0f, (in_e && in_s) ? cc[ose] : 0.0f, w_nw, w_ne,
-                               w_sw, w_se);
-          }
+          for (int ch = 0; ch < 3; ++ch) col[ch] = tap_sample(cg + (size_t)ch * a.HW, tp);
           const float l1 = (fabsf(col[0] - o0[i]) + fabsf(col[1] - o1[i])) + fabsf(col[2] - o2[i]);
           photo[i] = fminf(l1 / 3.0f, kEvalCap);
-          acc[2] += eval_fixed(rel[i], a.scale);
-          acc[3] += eval_fixed(photo[i], a.scale);
+          acc[2] += fixed_q(rel[i], a.scale);
+          acc[3] += fixed_q(photo[i], a.scale);
         }
       }
-      if (FLOW && row >= 0 && mk[i] == 0u && front) {
-        epe[i] = fminf(hypotf(dx - fl[2 * i], dy - fl[2 * i + 1]), kEvalCap);
+      if (FLOW && row >= 0 && mk[i] == 0u && h.front) {
+        epe[i] = fminf(hypotf(h.dx - fl[2 * i], h.dy - fl[2 * i + 1]), kEvalCap);
         acc[4] += 1;
-        acc[5] += eval_fixed(epe[i], a.scale);
+        acc[5] += fixed_q(epe[i], a.scale);
       }
     }
   }
   if (MAPS && have) {
     float* m = a.maps + (size_t)r * a.maps_stride + (size_t)b * 3 * a.HW + p0;
-    eval_store<PX>(m, rel);
-    eval_store<PX>(m + a.HW, photo);
-    eval_store<PX>(m + 2 * (size_t)a.HW, epe);
+    stpx<PX>(m, rel);
+    stpx<PX>(m + a.HW, photo);
+    stpx<PX>(m + 2 * (size_t)a.HW, epe);
   }
   if (!live) return;      // uniform over the block: nothing to add
-  __shared__ long long red[4][kEvalSums];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kEvalSums; ++k) {
-    const long long v = wave_sum_i64(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kEvalSums) {
-    const long long v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    if (v != 0)
-      atomicAdd(a.sums + (size_t)r * a.sums_stride + (size_t)b * kEvalSums + threadIdx.x, (unsigned long long)v);
-  }
-}
-
-static bool eval_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int eval_ceil_log2(long long n) {
-  int k = 0;
-  while ((1LL << k) < n) ++k;
-  return k;
+  block_add_i64<kEvalSums>(acc, a.sums + (size_t)r * a.sums_stride + (size_t)b * kEvalSums);
 }
 
 template <int PX>
@@ -238,7 +172,7 @@ int dvd_eval_tracks(const float* points, const int* source, int k_first, const f
   DVD_REQUIRE(d_min > 0.0f && d_min <= FLT_MAX, "eval_tracks: d_min=%g must be finite and > 0", (double)d_min);
   const long long HW = (long long)H * W;
   // a row sums H*W terms of at most 2^10 * 2^shift each: they must stay below 2^62
-  DVD_REQUIRE(shift >= 1 && shift <= 32 && shift + kEvalCapLog2 + eval_ceil_log2(HW) <= 62,
+  DVD_REQUIRE(shift >= 1 && shift <= 32 && shift + kEvalCapLog2 + ceil_log2(HW) <= 62,
               "eval_tracks: shift=%d outside 1 .. min(32, 62 - 10 - ceil_log2(H * W)) for H=%d W=%d", shift, H, W);
   DVD_REQUIRE(sums_step_stride >= (long long)B * kEvalSums, "eval_tracks: sums step stride %lld below B * 6", sums_step_stride);
   DVD_REQUIRE(!maps || maps_step_stride >= (long long)B * 3 * HW, "eval_tracks: maps step stride %lld below B * 3 * H * W",
@@ -248,15 +182,15 @@ int dvd_eval_tracks(const float* points, const int* source, int k_first, const f
   a.pair_row = pair_row, a.flow = flow_1_2, a.mask = mask;
   a.sums = reinterpret_cast<unsigned long long*>(sums), a.maps = maps;
   a.sums_stride = sums_step_stride, a.maps_stride = maps ? maps_step_stride : 0;
-  a.B = B, a.N = N, a.P = P, a.H = H, a.W = W, a.HW = (int)HW, a.k_first = k_first;
+  a.B = B, a.N = N, a.P = P, a.HW = (int)HW, a.k_first = k_first;
   a.tol = 1.0f + z_tol, a.d_min = d_min;
-  a.half_w = (float)((W - 1) / 2.0), a.half_h = (float)((H - 1) / 2.0), a.wmax = (float)(W - 1), a.hmax = (float)(H - 1);
+  a.view = track_view(H, W);
   a.scale = (double)(1ULL << shift);
   const double pts = (double)T * B * HW;
   const long long frames = N < T + B ? N : T + B;      // distinct target frames whose depth and colours feed the taps
   bytes_add(DVD_BYTES_GEOMETRY, pts * (12.0 + 12.0 + (pair_row ? 9.0 : 0.0) + (maps ? 12.0 : 0.0)) + 16.0 * (double)frames * HW);
-  const bool v4 = (W % 4 == 0) && eval_aligned16(points) && eval_aligned16(img_all) && eval_aligned16(flow_1_2) &&
-                  eval_aligned16(mask) && eval_aligned16(maps) && (maps_step_stride % 4 == 0 || !maps);
+  const bool v4 = (W % 4 == 0) && aligned_to(points, 16) && aligned_to(img_all, 16) && aligned_to(flow_1_2, 16) &&
+                  aligned_to(mask, 16) && aligned_to(maps, 16) && (maps_step_stride % 4 == 0 || !maps);
   const int px = v4 ? 4 : 1;
   dim3 grid((unsigned)((HW + 256 * px - 1) / (256 * px)), B, T);
   hipStream_t s = static_cast<hipStream_t>(stream);

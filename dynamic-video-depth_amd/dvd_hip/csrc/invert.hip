@@ -11,6 +11,7 @@
 // accesses where H * W is a multiple of 4 and the bases are 16-byte aligned, one value per thread otherwise.  Built with
 // -ffp-contract=off like the rest of the geometry (one subtraction per value: the flag only keeps the unit with its class).
 
+#include "dvd_post.h"
 #include "dvd_split.h"
 
 namespace dvd {
@@ -25,10 +26,9 @@ __global__ __launch_bounds__(256) void invert_update_kernel(const float* p, cons
   if (i < per_img) {                          // (no early return: every lane takes part in the wave's max)
     const long long at = (long long)b * per_img + i;
     if (PX == 4) {
-      const float4 a = *reinterpret_cast<const float4*>(p + at), s = *reinterpret_cast<const float4*>(sf + at);
-      const float4 o = *reinterpret_cast<const float4*>(y_old + at);
+      const float4 a = ld4(p + at), s = ld4(sf + at), o = ld4(y_old + at);
       const float4 y = make_float4(a.x - s.x, a.y - s.y, a.z - s.z, a.w - s.w);
-      *reinterpret_cast<float4*>(y_out + at) = y;
+      st4(y_out + at, y);
       m = amax_acc(amax_acc(amax_acc(amax_acc(m, y.x - o.x), y.y - o.y), y.z - o.z), y.w - o.w);
     } else {
       const float o = y_old[at];
@@ -52,8 +52,7 @@ int dvd_track_invert_update(const float* p, const float* sf, const float* y_old,
   DVD_REQUIRE(HW > 0 && HW < (1 << 30), "track_invert_update: bad image size H*W=%d", HW);
   const long long per_img = 3LL * HW;
   bytes_add(DVD_BYTES_GEOMETRY, (double)B * per_img * (y_old == p ? 12.0 : 16.0));
-  auto aligned16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  const bool v4 = (HW % 4 == 0) && aligned16(p) && aligned16(sf) && aligned16(y_old) && aligned16(y_out);
+  const bool v4 = (HW % 4 == 0) && aligned_to(p, 16) && aligned_to(sf, 16) && aligned_to(y_old, 16) && aligned_to(y_out, 16);
   const int px = v4 ? 4 : 1;
   dim3 grid((unsigned)((per_img + 256 * px - 1) / (256 * px)), B), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream);

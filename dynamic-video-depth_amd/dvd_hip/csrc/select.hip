@@ -23,7 +23,7 @@
 
 #include <stdint.h>
 
-#include "dvd_common.h"
+#include "dvd_post.h"
 
 namespace dvd {
 
@@ -68,17 +68,9 @@ __global__ __launch_bounds__(256) void ratio_hist_kernel(const float* __restrict
   for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * PX; i < L; i += (long long)gridDim.x * 256 * PX) {
     float a[PX], b[PX];
     unsigned int m[PX];
-    if (PX == 4) {      // L % 4 == 0 and 16-byte aligned bases: i + 3 < L
-      *reinterpret_cast<float4*>(a) = *reinterpret_cast<const float4*>(num + base + i);
-      *reinterpret_cast<float4*>(b) = *reinterpret_cast<const float4*>(den + base + i);
-      if (MASK) {
-        const unsigned int m4 = *reinterpret_cast<const unsigned int*>(mask + base + i);
-        m[0] = m4 & 255u, m[1] = (m4 >> 8) & 255u, m[2] = (m4 >> 16) & 255u, m[3] = m4 >> 24;
-      }
-    } else {
-      a[0] = num[base + i], b[0] = den[base + i];
-      if (MASK) m[0] = mask[base + i];
-    }
+    ldpx<PX>(num + base + i, a);      // PX == 4: L % 4 == 0 and 16-byte aligned bases, so i + 3 < L
+    ldpx<PX>(den + base + i, b);
+    if (MASK) ldpx_bytes<PX>(mask + base + i, m);
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
       if (!(b[k] > den_min) || (MASK && m[k] == 0u)) continue;
@@ -172,8 +164,8 @@ int dvd_ratio_median(const float* num, const float* den, const unsigned char* ma
   DVD_REQUIRE(S > 0 && S <= 65535 && L > 0, "ratio_median: bad sizes S=%d L=%lld", S, L);
   DVD_REQUIRE(L < (1LL << 31) && (long long)S * L < (1LL << 31), "ratio_median: S * L = %d * %lld must stay below 2^31", S, L);
   DVD_REQUIRE(den_min == den_min, "ratio_median: den_min is NaN");
-  DVD_REQUIRE(((uintptr_t)num & 3) == 0 && ((uintptr_t)den & 3) == 0 && ((uintptr_t)median & 3) == 0 &&
-                  ((uintptr_t)count & 7) == 0 && ((uintptr_t)workspace & 3) == 0,
+  DVD_REQUIRE(aligned_to(num, 4) && aligned_to(den, 4) && aligned_to(median, 4) && aligned_to(count, 8) &&
+                  aligned_to(workspace, 4),
               "ratio_median: misaligned pointer (num, den, median, workspace: 4 bytes; count: 8 bytes)");
   DVD_REQUIRE(workspace_bytes >= (size_t)S * DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT,
               "ratio_median: workspace of %zu bytes below S * %d", workspace_bytes, DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT);
@@ -181,7 +173,7 @@ int dvd_ratio_median(const float* num, const float* den, const unsigned char* ma
   unsigned int* ws = static_cast<unsigned int*>(workspace);
   const int rc = zero_words(ws, S * kSelectSegWords, st);
   if (rc != DVD_OK) return rc;
-  const bool v4 = (L % 4 == 0) && ((uintptr_t)num & 15) == 0 && ((uintptr_t)den & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+  const bool v4 = (L % 4 == 0) && aligned_to(num, 16) && aligned_to(den, 16) && aligned_to(mask, 4);
   const int px = v4 ? 4 : 1;
   long long bx = (L + 256 * px - 1) / (256 * px);
   const long long cap = kSelectMaxBlocks / S > 1 ? kSelectMaxBlocks / S : 1;

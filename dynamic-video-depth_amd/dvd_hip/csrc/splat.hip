@@ -75,10 +75,8 @@ __device__ __forceinline__ bool splat_point(const SplatArgs& a, const TrackCam& 
   if (!ok) return false;
   float P[3][1];
   load_points<1, PLANAR>(a.points, (size_t)s, p, a.HW, P);
-  float I0, I1, I2;
-  project_point(c, P[0][0], P[1][0], P[2][0], I0, I1, I2);
-  const float den = I2 + 1e-8f;
-  const float u = I0 / den, v = I1 / den;
+  float u, v, I2;
+  project_uvz(c, P[0][0], P[1][0], P[2][0], u, v, I2);
   // every comparison is false for a NaN; u, v are finite and within (-1, W) x (-1, H) behind this line
   if (!(I2 > a.z_near && finite_f(I2) && u > -1.0f && u < a.wf && v > -1.0f && v < a.hf)) return false;
   const float x0f = floorf(u), y0f = floorf(v);
@@ -189,31 +187,11 @@ __global__ __launch_bounds__(256) void splat_resolve_kernel(const ResolveArgs a)
   }
 #pragma unroll
   for (int ch = 0; ch < kSplatMaxC; ++ch) {
-    if (ch < a.C) {
-      float* dst = a.image + ((size_t)vw * a.C + ch) * a.HW + p0;
-      if (PX == 4)
-        *reinterpret_cast<float4*>(dst) = make_float4(img[ch][0], img[ch][1], img[ch][2], img[ch][3]);
-      else
-        dst[0] = img[ch][0];
-    }
+    if (ch < a.C) stpx<PX>(a.image + ((size_t)vw * a.C + ch) * a.HW + p0, img[ch]);
   }
-  if (PX == 4) {
-    *reinterpret_cast<float4*>(a.depth + pix) = make_float4(dep[0], dep[1], dep[2], dep[3]);
-    *reinterpret_cast<float4*>(a.weight + pix) = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
-    *reinterpret_cast<unsigned int*>(a.hit + pix) = hit[0] | (hit[1] << 8) | (hit[2] << 16) | (hit[3] << 24);
-  } else {
-    a.depth[pix] = dep[0];
-    a.weight[pix] = wgt[0];
-    a.hit[pix] = (unsigned char)hit[0];
-  }
-}
-
-static bool splat_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int splat_ceil_log2(long long n) {
-  int k = 0;
-  while ((1LL << k) < n) ++k;
-  return k;
+  stpx<PX>(a.depth + pix, dep);
+  stpx<PX>(a.weight + pix, wgt);
+  stpx_bytes<PX>(a.hit + pix, hit);
 }
 
 static int splat_shape_ok(const char* who, int V, int C, int H, int W) {
@@ -273,7 +251,7 @@ int dvd_splat_accumulate(const float* points, int points_planar, const float* va
               (double)value_bound);
   DVD_REQUIRE(shift >= 1 && shift <= 40, "splat_accumulate: shift=%d outside 1 .. 40", shift);
   // the sum of n_max terms of magnitude <= 2^shift must stay below 2^62
-  DVD_REQUIRE(n_max >= 1 && n_max < (1LL << 61) && shift + splat_ceil_log2(n_max) <= 62,
+  DVD_REQUIRE(n_max >= 1 && n_max < (1LL << 61) && shift + ceil_log2(n_max) <= 62,
               "splat_accumulate: shift=%d overflows 64 bits for n_max=%lld points per view", shift, n_max);
   SplatArgs a = {};
   a.points = points, a.values = values, a.valid = valid, a.view = view, a.R = R, a.t = t, a.K = K_T;
@@ -305,8 +283,8 @@ int dvd_splat_resolve(const unsigned int* zbuf, const unsigned long long* acc, i
   a.zbuf = zbuf, a.acc = acc, a.image = image, a.depth = depth, a.weight = weight, a.hit = hit;
   a.V = V, a.C = C, a.HW = H * W, a.shift = shift, a.w_min = w_min, a.value_bound = value_bound, a.fill = fill;
   bytes_add(DVD_BYTES_GEOMETRY, (double)V * a.HW * (4.0 + 8.0 * (C + 1) + 4.0 * (C + 2) + 1.0));
-  const bool v4 = (W % 4 == 0) && splat_aligned16(zbuf) && splat_aligned16(acc) && splat_aligned16(image) &&
-                  splat_aligned16(depth) && splat_aligned16(weight) && splat_aligned16(hit);
+  const bool v4 = (W % 4 == 0) && aligned_to(zbuf, 16) && aligned_to(acc, 16) && aligned_to(image, 16) &&
+                  aligned_to(depth, 16) && aligned_to(weight, 16) && aligned_to(hit, 16);
   const int px = v4 ? 4 : 1;
   dim3 grid((a.HW + 256 * px - 1) / (256 * px), V), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream);

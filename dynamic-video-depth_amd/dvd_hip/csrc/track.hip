@@ -76,19 +76,15 @@ __global__ __launch_bounds__(256) void track_project_kernel(const TrackArgs a) {
     }
   }
   if (PX == 4) {
-    float4* o = reinterpret_cast<float4*>(a.uv + pix * 2);
-    o[0] = make_float4(u[0], v[0], u[1], v[1]);
-    o[1] = make_float4(u[2], v[2], u[3], v[3]);
-    if (a.z) *reinterpret_cast<float4*>(a.z + pix) = make_float4(zz[0], zz[1], zz[2], zz[3]);
-    if (a.depth_all) *reinterpret_cast<float4*>(a.depth_at + pix) = make_float4(d[0], d[1], d[2], d[3]);
-    if (a.inside) *reinterpret_cast<unsigned int*>(a.inside + pix) = in[0] | (in[1] << 8) | (in[2] << 16) | (in[3] << 24);
+    st4(a.uv + pix * 2, make_float4(u[0], v[0], u[1], v[1]));
+    st4(a.uv + pix * 2 + 4, make_float4(u[2], v[2], u[3], v[3]));
   } else {
     a.uv[pix * 2] = u[0];
     a.uv[pix * 2 + 1] = v[0];
-    if (a.z) a.z[pix] = zz[0];
-    if (a.depth_all) a.depth_at[pix] = d[0];
-    if (a.inside) a.inside[pix] = (unsigned char)in[0];
   }
+  if (a.z) stpx<PX>(a.z + pix, zz);
+  if (a.depth_all) stpx<PX>(a.depth_at + pix, d);
+  if (a.inside) stpx_bytes<PX>(a.inside + pix, in);
 }
 
 // g_P (+)= J^T g_uv with u = I0 / den, v = I1 / den, den = I2 + 1e-8:
@@ -110,8 +106,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
     float P[3][PX], gu[PX], gv[PX];
     load_points<PX, PLANAR>(a.points, img, p0, a.HW, P);
     if (PX == 4) {
-      const float4* s = reinterpret_cast<const float4*>(a.g_uv + pix * 2);
-      const float4 lo = s[0], hi = s[1];
+      const float4 lo = ld4(a.g_uv + pix * 2), hi = ld4(a.g_uv + pix * 2 + 4);
       gu[0] = lo.x, gv[0] = lo.y, gu[1] = lo.z, gv[1] = lo.w;
       gu[2] = hi.x, gv[2] = hi.y, gu[3] = hi.z, gv[3] = hi.w;
     } else {
@@ -120,10 +115,9 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
-      float I0, I1, I2;
-      project_point(c, P[0][i], P[1][i], P[2][i], I0, I1, I2);
+      float ui, vi, I2;
+      project_uvz(c, P[0][i], P[1][i], P[2][i], ui, vi, I2);
       const float den = I2 + 1e-8f;
-      const float ui = I0 / den, vi = I1 / den;
       const float gI0 = gu[i] / den, gI1 = gv[i] / den;
       const float gI2 = -(gu[i] * ui + gv[i] * vi) / den;
       float q0, q1, q2;
@@ -136,16 +130,13 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       float* dst = o + (size_t)ch * a.HW;
-      if (PX == 4) {
-        float4 w = make_float4(G[ch][0], G[ch][1], G[ch][2], G[ch][3]);
-        if (a.accumulate) {
-          const float4 old = *reinterpret_cast<const float4*>(dst);
-          w.x += old.x, w.y += old.y, w.z += old.z, w.w += old.w;
-        }
-        *reinterpret_cast<float4*>(dst) = w;
-      } else {
-        dst[0] = a.accumulate ? dst[0] + G[ch][0] : G[ch][0];
+      float old[PX];
+      if (a.accumulate) {
+        ldpx<PX>(dst, old);
+#pragma unroll
+        for (int i = 0; i < PX; ++i) G[ch][i] += old[i];
       }
+      stpx<PX>(dst, G[ch]);
     }
   } else {
     float* o = a.g_points + pix * 3;
@@ -156,19 +147,16 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const TrackArgs a) {
       w[3 * i + 1] = G[1][i];
       w[3 * i + 2] = G[2][i];
     }
-    if (PX == 4) {
+    // (3 * PX floats: three 16-byte accesses, or three scalars)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        float4 n = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-        if (a.accumulate) {
-          const float4 old = *reinterpret_cast<const float4*>(o + 4 * q);
-          n.x += old.x, n.y += old.y, n.z += old.z, n.w += old.w;
-        }
-        *reinterpret_cast<float4*>(o + 4 * q) = n;
+    for (int q = 0; q < 3; ++q) {
+      float old[PX];
+      if (a.accumulate) {
+        ldpx<PX>(o + PX * q, old);
+#pragma unroll
+        for (int i = 0; i < PX; ++i) w[PX * q + i] += old[i];
       }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) o[q] = a.accumulate ? o[q] + w[q] : w[q];
+      stpx<PX>(o + PX * q, w + PX * q);
     }
   }
 }
@@ -188,8 +176,8 @@ static int track_project_launch(const float* points, int points_planar, const in
   const double pts = (double)T1 * B * a.HW;
   bytes_add(DVD_BYTES_GEOMETRY, pts * (12.0 + 8.0 + (z ? 4.0 : 0.0) + (inside ? 1.0 : 0.0) + (depth_all ? 4.0 : 0.0)) +
                                     (depth_all ? 4.0 * (double)(N < T1 + B ? N : T1 + B) * a.HW : 0.0));
-  const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(uv) && track_aligned16(z) &&
-                  track_aligned16(a.depth_at) && track_aligned16(inside);
+  const bool v4 = (W % 4 == 0) && aligned_to(points, 16) && aligned_to(uv, 16) && aligned_to(z, 16) &&
+                  aligned_to(a.depth_at, 16) && aligned_to(inside, 16);
   const int px = v4 ? 4 : 1;
   dim3 grid((a.HW + 256 * px - 1) / (256 * px), B, T1), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -234,7 +222,7 @@ int dvd_project_bwd(const float* g_uv, const float* points, int points_planar, c
   a.points = points, a.start = start, a.R = R, a.t = t, a.K = K_T, a.g_uv = g_uv, a.g_points = g_points;
   a.B = B, a.N = N, a.HW = H * W, a.accumulate = accumulate;
   bytes_add(DVD_BYTES_GEOMETRY, (double)T1 * B * a.HW * (accumulate ? 44.0 : 32.0));
-  const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(g_uv) && track_aligned16(g_points);
+  const bool v4 = (W % 4 == 0) && aligned_to(points, 16) && aligned_to(g_uv, 16) && aligned_to(g_points, 16);
   const int px = v4 ? 4 : 1;
   dim3 grid((a.HW + 256 * px - 1) / (256 * px), B, T1), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream);

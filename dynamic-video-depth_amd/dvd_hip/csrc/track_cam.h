@@ -7,7 +7,7 @@
 // -ffp-contract=off, so the same point and the same table row give the same bits in either of them.
 #pragma once
 
-#include "dvd_common.h"
+#include "dvd_post.h"
 
 namespace dvd {
 
@@ -35,18 +35,22 @@ __device__ __forceinline__ void project_point(const TrackCam& c, float P0, float
   rowvec_mat3(Q0, Q1, Q2, c.K, I0, I1, I2);
 }
 
+// ... and its perspective divide: (u, v) = I.xy / (I.z + 1e-8), z = I.z (the compiler's IEEE division; z is not bounded away
+// from 0 here).  Every unit that needs a pixel position takes it from here.
+__device__ __forceinline__ void project_uvz(const TrackCam& c, float P0, float P1, float P2, float& u, float& v, float& z) {
+  float I0, I1;
+  project_point(c, P0, P1, P2, I0, I1, z);
+  const float den = z + 1e-8f;
+  u = I0 / den, v = I1 / den;
+}
+
 // PX horizontally adjacent points of image `img`, from pixel p0 on: planar [.,3,H,W] or interleaved [.,H,W,3]
 template <int PX, bool PLANAR>
 __device__ __forceinline__ void load_points(const float* __restrict__ base, size_t img, int p0, int HW, float P[3][PX]) {
   if (PLANAR) {
     const float* s = base + img * 3 * HW + p0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (PX == 4)
-        *reinterpret_cast<float4*>(P[c]) = *reinterpret_cast<const float4*>(s + (size_t)c * HW);
-      else
-        P[c][0] = s[(size_t)c * HW];
-    }
+    for (int c = 0; c < 3; ++c) ldpx<PX>(s + (size_t)c * HW, P[c]);
   } else {
     const float* s = base + (img * HW + p0) * 3;
     float v[3 * PX];

@@ -68,10 +68,7 @@ __global__ __launch_bounds__(256) void track_filter_kernel(const FilterArgs a) {
   }
   if (live) {
     const float* ds = a.depth_all + (size_t)s * a.HW + p0;
-    if (PX == 4)
-      *reinterpret_cast<float4*>(d0) = *reinterpret_cast<const float4*>(ds);
-    else
-      d0[0] = ds[0];
+    ldpx<PX>(ds, d0);
     const int y = p0 / a.view.W, x = p0 - y * a.view.W;
     const float yf = (float)y;
     for (int k = 0; k < a.T1; ++k) {
@@ -118,41 +115,16 @@ __global__ __launch_bounds__(256) void track_filter_kernel(const FilterArgs a) {
   for (int i = 0; i < PX; ++i) {
     float ratio = 1.0f;
     if (live && d0[i] > 0.0f) {
-      if (MEDIAN) {
-        // the elements of rank (n - 1) / 2 and n / 2 of the column; equal values are ordered by their position
-        const float* q = smp + col + i;
-        const int m_lo = (n[i] - 1) >> 1, m_hi = n[i] >> 1;
-        float e_lo = 1.0f, e_hi = 1.0f;
-        for (int j = 0; j < n[i]; ++j) {
-          const float e = q[j * kFilterBlockPixels];
-          int rank = 0;
-          for (int l = 0; l < n[i]; ++l) {
-            const float f = q[l * kFilterBlockPixels];
-            rank += (f < e || (f == e && l < j)) ? 1 : 0;
-          }
-          e_lo = rank == m_lo ? e : e_lo;
-          e_hi = rank == m_hi ? e : e_hi;
-        }
-        ratio = (n[i] & 1) ? e_lo : (e_lo + e_hi) * 0.5f;
-      } else {
-        ratio = acc[i] / ws[i];
-      }
+      ratio = MEDIAN ? column_median(smp + col + i, kFilterBlockPixels, n[i], 1.0f) : acc[i] / ws[i];
       dep[i] = d0[i] * ratio, rat[i] = ratio, spr[i] = hi[i] - lo[i], cnt[i] = (unsigned int)n[i];
     } else {
       dep[i] = d0[i], rat[i] = 1.0f, spr[i] = 0.0f, cnt[i] = 0u;
     }
   }
-  if (PX == 4) {
-    *reinterpret_cast<float4*>(a.depth_out + pix) = make_float4(dep[0], dep[1], dep[2], dep[3]);
-    if (a.ratio) *reinterpret_cast<float4*>(a.ratio + pix) = make_float4(rat[0], rat[1], rat[2], rat[3]);
-    if (a.spread) *reinterpret_cast<float4*>(a.spread + pix) = make_float4(spr[0], spr[1], spr[2], spr[3]);
-    if (a.count) *reinterpret_cast<unsigned int*>(a.count + pix) = cnt[0] | (cnt[1] << 8) | (cnt[2] << 16) | (cnt[3] << 24);
-  } else {
-    a.depth_out[pix] = dep[0];
-    if (a.ratio) a.ratio[pix] = rat[0];
-    if (a.spread) a.spread[pix] = spr[0];
-    if (a.count) a.count[pix] = (unsigned char)cnt[0];
-  }
+  stpx<PX>(a.depth_out + pix, dep);
+  if (a.ratio) stpx<PX>(a.ratio + pix, rat);
+  if (a.spread) stpx<PX>(a.spread + pix, spr);
+  if (a.count) stpx_bytes<PX>(a.count + pix, cnt);
 }
 
 template <int PX, bool PLANAR>
@@ -193,8 +165,8 @@ int dvd_track_filter(const float* points, int points_planar, const int* start, c
   const double px = (double)B * a.HW;
   bytes_add(DVD_BYTES_GEOMETRY, px * (12.0 * (T1 - 1) + 4.0 + 4.0 + (ratio ? 4.0 : 0.0) + (count ? 1.0 : 0.0) + (spread ? 4.0 : 0.0)) +
                                     4.0 * (double)(N < T1 + B ? N : T1 + B) * a.HW);
-  const bool v4 = (W % 4 == 0) && track_aligned16(points) && track_aligned16(depth_all) && track_aligned16(depth_out) &&
-                  track_aligned16(ratio) && track_aligned16(count) && track_aligned16(spread);
+  const bool v4 = (W % 4 == 0) && aligned_to(points, 16) && aligned_to(depth_all, 16) && aligned_to(depth_out, 16) &&
+                  aligned_to(ratio, 16) && aligned_to(count, 16) && aligned_to(spread, 16);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (v4 && points_planar)
     track_filter_launch<4, true>(a, mode, s);

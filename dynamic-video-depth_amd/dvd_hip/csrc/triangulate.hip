@@ -29,11 +29,11 @@
 // float2 and 64 of mask per observation and writes 256 contiguous bytes per fp32 output.  The median's up to 32 samples per pixel
 // would be a run-time indexed private array, i.e. scratch memory; they live in LDS instead, [M][256] floats per block (32 KiB at
 // the cap), each pixel's column touched by its own thread only -- no barrier -- and the middle elements are picked by rank
-// counting as in track_filter.hip.  No atomics, one writer per output element: the same inputs give the same bits.
+// counting (column_median, dvd_post.h).  No atomics, one writer per output element: the same inputs give the same bits.
 
 #include <float.h>
 
-#include "dvd_common.h"
+#include "dvd_post.h"
 
 namespace dvd {
 
@@ -140,25 +140,7 @@ __global__ __launch_bounds__(kTriBlock) void triangulate_kernel(const TriArgs a)
   }
   float dep = 0.0f, spr = 0.0f;
   if (n >= a.min_count && n > 0) {
-    if (MEDIAN) {
-      // the elements of rank (n - 1) / 2 and n / 2 of the column; equal values are ordered by their position
-      const float* q = smp + col;
-      const int m_lo = (n - 1) >> 1, m_hi = n >> 1;
-      float e_lo = 0.0f, e_hi = 0.0f;
-      for (int j = 0; j < n; ++j) {
-        const float e = q[j * kTriBlock];
-        int rank = 0;
-        for (int l = 0; l < n; ++l) {
-          const float f = q[l * kTriBlock];
-          rank += (f < e || (f == e && l < j)) ? 1 : 0;
-        }
-        e_lo = rank == m_lo ? e : e_lo;
-        e_hi = rank == m_hi ? e : e_hi;
-      }
-      dep = (n & 1) ? e_lo : (e_lo + e_hi) * 0.5f;
-    } else {
-      dep = acc / ws;
-    }
+    dep = MEDIAN ? column_median(smp + col, kTriBlock, n, 0.0f) : acc / ws;
     if (dep != 0.0f) {
       spr = (hi - lo) / dep;
       spr = spr <= kTriCap ? spr : kTriCap;

@@ -9,6 +9,7 @@ import ctypes
 import os
 import sys
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -30,6 +31,135 @@ def _dev32(t, name):
     if t.dtype != torch.float32:
         raise RuntimeError('%s must be float32, got %s' % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
+
+
+# -- the checks the post-processing wrappers share: one copy each.  They run on the host and read nothing back -------------
+def _dev_u8(what, name, t, shape, dev, copy=True):
+    """None, or a GPU uint8 tensor of `shape` on `dev`; one that is not contiguous is copied, or refused where not `copy`."""
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.uint8 and tuple(t.shape) == tuple(shape)
+            and (copy or t.is_contiguous())):
+        raise RuntimeError('%s: %s must be a %sGPU uint8 tensor %s on the device of the data' % (
+            what, name, '' if copy else 'contiguous ', list(shape)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _out_ok(what, name, t, shape, dtype, dev, on):
+    """A tensor the kernel writes (or reads in place): it must be exactly this already, nothing is converted or copied."""
+    if not (torch.is_tensor(t) and t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise RuntimeError('%s: %s must be a contiguous %s tensor %s on the device of %s' % (what, name, dtype, list(shape), on))
+    return t
+
+
+def _outputs(what, out, shapes, dev, on):
+    """{name: (shape, dtype)} -> {name: tensor}: out[name] where the caller preallocated it, a new tensor otherwise."""
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        o = out.get(k) if out is not None else None
+        res[k] = torch.empty(shape, device=dev, dtype=dtype) if o is None else _out_ok(what, 'out[%r]' % k, o, shape, dtype, dev, on)
+    return res
+
+
+def _int_arg(what, name, v, lo, hi, floats=True):
+    """v as an int in lo .. hi: anything but a bool whose int(v) equals it (an integral float only where `floats` allows it)."""
+    ok = type(v) is int
+    if not ok:                                                        # (a plain int skips all this)
+        try:
+            ok = not isinstance(v, (bool, np.bool_)) and (floats or not isinstance(v, (float, np.floating))) and bool(int(v) == v)
+        except (TypeError, ValueError, OverflowError):                # not a number; a NaN; an Inf
+            ok = False
+    if not (ok and lo <= v <= hi):
+        raise RuntimeError('%s: %s must be an integer in %d .. %d, got %r' % (what, name, lo, hi, v))
+    return int(v)
+
+
+_FLT_MAX = 3.4028234663852886e+38
+
+
+def _real_arg(what, name, v, lo=0.0, lo_open=False, hi=None):
+    """v as a float: a number (no bool) that is finite -- as float32 too, which is what the kernel receives -- and lies in
+    [lo, hi], (lo, hi] where lo_open; hi None: no upper end."""
+    ok = type(v) is float
+    if not ok:                                                        # (a plain float skips all this)
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+    if not (ok and -_FLT_MAX <= v <= _FLT_MAX and (v > lo if lo_open else v >= lo) and (hi is None or v <= hi)):   # (no NaN passes)
+        raise RuntimeError('%s: %s must be a finite number %s, got %r' % (
+            what, name, ('> %g' if lo_open else '>= %g') % lo if hi is None else 'in %s%g, %g]' % ('(' if lo_open else '[', lo, hi), v))
+    return float(v)
+
+
+def _ids_in(what, name, host, lo, hi):
+    if host.size and (int(host.min()) < lo or int(host.max()) >= hi):
+        raise RuntimeError('%s: the ids of %s span [%d, %d], outside %d .. %d' % (what, name, int(host.min()), int(host.max()), lo, hi - 1))
+
+
+def _host_ids(what, name, ids, shape, lo=None, hi=None, floats=True):
+    """A host sequence / array / CPU tensor of ids -> an integer numpy array of exactly `shape` (None: any extent), every id in
+    lo .. hi - 1 (no range check without lo).  An array of integral floats is taken where `floats` allows it."""
+    try:
+        host = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids)
+    except (TypeError, ValueError):
+        raise RuntimeError('%s: %s must be a host array of integers' % (what, name))
+    if floats and host.dtype.kind == 'f' and host.size and np.all(np.isfinite(host)) and np.all(host == np.floor(host)):
+        host = host.astype(np.int64)
+    if host.dtype.kind not in 'iu' or (host.shape != tuple(shape) and (host.ndim != len(shape) or any(
+            s is not None and s != h for s, h in zip(shape, host.shape)))):
+        raise RuntimeError('%s: %s must hold [%s] integral ids, got %s %s' % (
+            what, name, ', '.join('any' if s is None else str(s) for s in shape), host.dtype, host.shape))
+    if lo is not None:
+        _ids_in(what, name, host, lo, hi)
+    return host
+
+
+def _ids(what, name, ids, shape, lo, hi, dev, on, host=None, read_back=False, floats=True, non_blocking=True):
+    """Ids for a kernel -> (contiguous int32 tensor on dev, their checked host copy or None).  `ids` is a host sequence / array
+    / CPU tensor (checked by _host_ids, uploaded here) or a GPU int32 tensor; the latter is range-checked from `host`, its host
+    copy, where the caller has one, is read back where read_back asks for it, and is otherwise taken as it is."""
+    if torch.is_tensor(ids) and ids.is_cuda:
+        if ids.dtype != torch.int32 or tuple(ids.shape) != tuple(shape) or not ids.is_contiguous() or ids.device != dev:
+            raise RuntimeError('%s: %s must be a contiguous GPU int32 tensor %s of ids on the device of %s' % (what, name, list(shape), on))
+        if host is None and read_back:
+            host = ids.cpu()
+        return ids, (None if host is None else _host_ids(what, name, host, shape, lo, hi, floats))
+    host = _host_ids(what, name, ids, shape, lo, hi, floats)
+    return torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev, non_blocking=non_blocking), host
+
+
+def _tables(what, tables, keys, per, dev, on, n=None):
+    """The per-frame camera tables `keys` of a dict -> (the tensors, their number of rows n).  Each is float32 on dev and holds
+    per[i] values for each of n rows; n None: as many as the first table has."""
+    tabs = []
+    for k in keys:
+        if k not in tables:
+            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(keys)))
+        tab = _dev32(tables[k], 'table ' + k)
+        if tab.device != dev:
+            raise RuntimeError('%s: table %s and %s are on different devices' % (what, k, on))
+        tabs.append(tab)
+    if n is None:
+        n = int(tabs[0].shape[0]) if tabs[0].dim() > 0 else 0
+    for k, tab, p in zip(keys, tabs, per):
+        if n <= 0 or tab.dim() < 2 or tab.shape[0] != n or tab.numel() != n * p:
+            raise RuntimeError('%s: table %s must hold %d values for each of %d rows, got %s' % (what, k, p, n, tuple(tab.shape)))
+    return tabs, n
+
+
+def _depth_all(what, depth_all, N, H, W, dev):
+    depth_all = _dev32(depth_all, 'depth_all')
+    if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
+        raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
+            what, N, H, W, tuple(depth_all.shape)))
+    return depth_all
+
+
+def _point_slab(what, p):
+    """p [B,3,H,W]: the contiguous float32 GPU points of the inverse step."""
+    if not (torch.is_tensor(p) and p.is_cuda):
+        raise RuntimeError('p must be a GPU tensor (dvd_hip has no CPU path)')
+    if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 3 or p.numel() == 0 or not p.is_contiguous():
+        raise RuntimeError('%s: p must be a contiguous float32 tensor [B,3,H,W], got %s %s' % (what, p.dtype, tuple(p.shape)))
+    return p
 
 
 def pack_cameras(cams):
@@ -56,9 +186,8 @@ def unproject(depth, R, t, K_inv, planar=True, out=None):
     shape = (B, 3, H, W) if planar else (B, H, W, 1, 3)
     if out is None:
         out = torch.empty(shape, device=depth.device, dtype=torch.float32)
-    elif not (torch.is_tensor(out) and out.device == depth.device and out.dtype == torch.float32 and tuple(out.shape) == shape
-              and out.is_contiguous()):
-        raise RuntimeError('unproject: out must be a contiguous float32 tensor %s on the device of the depth' % (shape,))
+    else:
+        _out_ok('unproject', 'out', out, shape, torch.float32, depth.device, 'the depth')
     lib = _lib.load()
     _lib.check(lib.dvd_unproject_fwd(_p(depth), _p(R), _p(t), _p(K_inv), _p(out), int(planar), B, H, W, _stream()),
                'dvd_unproject_fwd')
@@ -90,7 +219,6 @@ TRACK_TABLES = ('R', 't', 'K_T')
 def _track_args(what, points, start, tables, planar, host_start):
     """Everything track_project and project_backward check before a launch -> (points, start on the device, the three tables,
     T1, B, H, W, N).  Runs on the host; a CPU tensor is refused before any shape is looked at."""
-    import numpy as np
     points = _dev32(points, 'points')
     if points.dim() != 5 or points.shape[2 if planar else 4] != 3 or points.numel() == 0:
         raise RuntimeError('%s: points must be [T1,B,3,H,W] (planar) or [T1,B,H,W,3], got %s' % (what, tuple(points.shape)))
@@ -100,33 +228,10 @@ def _track_args(what, points, start, tables, planar, host_start):
         raise RuntimeError('%s: images of %d x %d; the sampling rule needs H, W >= 2' % (what, H, W))
     if T1 > 65535 or B > 65535:
         raise RuntimeError('%s: at most 65535 steps and 65535 images per launch, got %d and %d' % (what, T1, B))
-    tabs = []
-    for k in TRACK_TABLES:
-        if k not in tables:
-            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRACK_TABLES)))
-        tab = _dev32(tables[k], 'table ' + k)
-        if tab.device != points.device:
-            raise RuntimeError('%s: table %s and the points are on different devices' % (what, k))
-        tabs.append(tab)
-    N = int(tabs[0].shape[0]) if tabs[0].dim() > 0 else 0
-    for k, tab, per in zip(TRACK_TABLES, tabs, (9, 3, 9)):
-        if N <= 0 or tab.dim() < 2 or tab.shape[0] != N or tab.numel() != N * per:
-            raise RuntimeError('%s: table %s must hold %d values for each of %d frames, got %s' % (what, k, per, N, tuple(tab.shape)))
-    if torch.is_tensor(start) and start.is_cuda:
-        if start.dtype != torch.int32 or start.dim() != 1 or not start.is_contiguous() or start.device != points.device:
-            raise RuntimeError('%s: start must be a contiguous GPU int32 tensor of %d frame ids on the device of the points' % (what, B))
-        host = np.asarray(start.cpu() if host_start is None else host_start)
-    else:
-        host = np.asarray(start.cpu() if torch.is_tensor(start) else start)
-        start = None
-    if host.dtype.kind == 'f' and host.size and np.all(np.isfinite(host)) and np.all(host == np.floor(host)):
-        host = host.astype(np.int64)
-    if host.dtype.kind not in 'iu' or host.shape != (B,):
-        raise RuntimeError('%s: start must hold %d integral frame ids, got %s %s' % (what, B, host.dtype, host.shape))
-    if int(host.min()) < 0 or int(host.max()) >= N:
-        raise RuntimeError('%s: start spans [%d, %d], outside the %d frames of the tables' % (what, int(host.min()), int(host.max()), N))
-    if start is None:
-        start = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(points.device)
+    tabs, N = _tables(what, tables, TRACK_TABLES, (9, 3, 9), points.device, 'the points')
+    # (a device tensor without its host copy is read back: the range check needs the ids)
+    start, _ = _ids(what, 'start', start, (B,), 0, N, points.device, 'the points', host=host_start, read_back=True,
+                    non_blocking=False)
     return points, start, tabs, T1, B, H, W, N
 
 
@@ -144,16 +249,10 @@ def track_project(points, start, tables, depth_all=None, out=None, planar=True, 
                row n_back is the start frame); frames before the video give zeros like frames past its end
     Frames past the end of the tables give zeros.  Everything is checked on the host before the launch."""
     what = 'track_project'
-    if isinstance(k0, bool) or int(k0) != k0 or abs(int(k0)) >= 1 << 30:
-        raise RuntimeError('%s: k0 must be an integer row offset, got %r' % (what, k0))
-    k0 = int(k0)
+    k0 = _int_arg(what, 'k0', k0, 1 - (1 << 30), (1 << 30) - 1)
     points, start, (R, t, K_T), T1, B, H, W, N = _track_args(what, points, start, tables, planar, host_start)
-    dev = points.device
     if depth_all is not None:
-        depth_all = _dev32(depth_all, 'depth_all')
-        if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
-            raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
-                what, N, H, W, tuple(depth_all.shape)))
+        depth_all = _depth_all(what, depth_all, N, H, W, points.device)
     shapes = {'uv': ((T1, B, H, W, 2), torch.float32)}
     if 'z' in want:
         shapes['z'] = ((T1, B, H, W), torch.float32)
@@ -161,14 +260,7 @@ def track_project(points, start, tables, depth_all=None, out=None, planar=True, 
         shapes['inside'] = ((T1, B, H, W), torch.uint8)
     if depth_all is not None:
         shapes['depth_at'] = ((T1, B, H, W), torch.float32)
-    res = {}
-    for k, (shape, dtype) in shapes.items():
-        o = out.get(k) if out is not None else None
-        if o is None:
-            o = torch.empty(shape, device=dev, dtype=dtype)
-        elif not (torch.is_tensor(o) and o.device == dev and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
-            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the points' % (what, k, dtype, shape))
-        res[k] = o
+    res = _outputs(what, out, shapes, points.device, 'the points')
     args = (_p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N, _p(res['uv']),
             int(bool(displacement)), _p(res.get('z')), _p(res.get('depth_at')), _p(res.get('inside')), T1, B, H, W)
     if k0 != 0:
@@ -194,17 +286,12 @@ def track_filter(points, start, tables, depth_all, weights, k0=0, mode='mean', t
       out      optional dict of preallocated outputs
     depth = depth_all[start] * ratio; a pixel whose own depth is not > 0 keeps it (ratio 1, count 0, spread 0).  Everything
     is checked on the host before the launch."""
-    import math
     import numpy as np
     what = 'track_filter'
-    if isinstance(k0, bool) or int(k0) != k0 or abs(int(k0)) >= 1 << 30:
-        raise RuntimeError('%s: k0 must be an integer row offset, got %r' % (what, k0))
-    k0 = int(k0)
+    k0 = _int_arg(what, 'k0', k0, 1 - (1 << 30), (1 << 30) - 1)
     if mode not in FILTER_MODES:
         raise RuntimeError('%s: mode must be one of %s, got %r' % (what, ', '.join(sorted(FILTER_MODES)), mode))
-    for name, v in (('tol', tol), ('z_near', z_near)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
-            raise RuntimeError('%s: %s must be a finite number >= 0, got %r' % (what, name, v))
+    tol, z_near = _real_arg(what, 'tol', tol), _real_arg(what, 'z_near', z_near)
     if any(k not in ('ratio', 'count', 'spread') for k in want):
         raise RuntimeError("%s: want may name 'ratio', 'count' and 'spread', got %r" % (what, tuple(want)))
     # the weights first: they are host data, so a bad list is refused before a tensor is looked at
@@ -229,26 +316,16 @@ def track_filter(points, start, tables, depth_all, weights, k0=0, mode='mean', t
         raise RuntimeError('%s: %d weights for a slab of %d rows (at most %d)' % (what, w.size, T1, FILTER_MAX_ROWS))
     if depth_all is None:
         raise RuntimeError('%s: depth_all is required' % what)
-    depth_all = _dev32(depth_all, 'depth_all')
-    if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
-        raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
-            what, N, H, W, tuple(depth_all.shape)))
+    depth_all = _depth_all(what, depth_all, N, H, W, dev)
     wdev = torch.from_numpy(w).to(dev)
     shapes = {'depth': ((B, 1, H, W), torch.float32)}
     for k in ('ratio', 'count', 'spread'):
         if k in want:
             shapes[k] = ((B, H, W), torch.uint8) if k == 'count' else ((B, 1, H, W), torch.float32)
-    res = {}
-    for k, (shape, dtype) in shapes.items():
-        o = out.get(k) if out is not None else None
-        if o is None:
-            o = torch.empty(shape, device=dev, dtype=dtype)
-        elif not (torch.is_tensor(o) and o.device == dev and o.dtype == dtype and tuple(o.shape) == shape and o.is_contiguous()):
-            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the points' % (what, k, dtype, shape))
-        res[k] = o
+    res = _outputs(what, out, shapes, dev, 'the points')
     _lib.check(_lib.load().dvd_track_filter(
         _p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), _p(depth_all), N, _p(wdev), FILTER_MODES[mode],
-        float(tol), float(z_near), _p(res['depth']), _p(res.get('ratio')), _p(res.get('count')), _p(res.get('spread')),
+        tol, z_near, _p(res['depth']), _p(res.get('ratio')), _p(res.get('count')), _p(res.get('spread')),
         T1, B, H, W, k0, _stream()), 'dvd_track_filter')
     return res
 
@@ -274,62 +351,42 @@ def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='m
       out      optional dict of preallocated outputs
     include/dvd_hip.h has the formulae and the gates.  Everything is checked on the host before the launch, and nothing
     synchronises with the device."""
-    import math
     import numpy as np
     what = 'triangulate'
     if mode not in FILTER_MODES:
         raise RuntimeError('%s: mode must be one of %s, got %r' % (what, ', '.join(sorted(FILTER_MODES)), mode))
-    for name, v, lo_open, hi in (('epi_tol', epi_tol, False, None), ('sin2_min', sin2_min, True, 1.0), ('z_near', z_near, False, None)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0 or \
-                (lo_open and not v > 0) or (hi is not None and v > hi) or not math.isfinite(np.float32(v)):
-            raise RuntimeError('%s: %s must be a finite number %s, got %r' % (what, name, 'in (0, 1]' if lo_open else '>= 0', v))
-    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= min_count <= 255:
-        raise RuntimeError('%s: min_count must be an integer in 1 .. 255, got %r' % (what, min_count))
+    epi_tol, z_near = _real_arg(what, 'epi_tol', epi_tol), _real_arg(what, 'z_near', z_near)
+    sin2_min = _real_arg(what, 'sin2_min', sin2_min, lo_open=True, hi=1.0)
+    min_count = _int_arg(what, 'min_count', min_count, 1, 255, floats=False)
     # the host data first: a bad table is refused before a tensor is looked at
+    fr = _host_ids(what, 'frames', frames, (None,), floats=False)
+    B = int(fr.size)
+    if not 1 <= B <= 65535:
+        raise RuntimeError('%s: frames must hold 1 .. 65535 frame ids per launch, got %d' % (what, B))
     try:
         o = np.asarray(obs.cpu() if torch.is_tensor(obs) else obs)
-        fr = np.asarray(frames.cpu() if torch.is_tensor(frames) else frames)
     except (TypeError, ValueError):
-        raise RuntimeError('%s: obs and frames must be host arrays of integers' % what)
-    if fr.dtype.kind not in 'iu' or fr.ndim != 1 or fr.size == 0:
-        raise RuntimeError('%s: frames must hold at least one integral frame id, got %s %s' % (what, fr.dtype, fr.shape))
-    B = int(fr.size)
-    if B > 65535:
-        raise RuntimeError('%s: at most 65535 frames per launch, got %d' % (what, B))
-    if o.size == 0 and o.ndim <= 3:
+        raise RuntimeError('%s: obs must be a host array of integers' % what)
+    if o.size == 0 and o.ndim <= 3:                                   # (no observations, in whatever empty form)
         o = np.zeros((B, 0, 3), np.int32)
-    if o.dtype.kind not in 'iu' or o.ndim != 3 or o.shape[0] != B or o.shape[2] != 3:
-        raise RuntimeError('%s: obs must be integral [%d,M,3] rows (pair, frame, dir), got %s %s' % (what, B, o.dtype, o.shape))
+    o = _host_ids(what, 'obs (rows of pair, frame, dir)', o, (B, None, 3), floats=False)
     M = int(o.shape[1])
     if M > TRI_MAX_OBS:
         raise RuntimeError('%s: obs holds M=%d observations per frame, at most %d' % (what, M, TRI_MAX_OBS))
     f12 = _dev32(flow_1_2, 'flow_1_2')
     dev = f12.device
-    if f12.dim() != 4 or f12.shape[3] != 2 or f12.shape[1] < 1 or f12.shape[2] < 1:
-        raise RuntimeError('%s: flow_1_2 must be [P,H,W,2], got %s' % (what, tuple(f12.shape)))
+    if f12 is not flow_1_2 or f12.dim() != 4 or f12.shape[3] != 2 or f12.shape[1] < 1 or f12.shape[2] < 1:
+        raise RuntimeError('%s: flow_1_2 must be contiguous [P,H,W,2], got %s' % (what, tuple(f12.shape)))
     P, H, W = (int(v) for v in f12.shape[:3])
     if H * W >= 1 << 30:
         raise RuntimeError('%s: images of %d x %d: H * W must stay below 2^30' % (what, H, W))
-    if not (torch.is_tensor(flow_2_1) and flow_2_1.is_cuda and flow_2_1.device == dev and flow_2_1.dtype == torch.float32 and
-            flow_2_1.shape == f12.shape and flow_2_1.is_contiguous() and flow_1_2.is_contiguous()):
-        raise RuntimeError('%s: flow_1_2 and flow_2_1 must be contiguous float32 GPU tensors %s on one device' % (what, tuple(f12.shape)))
-    for name, m in (('mask_1', mask_1), ('mask_2', mask_2)):
-        if not (torch.is_tensor(m) and m.device == dev and m.dtype == torch.uint8 and tuple(m.shape) == (P, H, W) and m.is_contiguous()):
-            raise RuntimeError('%s: %s must be a contiguous uint8 tensor %s on the device of the flows' % (what, name, (P, H, W)))
-    tabs = []
-    for k in TRI_TABLES:
-        if k not in tables:
-            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRI_TABLES)))
-        tab = _dev32(tables[k], 'table ' + k)
-        if tab.device != dev:
-            raise RuntimeError('%s: table %s and the flows are on different devices' % (what, k))
-        tabs.append(tab)
-    N = int(tabs[0].shape[0]) if tabs[0].dim() > 0 else 0
-    for k, tab, per in zip(TRI_TABLES, tabs, (9, 3, 9, 9)):
-        if N <= 0 or tab.dim() < 2 or tab.shape[0] != N or tab.numel() != N * per:
-            raise RuntimeError('%s: table %s must hold %d values for each of %d frames, got %s' % (what, k, per, N, tuple(tab.shape)))
-    if int(fr.min()) < 0 or int(fr.max()) >= N:
-        raise RuntimeError('%s: frames span [%d, %d], outside the %d frames of the tables' % (what, int(fr.min()), int(fr.max()), N))
+    _out_ok(what, 'flow_2_1', flow_2_1, f12.shape, torch.float32, dev, 'flow_1_2')
+    if mask_1 is None or mask_2 is None:
+        raise RuntimeError('%s: mask_1 and mask_2 are required, got None for %s' % (what, 'mask_1' if mask_1 is None else 'mask_2'))
+    mask_1 = _dev_u8(what, 'mask_1', mask_1, (P, H, W), dev, copy=False)
+    mask_2 = _dev_u8(what, 'mask_2', mask_2, (P, H, W), dev, copy=False)
+    tabs, N = _tables(what, tables, TRI_TABLES, (9, 3, 9, 9), dev, 'the flows')
+    _ids_in(what, 'frames', fr, 0, N)
     live = o[..., 0] >= 0
     if M:
         if int(o[..., 0].min()) < -1 or int(o[..., 0].max()) >= P:
@@ -340,15 +397,7 @@ def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='m
                 what, int(o[..., 1][live].min()), int(o[..., 1][live].max()), N))
         if live.any() and not np.isin(o[..., 2][live], (0, 1)).all():
             raise RuntimeError('%s: the dir column of obs must be 0 (flow_1_2) or 1 (flow_2_1)' % what)
-    res = {}
-    for k, dtype, chan in TRI_OUT:
-        shape = (B, 1, H, W) if chan else (B, H, W)
-        t_ = out.get(k) if out is not None else None
-        if t_ is None:
-            t_ = torch.empty(shape, device=dev, dtype=dtype)
-        elif not (torch.is_tensor(t_) and t_.device == dev and t_.dtype == dtype and tuple(t_.shape) == shape and t_.is_contiguous()):
-            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the flows' % (what, k, dtype, shape))
-        res[k] = t_
+    res = _outputs(what, out, {k: ((B, 1, H, W) if chan else (B, H, W), dtype) for k, dtype, chan in TRI_OUT}, dev, 'the flows')
     # the frame ids and the table in ONE upload from pinned memory, enqueued on the current stream: a copy from pageable memory
     # would make the host wait for the stream
     host = torch.from_numpy(np.concatenate([fr.astype(np.int32), o.astype(np.int32).ravel()])).pin_memory()
@@ -356,23 +405,10 @@ def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='m
     fr_dev, obs_dev = both[:B], (both[B:] if M else None)
     _lib.check(_lib.load().dvd_triangulate(
         _p(f12), _p(flow_2_1), _p(mask_1), _p(mask_2), P, _p(obs_dev), _p(fr_dev), int(live.sum()), _p(tabs[0]), _p(tabs[1]),
-        _p(tabs[2]), _p(tabs[3]), N, FILTER_MODES[mode], float(epi_tol), float(sin2_min), float(z_near), int(min_count),
+        _p(tabs[2]), _p(tabs[3]), N, FILTER_MODES[mode], epi_tol, sin2_min, z_near, min_count,
         _p(res['depth']), _p(res['count']), _p(res['usable']), _p(res['epi']), _p(res['spread']), M, B, H, W, _stream()),
         'dvd_triangulate')
     return res
-
-
-def _like(what, name, t, ref):
-    if not (torch.is_tensor(t) and t.is_cuda and t.device == ref.device and t.dtype == torch.float32 and t.shape == ref.shape
-            and t.is_contiguous()):
-        raise RuntimeError('%s: %s must be a contiguous float32 GPU tensor %s on the device of p' % (what, name, tuple(ref.shape)))
-    return t
-
-
-def _resid_ok(what, resid, B, dev):
-    if resid is not None and not (torch.is_tensor(resid) and resid.device == dev and resid.dtype == torch.float32 and
-                                  tuple(resid.shape) == (B,) and resid.is_contiguous()):
-        raise RuntimeError('%s: resid must be a contiguous float32 tensor [%d] on the device of p' % (what, B))
 
 
 def invert_update(p, sf, y_old, out=None, resid=None):
@@ -382,20 +418,18 @@ def invert_update(p, sf, y_old, out=None, resid=None):
       out      optional destination [B,3,H,W] (it may be y_old; not p or sf);  resid: optional fp32 [B]
     Everything is checked on the host before the launch."""
     what = 'invert_update'
-    if not (torch.is_tensor(p) and p.is_cuda):
-        raise RuntimeError('p must be a GPU tensor (dvd_hip has no CPU path)')
-    if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 3 or p.numel() == 0 or not p.is_contiguous():
-        raise RuntimeError('%s: p must be a contiguous float32 tensor [B,3,H,W], got %s %s' % (what, p.dtype, tuple(p.shape)))
+    p = _point_slab(what, p)
     B, _, H, W = (int(v) for v in p.shape)
     if B > 65535 or H * W >= 1 << 30:
         raise RuntimeError('%s: at most 65535 images of fewer than 2^30 pixels per launch, got %d of %d x %d' % (what, B, H, W))
-    sf, y_old = _like(what, 'sf', sf, p), _like(what, 'y_old', y_old, p)
     if out is None:
         out = torch.empty_like(p)
-    _like(what, 'out', out, p)
+    for name, v in (('sf', sf), ('y_old', y_old), ('out', out)):
+        _out_ok(what, name, v, p.shape, torch.float32, p.device, 'p')
     if out.data_ptr() in (p.data_ptr(), sf.data_ptr()) and out.data_ptr() != y_old.data_ptr():
         raise RuntimeError('%s: out may alias y_old only' % what)
-    _resid_ok(what, resid, B, p.device)
+    if resid is not None:
+        _out_ok(what, 'resid', resid, (B,), torch.float32, p.device, 'p')
     _lib.check(_lib.load().dvd_track_invert_update(_p(p), _p(sf), _p(y_old), _p(out), _p(resid), B, H * W, _stream()),
                'dvd_track_invert_update')
     return out
@@ -414,19 +448,17 @@ def invert_step(mlp, p, t, t_offset, out_scale, n_iter=4, out=None, resid=None, 
     what = 'invert_step'
     if isinstance(n_iter, bool) or int(n_iter) != n_iter or n_iter < 1:
         raise ValueError('%s: n_iter must be an integer >= 1, got %r' % (what, n_iter))
-    if not (torch.is_tensor(p) and p.is_cuda):
-        raise RuntimeError('p must be a GPU tensor (dvd_hip has no CPU path)')
-    if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 3 or p.numel() == 0 or not p.is_contiguous():
-        raise RuntimeError('%s: p must be a contiguous float32 tensor [B,3,H,W], got %s %s' % (what, p.dtype, tuple(p.shape)))
+    p = _point_slab(what, p)
     if out is None:
         out = torch.empty_like(p)
     if scratch is None:
         scratch = torch.empty_like(p)
-    _like(what, 'out', out, p)
-    _like(what, 'scratch', scratch, p)
+    for name, v in (('out', out), ('scratch', scratch)):
+        _out_ok(what, name, v, p.shape, torch.float32, p.device, 'p')
     if len({p.data_ptr(), out.data_ptr(), scratch.data_ptr()}) != 3:
         raise RuntimeError('%s: p, out and scratch must be three buffers' % what)
-    _resid_ok(what, resid, int(p.shape[0]), p.device)
+    if resid is not None:
+        _out_ok(what, 'resid', resid, (int(p.shape[0]),), torch.float32, p.device, 'p')
     y = p
     for i in range(int(n_iter)):
         last = i == int(n_iter) - 1
@@ -450,9 +482,8 @@ def project_backward(g_uv, points, start, tables, planar=True, out=None, accumul
         if accumulate:
             raise RuntimeError('accumulate=True needs an output tensor')
         out = torch.empty_like(points)
-    elif not (torch.is_tensor(out) and out.device == points.device and out.dtype == torch.float32 and
-              out.shape == points.shape and out.is_contiguous()):
-        raise RuntimeError('%s: out must be a contiguous float32 tensor shaped like points' % what)
+    else:
+        _out_ok(what, 'out', out, points.shape, torch.float32, points.device, 'the points')
     _lib.check(_lib.load().dvd_project_bwd(_p(g_uv), _p(points), int(bool(planar)), _p(start), _p(R), _p(t), _p(K_T), N, _p(out),
                                            int(bool(accumulate)), T1, B, H, W, _stream()), 'dvd_project_bwd')
     return out
@@ -493,59 +524,24 @@ def _splat_sources(what, points, values, view, tables, n_views, valid, planar, h
         raise RuntimeError('%s: values must be [%d,C,%d,%d] with 1 <= C <= %d on the device of the points, got %s' % (
             what, S, H, W, SPLAT_MAX_C, tuple(values.shape)))
     C = int(values.shape[1])
-    if valid is not None:
-        if not (torch.is_tensor(valid) and valid.is_cuda and valid.device == dev and valid.dtype == torch.uint8 and
-                tuple(valid.shape) == (S, H, W)):
-            raise RuntimeError('%s: valid must be a GPU uint8 tensor [%d,%d,%d] on the device of the points' % (what, S, H, W))
-        valid = valid if valid.is_contiguous() else valid.contiguous()
-    V = int(n_views)
-    if isinstance(n_views, bool) or V != n_views or not 1 <= V <= 65535:
-        raise RuntimeError('%s: n_views must be an integer in 1 .. 65535, got %r' % (what, n_views))
-    tabs = []
-    for k, per in zip(TRACK_TABLES, (9, 3, 9)):
-        if k not in tables:
-            raise RuntimeError('%s: tables must hold %s' % (what, ', '.join(TRACK_TABLES)))
-        tab = _dev32(tables[k], 'table ' + k)
-        if tab.device != dev:
-            raise RuntimeError('%s: table %s and the points are on different devices' % (what, k))
-        if tab.dim() < 2 or tab.shape[0] != V or tab.numel() != V * per:
-            raise RuntimeError('%s: table %s must hold %d values for each of %d views, got %s' % (what, k, per, V, tuple(tab.shape)))
-        tabs.append(tab)
-    host = None
-    if torch.is_tensor(view) and view.is_cuda:
-        if view.dtype != torch.int32 or view.dim() != 1 or view.shape[0] != S or not view.is_contiguous() or view.device != dev:
-            raise RuntimeError('%s: view must be a contiguous GPU int32 tensor of %d view ids on the device of the points' % (what, S))
-        if host_view is not None:
-            host = np.asarray(host_view)
-    else:
-        host = np.asarray(view.cpu() if torch.is_tensor(view) else view)
-        view = None
+    valid = _dev_u8(what, 'valid', valid, (S, H, W), dev)
+    V = _int_arg(what, 'n_views', n_views, 1, 65535)
+    tabs, _ = _tables(what, tables, TRACK_TABLES, (9, 3, 9), dev, 'the points', n=V)
+    # any id that fits 32 bits: one that is no view (< 0 or >= V) skips its image
+    view, host = _ids(what, 'view', view, (S,), -2 ** 31, 2 ** 31, dev, 'the points', host=host_view)
+    n_max = S * H * W
     if host is not None:
-        if host.dtype.kind == 'f' and host.size and np.all(np.isfinite(host)) and np.all(host == np.floor(host)):
-            host = host.astype(np.int64)
-        if host.dtype.kind not in 'iu' or host.shape != (S,):
-            raise RuntimeError('%s: view must hold %d integral view ids, got %s %s' % (what, S, host.dtype, host.shape))
-        if int(host.min()) < -2 ** 31 or int(host.max()) >= 2 ** 31:
-            raise RuntimeError('%s: view ids must fit 32 bits' % what)
         live = host[(host >= 0) & (host < V)]
         per_view = int(np.bincount(live.astype(np.int64), minlength=1).max()) if live.size else 0
         n_max = max(1, per_view) * H * W
-        if view is None:
-            view = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev, non_blocking=True)
-    else:
-        n_max = S * H * W
     return points, values, valid, view, tabs, S, C, H, W, V, n_max
 
 
 def _splat_params(what, **p):
     """The numeric parameters as floats, refused here with the kernels' own rules."""
-    p = {k: float(v) for k, v in p.items()}
-    ok = {'z_near': lambda v: v >= 0, 'z_tol': lambda v: v >= 0, 'w_tap': lambda v: 0 < v <= 0.25, 'w_min': lambda v: v > 0,
-          'value_bound': lambda v: v > 0, 'fill': lambda v: True}
-    for k, v in p.items():
-        if not (ok[k](v) and (k == 'fill' or v < float('inf'))):
-            raise RuntimeError('%s: %s=%r is out of range' % (what, k, v))
-    return p
+    rules = {'z_near': {}, 'z_tol': {}, 'w_tap': dict(lo_open=True, hi=0.25), 'w_min': dict(lo_open=True),
+             'value_bound': dict(lo_open=True), 'fill': None}
+    return {k: float(v) if rules[k] is None else _real_arg(what, k, float(v), **rules[k]) for k, v in p.items()}
 
 
 def splat_workspace(n_views, C, H, W, device):
@@ -567,12 +563,9 @@ def splat_clear(zbuf, acc):
 
 
 def _splat_ws_ok(what, zbuf, acc, dev, V, C, H, W):
-    if not (torch.is_tensor(zbuf) and zbuf.device == dev and zbuf.dtype == torch.int32 and tuple(zbuf.shape) == (V, H, W) and
-            zbuf.is_contiguous()):
-        raise RuntimeError('%s: zbuf must be a contiguous int32 tensor %s on the device of the points' % (what, (V, H, W)))
-    if acc is not None and not (torch.is_tensor(acc) and acc.device == dev and acc.dtype == torch.int64 and
-                                tuple(acc.shape) == (V, H, W, C + 1) and acc.is_contiguous()):
-        raise RuntimeError('%s: acc must be a contiguous int64 tensor %s on the device of the points' % (what, (V, H, W, C + 1)))
+    _out_ok(what, 'zbuf', zbuf, (V, H, W), torch.int32, dev, 'the points')
+    if acc is not None:
+        _out_ok(what, 'acc', acc, (V, H, W, C + 1), torch.int64, dev, 'the points')
 
 
 def splat_zmin(zbuf, points, values, view, tables, n_views, valid=None, planar=True, z_near=1e-3, w_tap=1.0 / 64,
@@ -610,17 +603,8 @@ def splat_resolve(zbuf, acc, shift, w_min=0.25, value_bound=1.0, fill=0.0, out=N
     C -= 1
     _splat_ws_ok(what, zbuf, acc, acc.device, V, C, H, W)
     p = _splat_params(what, w_min=w_min, value_bound=value_bound, fill=fill)
-    shapes = {'image': ((V, C, H, W), torch.float32), 'depth': ((V, 1, H, W), torch.float32),
-              'weight': ((V, 1, H, W), torch.float32), 'hit': ((V, H, W), torch.uint8)}
-    res = {}
-    for k, (shape, dtype) in shapes.items():
-        o = out.get(k) if out is not None else None
-        if o is None:
-            o = torch.empty(shape, device=acc.device, dtype=dtype)
-        elif not (torch.is_tensor(o) and o.device == acc.device and o.dtype == dtype and tuple(o.shape) == shape and
-                  o.is_contiguous()):
-            raise RuntimeError('%s: out[%r] must be a contiguous %s tensor %s on the device of the workspace' % (what, k, dtype, shape))
-        res[k] = o
+    res = _outputs(what, out, {'image': ((V, C, H, W), torch.float32), 'depth': ((V, 1, H, W), torch.float32),
+                               'weight': ((V, 1, H, W), torch.float32), 'hit': ((V, H, W), torch.uint8)}, acc.device, 'the workspace')
     _lib.check(_lib.load().dvd_splat_resolve(_p(zbuf), _p(acc), V, C, H, W, int(shift), p['w_min'], p['value_bound'], p['fill'],
                                              _p(res['image']), _p(res['depth']), _p(res['weight']), _p(res['hit']), _stream()),
                'dvd_splat_resolve')
@@ -694,21 +678,12 @@ def eval_tracks(points, source, tables, depth_all, img_all, k_first=1, pairs=Non
       maps     True, or a float32 [T,B,3,H,W] destination: rel, photo, epe per point, -1 where the point does not count
     Rows whose target frame is past the end of the tables add nothing.  Integer atomics only: the same inputs give the same
     bits for any grid.  Everything is checked on the host before the launch; no device tensor is read back."""
-    import numpy as np
     what = 'eval_tracks'
     points, source, (R, t, K_T), T, B, H, W, N = _track_args(what, points, source, tables, True, host_source)
     dev = points.device
-    if isinstance(k_first, bool) or k_first not in (0, 1):
-        raise RuntimeError('%s: k_first must be 0 or 1, got %r' % (what, k_first))
-    z_tol, d_min = float(z_tol), float(d_min)
-    if not (0.0 <= z_tol < float('inf')):
-        raise RuntimeError('%s: z_tol=%r is out of range' % (what, z_tol))
-    if not (0.0 < d_min < float('inf')):
-        raise RuntimeError('%s: d_min=%r is out of range' % (what, d_min))
-    depth_all, img_all = _dev32(depth_all, 'depth_all'), _dev32(img_all, 'img_all')
-    if depth_all.device != dev or depth_all.numel() != N * H * W or depth_all.shape[0] != N:
-        raise RuntimeError('%s: depth_all must be [%d,1,%d,%d] on the device of the points, got %s' % (
-            what, N, H, W, tuple(depth_all.shape)))
+    k_first = _int_arg(what, 'k_first', k_first, 0, 1)
+    z_tol, d_min = _real_arg(what, 'z_tol', float(z_tol)), _real_arg(what, 'd_min', float(d_min), lo_open=True)
+    depth_all, img_all = _depth_all(what, depth_all, N, H, W, dev), _dev32(img_all, 'img_all')
     if img_all.device != dev or tuple(img_all.shape) != (N, 3, H, W):
         raise RuntimeError('%s: img_all must be [%d,3,%d,%d] on the device of the points, got %s' % (
             what, N, H, W, tuple(img_all.shape)))
@@ -722,22 +697,9 @@ def eval_tracks(points, source, tables, depth_all, img_all, k_first=1, pairs=Non
         if flow.device != dev or flow.dim() != 4 or tuple(flow.shape[1:]) != (H, W, 2) or flow.shape[0] < 1:
             raise RuntimeError('%s: flow_1_2 must be [P,%d,%d,2] on the device of the points, got %s' % (what, H, W, tuple(flow.shape)))
         P = int(flow.shape[0])
-        if not (torch.is_tensor(mask) and mask.is_cuda and mask.device == dev and mask.dtype == torch.uint8 and
-                tuple(mask.shape) == (P, H, W)):
-            raise RuntimeError('%s: mask must be a GPU uint8 tensor [%d,%d,%d] on the device of the points' % (what, P, H, W))
-        mask = mask if mask.is_contiguous() else mask.contiguous()
-        if torch.is_tensor(pair_row) and pair_row.is_cuda:
-            if pair_row.dtype != torch.int32 or tuple(pair_row.shape) != (T, B) or not pair_row.is_contiguous() or \
-                    pair_row.device != dev:
-                raise RuntimeError('%s: pair_row must be a contiguous GPU int32 tensor [%d,%d] on the device of the points' % (what, T, B))
-        else:
-            host = np.asarray(pair_row.cpu() if torch.is_tensor(pair_row) else pair_row)
-            if host.dtype.kind not in 'iu' or host.shape != (T, B):
-                raise RuntimeError('%s: pair_row must hold [%d,%d] integral rows, got %s %s' % (what, T, B, host.dtype, host.shape))
-            if host.size and (int(host.min()) < -1 or int(host.max()) >= P):
-                raise RuntimeError('%s: pair_row spans [%d, %d]; -1 or a row of the %d flow pairs' % (
-                    what, int(host.min()), int(host.max()), P))
-            pair_row = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev, non_blocking=True)
+        mask = _dev_u8(what, 'mask', mask, (P, H, W), dev)
+        # -1 or a row of the P flow pairs; a device tensor is never read back
+        pair_row, _ = _ids(what, 'pair_row', pair_row, (T, B), -1, P, dev, 'the points', floats=False)
     shift = eval_shift(H * W)
     if sums is None:
         sums = torch.zeros((T, B, 6), device=dev, dtype=torch.int64)
@@ -749,7 +711,7 @@ def eval_tracks(points, source, tables, depth_all, img_all, k_first=1, pairs=Non
         maps = None
     if maps is not None:
         maps_stride = _step_view(what, 'maps', maps, (T, B, 3, H, W), torch.float32, dev)
-    _lib.check(_lib.load().dvd_eval_tracks(_p(points), _p(source), int(k_first), _p(R), _p(t), _p(K_T), N, _p(depth_all),
+    _lib.check(_lib.load().dvd_eval_tracks(_p(points), _p(source), k_first, _p(R), _p(t), _p(K_T), N, _p(depth_all),
                                            _p(img_all), _p(pair_row), _p(flow), _p(mask), P, z_tol, d_min, shift, _p(sums),
                                            sums_stride, _p(maps), maps_stride, T, B, H, W, _stream()), 'dvd_eval_tracks')
     res = {'sums': sums, 'shift': shift}
@@ -764,14 +726,6 @@ SCORE_LOG_CAP = 32.0
 SCORE_SUMS = ('n', 'abs_rel', 'sq_rel', 'sq', 'log_sq', 'log', 'n_d1', 'n_d2', 'n_d3')
 SCORE_REGIONS = ('all', 'static', 'dynamic')
 SCORE_MAPS = ('abs_rel', 'sq', 'log')
-
-
-def _dev_u8(what, name, t, shape, dev):
-    if t is None:
-        return None
-    if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.uint8 and tuple(t.shape) == shape):
-        raise RuntimeError('%s: %s must be a GPU uint8 tensor %s on the device of the data' % (what, name, list(shape)))
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def ratio_median(num, den, mask=None, den_min=0.0):
@@ -834,22 +788,15 @@ def depth_score(pred, gt, scale, seg=None, mask=None, g_min=1e-2, sums=None, map
         if seg.device != dev or tuple(seg.shape) != (N, H, W):
             raise RuntimeError('%s: seg must be [%d,%d,%d] on the device of pred, got %s' % (what, N, H, W, tuple(seg.shape)))
     mask = _dev_u8(what, 'mask', mask, (N, H, W), dev)
-    g_min = float(g_min)
-    if not (0.0 <= g_min < float('inf')):
-        raise RuntimeError('%s: g_min=%r is out of range' % (what, g_min))
+    g_min = _real_arg(what, 'g_min', float(g_min))
     if N > 65535 or H * W >= 2 ** 30:
         raise RuntimeError('%s: N=%d frames of %dx%d: N <= 65535 and H * W < 2^30 are required' % (what, N, H, W))
-    limit = eval_shift(N * H * W)
-    if shift is None:
-        shift = limit
-    if isinstance(shift, bool) or int(shift) != shift or not (1 <= shift <= limit):
-        raise RuntimeError('%s: shift=%r outside 1 .. %d for %d pixels' % (what, shift, limit, N * H * W))
-    shift = int(shift)
+    limit = eval_shift(N * H * W)      # (for all the pixels of the call)
+    shift = limit if shift is None else _int_arg(what, 'shift', shift, 1, limit)
     if sums is None:
         sums = torch.zeros((N, 3, 9), device=dev, dtype=torch.int64)
-    elif not (torch.is_tensor(sums) and sums.device == dev and sums.dtype == torch.int64 and tuple(sums.shape) == (N, 3, 9) and
-              sums.is_contiguous()):
-        raise RuntimeError('%s: sums must be a contiguous int64 tensor [%d,3,9] on the device of pred' % (what, N))
+    else:
+        _out_ok(what, 'sums', sums, (N, 3, 9), torch.int64, dev, 'pred')
     point_maps = counted = None
     if maps is True:
         point_maps = torch.empty((N, 3, H, W), device=dev, dtype=torch.float32)

@@ -14,7 +14,8 @@ tests/test_eval_cpu.py shows that at most 1 % of the live points of each case ar
        kernel, measured     1.42e-6    1.00e-6    1.03e-4     (epe is largest on the points far outside the image, |u| ~ 300)
        fp32 specification   9.4e-7     8.5e-7     9.7e-5      (worst case each; the kernel / fp32 ratio is at most 1.5)
 2. sums against the maps, bit for bit: sums == sum of round(maps.double() * 2^shift) over the counted points; the counts are the
-   counts of non-negative map entries and of dvd_track_project's own `inside` / depth_at flags (the same u, v, z, d bit for bit).
+   counts of non-negative map entries and of dvd_track_project's own `inside` / depth_at flags (the same u, v, z, d bit for bit),
+   and where a point is seen the rel map is min(|z - d| / max(d, d_min), 1) in float32 of dvd_track_project's z and depth_at.
 3. sums against the spec: counts within the row's fragile points, value sums within n * (map bound) + n_fragile * cap +
    n * 2^-(shift+1).
 4. two runs give equal bits; maps on or off, and two halves of B accumulated into one tensor, give the same sums; dead rows are
@@ -132,6 +133,13 @@ def test_kernel_against_the_specification(shape, k_first, with_pairs):
     occluded = inside & (proj['z'].cpu() > proj['depth_at'].cpu() * torch.tensor(tol, dtype=torch.float32))
     assert torch.equal(sums[..., 0], inside.flatten(2).sum(2)) and torch.equal(sums[..., 1], occluded.flatten(2).sum(2)), name
     assert torch.equal(counted[:, :, 0], inside & ~occluded), name
+    # ... and the rel map itself: float32 arithmetic on dvd_track_project's z and depth_at of the same slab, bit for bit
+    seen = counted[:, :, 0].numpy()
+    z, d = proj['z'].cpu().numpy(), proj['depth_at'].cpu().numpy()
+    with np.errstate(all='ignore'):                                           # (points that are not seen may divide by anything)
+        rel = np.minimum(np.abs(z - d) / np.maximum(d, np.float32(1e-3)), np.float32(1.0))
+    assert rel.dtype == np.float32 and seen.any()
+    assert np.array_equal(got[:, :, 0].numpy()[seen].view(np.uint32), rel[seen].view(np.uint32)), name
 
     # 3. sums against the spec
     scale = float(2 ** shift)

@@ -117,7 +117,7 @@ def test_the_wrapper_refuses_what_needs_a_device_to_tell(ctx):
     bad_pair[0, 0, 0], bad_frame[0, 1, 1], bad_dir[0, 2, 2] = len(ctx.sc['pairs']), N, 2
     for kw, word in ((dict(obs=bad_pair), 'obs names pairs'), (dict(obs=bad_frame), 'obs names frames'), (dict(obs=bad_dir), 'dir column of obs'),
                      (dict(frames=[N]), 'frames span'), (dict(flow_2_1=s.flow_2_1[:-1]), 'flow_2_1'), (dict(flow_2_1=s.flow_2_1.cpu()), 'flow_2_1'),
-                     (dict(flow_1_2=s.flow_1_2.transpose(1, 2)), 'flow_1_2'), (dict(mask_1=s.mask_1.float()), 'mask_1'),
+                     (dict(flow_1_2=s.flow_1_2.transpose(1, 2)), 'flow_1_2'), (dict(mask_1=s.mask_1.float()), 'mask_1'), (dict(mask_1=None), 'mask_1'), (dict(mask_2=None), 'mask_2'),
                      (dict(mask_2=s.mask_2[:, :, ::2]), 'mask_2'), (dict(tables={k: v for k, v in s.tables.items() if k != 'K_inv_T'}), 'K_inv_T'),
                      (dict(tables=dict(s.tables, t=s.tables['t'][:-1])), 'table t'), (dict(tables=dict(s.tables, R=s.tables['R'].cpu())), 'table R'),
                      (dict(out={'depth': torch.empty(1, H, W, device=DEV)}), r"out\['depth'\]"),
