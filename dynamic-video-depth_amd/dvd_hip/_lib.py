@@ -246,6 +246,9 @@ SIGNATURES = {
     # triangulated depth and epipolar motion cue from stored flow and cameras (csrc/triangulate.hip; an addition within ABI 8)
     'dvd_triangulate': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_longlong] + [c_void_p] * 4 +
                         [c_int, c_int, c_float, c_float, c_float, c_int] + [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    # push-pull hole filling (csrc/fill.hip; additions within ABI 8)
+    'dvd_fill_workspace_bytes': (c_size_t, [c_int] * 4),
+    'dvd_fill_holes': (c_int, [c_void_p] * 3 + [c_int, c_float] + [c_int] * 4 + [c_void_p] * 4),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

@@ -51,6 +51,7 @@ SOURCES = [
     ('invert.hip', ['-ffp-contract=off']),
     ('track_filter.hip', ['-ffp-contract=off']),
     ('triangulate.hip', ['-ffp-contract=off']),
+    ('fill.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -161,9 +161,13 @@ def advect_points(model, store, depth, frames, steps, chunk, n_iter=4):
 
 
 def render(model, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
-           backward=False, n_iter=4, **splat_params):
+           backward=False, n_iter=4, inpaint=False, bg_power=2, **splat_params):
     """Model.render: see there."""
     opt = model.opt
+    if not isinstance(inpaint, (bool, np.bool_)):
+        raise ValueError('render: inpaint must be True or False, got %r' % (inpaint,))
+    if isinstance(bg_power, (bool, np.bool_)) or not isinstance(bg_power, (int, np.integer)) or not 0 <= bg_power <= 4:
+        raise ValueError('render: bg_power must be an integer in 0 .. 4, got %r' % (bg_power,))
     if advect and opt.use_cnn:
         raise NotImplementedError('Model.render integrates the scene-flow MLP kernels; the --use_cnn U-Net branch has no '
                                   'stash-free forward to chain and is not supported (advect=False renders held time)')
@@ -203,4 +207,18 @@ def render(model, store, target, sources, cam_c2w=None, K=None, depth=None, adve
             mask = torch.empty(S, H, W, device=dev, dtype=torch.uint8)
             entries.append((valid.contiguous(), mask, 'copy', 0))
         ops.store_gather(entries, np.array([frames, frames, frames], dtype=np.int32))
-        return ops.splat(points, colours, view, tabs, V, valid=mask, planar=True, **splat_params)
+        res = ops.splat(points, colours, view, tabs, V, valid=mask, planar=True, **splat_params)
+        if inpaint:
+            inpaint_views(res, int(bg_power), splat_params.get('fill', ops.SPLAT_DEFAULTS['fill']))
+        return res
+
+
+def inpaint_views(res, bg_power, fill):
+    """Fill the holes of a splat's result in place (ops.fill_holes, three launches): image and depth jointly as 4 channels,
+    known = hit, a hit pixel weighted by depth^bg_power.  image and depth are replaced by the completed ones -- their hit pixels
+    keep their bits --, 'level' is added, hit and weight stay.  A view that nothing hit is `fill` in all four channels."""
+    joint = torch.cat((res['image'], res['depth']), dim=1)
+    filled = ops.fill_holes(joint, res['hit'], bias=res['depth'], power=bg_power, fill=fill, out={'values': joint})
+    C = res['image'].shape[1]
+    res['image'], res['depth'], res['level'] = joint[:, :C], joint[:, C:], filled['level']
+    return res

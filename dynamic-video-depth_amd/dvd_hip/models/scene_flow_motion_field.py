@@ -535,7 +535,7 @@ class Model(NetInterface):
         return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk, n_back=n_back, n_iter=n_iter)
 
     def render(self, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
-               backward=False, n_iter=4, **splat_params):
+               backward=False, n_iter=4, inpaint=False, bg_power=2, **splat_params):
         """The video re-rendered from its own geometry and motion (models/render.py): for every view v the frames sources[v],
         un-projected with their refined depth, pushed along the scene-flow field to the time of frame target[v] (target[v] - f
         Euler steps, as in `track`) and splatted into one image with a soft z-buffer (ops.splat, csrc/splat.hip).
@@ -550,10 +550,18 @@ class Model(NetInterface):
                    True raises NotImplementedError)
           chunk    source images integrated per pass (default: 8 GB of world points); the result does not depend on it
           splat_params  z_near, z_tol, w_tap, w_min, value_bound (default 1: colours), fill of ops.splat
+          inpaint  True closes what no source reached (splat gaps, never-seen regions, the borders of a moved camera) by
+                   push-pull filling (ops.fill_holes, csrc/fill.hip; three more launches): image and depth jointly as 4
+                   channels, known = hit.  A hit pixel weighs depth^bg_power, bg_power 0 .. 4, so with bg_power > 0 the deeper
+                   surface dominates a coarse pixel that mixes foreground and background, which is what a disocclusion wants;
+                   2 is an untuned default.  The result gains `level` uint8 [V,H,W] (0 hit, k >= 1 the pyramid level of the
+                   nearest data, 255 a view nothing hit, which stays `fill`, depth included); image and depth keep their bits
+                   at hit pixels and are then views of one [V,4,H,W] tensor; hit and weight are unchanged.
         Returns device tensors: image [V,3,H,W], depth [V,1,H,W] (the nearest surface, 0 where nothing landed), weight
         [V,1,H,W] (summed bilinear weight) and hit uint8 [V,H,W].  Bitwise reproducible; nothing synchronises with the device."""
         return render.render(self, store, target, sources, cam_c2w=cam_c2w, K=K, depth=depth, advect=advect, chunk=chunk,
-                             valid=valid, backward=backward, n_iter=n_iter, **splat_params)
+                             valid=valid, backward=backward, n_iter=n_iter, inpaint=inpaint, bg_power=bg_power,
+                             **splat_params)
 
     def evaluate(self, store, start=None, n_steps=None, depth=None, chunk=None, maps=False, z_tol=0.05):
         """How consistent are the refined depth, the scene-flow field, the cameras and the optical flow? (models/evaluate.py)

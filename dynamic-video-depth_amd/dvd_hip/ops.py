@@ -638,6 +638,67 @@ def splat(points, values, view, tables, n_views, valid=None, planar=True, z_near
     return splat_resolve(zbuf, acc, shift, w_min=w_min, value_bound=value_bound, fill=fill, out=out)
 
 
+# -- push-pull hole filling (csrc/fill.hip) ----------------------------------------------------------------------------------
+FILL_MAX_C = 8              # kFillMaxC of csrc/fill.hip
+FILL_MAX_TILES = 2048       # kFillMaxTiles: the largest ceil(H / 32) * ceil(W / 32)
+FILL_EMPTY = 255            # the level of a view without a known pixel
+
+
+def fill_workspace(n_views, C, H, W, device):
+    """The workspace of fill_holes as a torch tensor, uncleared: levels 1 .. 5 of the pyramid, float32 [V, floats per view]."""
+    V, C, H, W = int(n_views), int(C), int(H), int(W)
+    nbytes = _lib.load().dvd_fill_workspace_bytes(V, C, H, W)
+    if nbytes == 0:
+        raise RuntimeError('fill_workspace: no workspace for V=%d C=%d H=%d W=%d (1 <= C <= %d, at most %d tiles of 32 x 32)' % (
+            V, C, H, W, FILL_MAX_C, FILL_MAX_TILES))
+    return torch.empty((V, nbytes // (4 * V)), device=device, dtype=torch.float32)
+
+
+def fill_holes(values, known, bias=None, power=0, fill=0.0, out=None, workspace=None):
+    """Push-pull hole filling (csrc/fill.hip) -> dict of values [V,C,H,W] and level uint8 [V,H,W].
+      values   [V,C,H,W], 1 <= C <= 8;  known  uint8 [V,H,W], non-zero where the pixel holds data
+      bias     [V,1,H,W] or None, power 0 .. 4: a known pixel weighs bias^power (one whose bias is not > 0, or whose weight is not
+               finite, counts as unknown), so that with a depth as bias the deeper surface dominates a coarse pixel that mixes two
+      fill     the values of a view without a known pixel
+      out      {'values', 'level'}, either or both preallocated; out['values'] may be `values` itself (in place)
+      workspace  fill_workspace(V, C, H, W, device), or None to allocate it here
+    Known pixels come back bit for bit; level is 0 there, k >= 1 where the nearest known ancestor sits at pyramid level k, 255
+    for an empty view.  Three launches on the current stream whatever the size, no atomics: the same inputs give the same bits,
+    and a view's result does not depend on the views it shares the call with."""
+    what = 'fill_holes'
+    values = _dev32(values, 'values')
+    if values.dim() != 4 or not 1 <= values.shape[1] <= FILL_MAX_C or values.numel() == 0:
+        raise RuntimeError('%s: values must be [V,C,H,W] with 1 <= C <= %d, got %s' % (what, FILL_MAX_C, tuple(values.shape)))
+    V, C, H, W = (int(v) for v in values.shape)
+    dev = values.device
+    if V > 65535:
+        raise RuntimeError('%s: at most 65535 views per launch, got %d' % (what, V))
+    known = _dev_u8(what, 'known', known, (V, H, W), dev)
+    if known is None:
+        raise RuntimeError('%s: known must be a GPU uint8 tensor [%d, %d, %d]' % (what, V, H, W))
+    if bias is not None:
+        bias = _dev32(bias, 'bias')
+        if bias.device != dev or tuple(bias.shape) != (V, 1, H, W):
+            raise RuntimeError('%s: bias must be [%d,1,%d,%d] on the device of the values, got %s' % (what, V, H, W, tuple(bias.shape)))
+    power = _int_arg(what, 'power', power, 0, 4)
+    if isinstance(fill, bool) or not isinstance(fill, (int, float, np.integer, np.floating)):
+        raise RuntimeError('%s: fill must be a number, got %r' % (what, fill))
+    if workspace is None:
+        workspace = fill_workspace(V, C, H, W, dev)
+    else:
+        nbytes = _lib.load().dvd_fill_workspace_bytes(V, C, H, W)
+        if nbytes == 0:
+            raise RuntimeError('%s: images of %d x %d are not supported (at most %d tiles of 32 x 32)' % (what, H, W, FILL_MAX_TILES))
+        if not (torch.is_tensor(workspace) and workspace.device == dev and workspace.dtype == torch.float32 and
+                workspace.is_contiguous() and workspace.numel() * 4 >= nbytes):
+            raise RuntimeError('%s: workspace must be a contiguous float32 tensor of at least %d bytes on the device of the values' % (
+                what, nbytes))
+    res = _outputs(what, out, {'values': ((V, C, H, W), torch.float32), 'level': ((V, H, W), torch.uint8)}, dev, 'the values')
+    _lib.check(_lib.load().dvd_fill_holes(_p(values), _p(known), _p(bias), power, float(fill), V, C, H, W, _p(res['values']),
+                                          _p(res['level']), _p(workspace), _stream()), 'dvd_fill_holes')
+    return res
+
+
 # -- a finished optimisation scored along its tracks (csrc/eval.hip) ---------------------------------------------------------
 EVAL_CAP = 1024.0            # photo and epe are capped here (2^10); rel at 1
 EVAL_SUMS = ('n_inside', 'n_occluded', 'depth_rel', 'photo', 'n_flow', 'flow_epe')
@@ -1025,7 +1086,8 @@ BYTE_CLASS_KERNELS = {
                                                   'head1x1_', 'cast_scale_kernel'),
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
                                                    'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
-                                                   'depth_score_kernel', 'track_filter_kernel', 'triangulate_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'depth_score_kernel', 'track_filter_kernel', 'triangulate_kernel', 'fill_pull_kernel',
+                                                   'fill_mid_kernel', 'fill_push_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

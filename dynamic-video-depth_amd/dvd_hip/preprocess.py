@@ -89,7 +89,7 @@ def triangulate_plan(pairs, n_frames, frames=None, gaps=None):
 
 
 def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0, min_parallax_deg=0.5, z_near=1e-3, min_count=2,
-                      tables=None, chunk=None):
+                      tables=None, chunk=None, densify=False):
     """A depth map that does not depend on the network, a confidence for it and a motion cue, from a FrameStore's flows,
     occlusion masks and cameras (ops.triangulate, csrc/triangulate.hip; the table of triangulate_plan over store.cat.pairs).
     -> dict on the device, for the B requested frames (None: all):
@@ -100,7 +100,10 @@ def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0,
       static, moving    bool [B,H,W]: count >= min_count;  usable >= min_count and no consistent observation
       frames            the frame ids, int32 on the host
     min_parallax_deg: an observation whose rays meet under a smaller angle is not used.  tables: cameras other than the store's
-    (e.g. at another scale).  chunk: frames per launch (None: one launch); it does not change a bit."""
+    (e.g. at another scale).  chunk: frames per launch (None: one launch); it does not change a bit.
+    densify=True adds depth_dense [B,1,H,W], `depth` with everything that is not `static` filled from the static pixels by
+    push-pull interpolation (ops.fill_holes with equal weights; 0 for a frame without a static pixel), and dense_level uint8
+    [B,H,W], the pyramid level of the nearest static pixel (0 on them, 255 for such a frame).  Nothing else changes."""
     import math
     import numpy as np
     from . import ops
@@ -108,6 +111,8 @@ def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0,
         raise ValueError('triangulate_depth: min_parallax_deg must be in (0, 90], got %r' % (min_parallax_deg,))
     if chunk is not None and (isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1):
         raise ValueError('triangulate_depth: chunk must be a positive number of frames, got %r' % (chunk,))
+    if not isinstance(densify, (bool, np.bool_)):
+        raise ValueError('triangulate_depth: densify must be True or False, got %r' % (densify,))
     fr, obs = triangulate_plan(store.cat.pairs, store.cat.n_frames, frames, gaps)
     B, H, W, dev = len(fr), store.H, store.W, store.device
     chunk = min(B, 65535) if chunk is None else min(int(chunk), 65535)
@@ -122,6 +127,9 @@ def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0,
     res['frames'] = fr
     res['static'] = res['count'] >= min_count
     res['moving'] = (res['usable'] >= min_count) & (res['count'] == 0)
+    if densify:
+        filled = ops.fill_holes(res['depth'], res['static'].to(torch.uint8), power=0, fill=0.0)
+        res['depth_dense'], res['dense_level'] = filled['values'], filled['level']
     return res
 
 

@@ -975,6 +975,36 @@ int dvd_depth_score(const float* pred, const float* gt, const float* scale, cons
                     float g_min, int shift, long long* sums, float* maps, unsigned char* counted, int N, int H, int W,
                     dvd_stream_t stream);
 
+/* Push-pull hole filling (additions within ABI 8; csrc/fill.hip, ops.fill_holes, Model.render(inpaint=True),
+ * preprocess.triangulate_depth(densify=True)): what a splat or a triangulation left empty, from a 2x pyramid of what it did not.
+ *   values  float [V, C, H, W], 1 <= C <= 8;  known  uint8 [V, H, W];  bias  float [V, 1, H, W] or NULL;  power 0 .. 4
+ *   level 0   a = known != 0 ? bias^power : 0, the power by repeated multiplication (1 without bias or with power 0).  A pixel
+ *             whose a is not finite or not > 0 is unknown, and so is one whose bias (where it is used) is not > 0, which an
+ *             even power would hide; the value of an unknown pixel is never read into a result.
+ *   pull      level l + 1 is (ceil(H_l / 2), ceil(W_l / 2)), up to 1 x 1.  Over the children (2y+dy, 2x+dx) inside the level, in
+ *             the order (0,0) (0,1) (1,0) (1,1):  A = sum a_c, n = #{a_c > 0};  n > 0: v' = (sum a_c v_c) / A, a' = A / n;
+ *             else v' = a' = 0.  (The mean as the carried weight keeps a within the range of the level-0 weights.)
+ *   push      a pixel with a_l > 0 keeps v_l; any other takes the bilinear sample of the completed level above at
+ *             ((y + .5) / 2 - .5, (x + .5) / 2 - .5): 0.75 of the parent x >> 1 and 0.25 of its neighbour on the pixel's side,
+ *             the neighbour's index clamped to the level; horizontal pairs first, then the vertical pair.
+ *   out_values  the completed values; known pixels are the input bits.  out_values == values is allowed (any other overlap is not).
+ *   out_level   uint8 [V, H, W]: 0 known, k >= 1 the lowest level at which an ancestor (y >> k, x >> k) is known, 255 for a
+ *               view without a known pixel, whose values all become `fill`.
+ * Every statement is a separate fp32 operation in the order written, sums from left to right, divisions IEEE.  Three launches
+ * whatever V, H and W (32 x 32 tiles pull levels 1 .. 5 into the workspace; one block per view finishes level 5 and above in
+ * LDS; the tiles push back down); no atomics, nothing synchronises with the host.  A view's result does not depend on V or on
+ * the views it shares a call with, and two runs give the same bits.  Vector accesses need W % 4 == 0 and 16-byte aligned float
+ * (4-byte aligned byte) tensors; anything else takes the one-pixel path.
+ *   workspace   dvd_fill_workspace_bytes(V, C, H, W) bytes, 4-byte aligned, uncleared: 4 V (C + 1) sum_{l=1..5} H_l W_l.  The
+ *               function returns 0 for arguments dvd_fill_holes refuses.
+ * DVD_EINVAL before any HIP call: a null pointer (bias excepted), power outside 0 .. 4, V outside 1 .. 65535, C outside 1 .. 8,
+ * H or W < 1, H * W >= 2^30, ceil(H / 32) * ceil(W / 32) > 2048 (the one-block-per-view kernel holds level 5 and above in
+ * 148,032 of the 163,840 bytes of LDS), a misaligned float pointer.  Weights are expected below FLT_MAX / 4.  Bytes are counted
+ * under DVD_BYTES_GEOMETRY. */
+size_t dvd_fill_workspace_bytes(int V, int C, int H, int W);
+int dvd_fill_holes(const float* values, const unsigned char* known, const float* bias, int power, float fill, int V, int C,
+                   int H, int W, float* out_values, unsigned char* out_level, void* workspace, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
