@@ -249,6 +249,12 @@ SIGNATURES = {
     # push-pull hole filling (csrc/fill.hip; additions within ABI 8)
     'dvd_fill_workspace_bytes': (c_size_t, [c_int] * 4),
     'dvd_fill_holes': (c_int, [c_void_p] * 3 + [c_int, c_float] + [c_int] * 4 + [c_void_p] * 4),
+    # query-point tracks: seed, per-point projection and the TAP-Vid counts (csrc/point_track.hip; additions within ABI 8)
+    'dvd_point_seed': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    'dvd_point_project': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int, c_float] + [c_void_p] * 6 + [c_int] * 4 +
+                          [c_void_p]),
+    'dvd_point_score': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_void_p,
+                                c_int, c_int, c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

@@ -52,6 +52,7 @@ SOURCES = [
     ('track_filter.hip', ['-ffp-contract=off']),
     ('triangulate.hip', ['-ffp-contract=off']),
     ('fill.hip', ['-ffp-contract=off']),
+    ('point_track.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

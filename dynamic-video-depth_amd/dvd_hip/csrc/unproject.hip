@@ -7,9 +7,11 @@
 // accumulating) + 4 B written backward.  One thread per 4 horizontally adjacent
 // pixels (16-byte accesses on the planar layout the scene-flow MLP consumes).
 // Same fp32 operation order as torch's CPU matmul (dvd_common.h), built with
-// -ffp-contract=off, so the points are bit-identical to the reference's.
+// -ffp-contract=off, so the points are bit-identical to the reference's.  The
+// per-pixel body is unproject_point (unproject_point.h), shared with the query seed
+// of csrc/point_track.hip.
 
-#include "dvd_common.h"
+#include "unproject_point.h"
 
 namespace dvd {
 
@@ -40,14 +42,7 @@ __global__ __launch_bounds__(256) void unproject_fwd_kernel(const float* __restr
   const int y = p0 / W, x = p0 - y * W;
   float P[3][PX];
 #pragma unroll
-  for (int i = 0; i < PX; ++i) {
-    float r0, r1, r2, q0, q1, q2;
-    rowvec_mat3((float)(x + i), (float)y, 1.0f, Ki, r0, r1, r2);
-    rowvec_mat3(d[i] * r0, d[i] * r1, d[i] * r2, R, q0, q1, q2);
-    P[0][i] = q0 + t[0];
-    P[1][i] = q1 + t[1];
-    P[2][i] = q2 + t[2];
-  }
+  for (int i = 0; i < PX; ++i) unproject_point((float)(x + i), (float)y, d[i], Ki, R, t, P[0][i], P[1][i], P[2][i]);
   if (PLANAR) {
     float* o = out + (size_t)b * 3 * HW + p0;
 #pragma unroll

@@ -50,7 +50,7 @@ from ..networks.FCNUnet import FCNUnet
 from ..networks.sceneflow_field import SceneFlowFieldNet
 from ..third_party.hourglass import HourglassModel_Embed
 from ..third_party.MiDaS import MidasNet
-from . import evaluate, frame_union, render, score_depth, sf_step, tracks
+from . import evaluate, frame_union, point_tracks, render, score_depth, sf_step, tracks
 from . import filter as depth_filter
 from .depth_runner import DepthRunner, head_room_fraction, images_per_chunk, keep_slot_fits      # noqa: F401 (re-exported)
 from .netinterface import NetInterface
@@ -533,6 +533,58 @@ class Model(NetInterface):
         (= n_back, a Python int), steps_valid_back int32 [B] (= min(n_back, start)) and resid fp32 [n_back,B] -- per backward
         step j (row j - 1) the largest move of a point in the last iteration, 0 where there is no frame."""
         return tracks.track(self, store, start, n_steps, depth=depth, chunk=chunk, n_back=n_back, n_iter=n_iter)
+
+    def track_points(self, store, queries, n_steps=None, n_back=None, depth=None, z_tol=0.05, n_iter=4, chunk=None):
+        """Where chosen points of the video are in its other frames (models/point_tracks.py): `track` for a list of queries
+        instead of every pixel of whole frames.  queries: a host array [Q,3] of (frame, x, y) in the store's pixel coordinates,
+        pixel centres at integers, sub-pixel positions welcome, any mix of frames; ValueError for an empty list, a frame that is
+        not integral or not a frame, a position outside [0,W-1] x [0,H-1], or a NaN.  Each query is seeded from the refined depth
+        of its own frame at its own position (ops.point_seed: direct bilinear taps, then the per-pixel body of ops.unproject),
+        carried n_steps Euler steps forwards and n_back inverse steps (n_iter fixed-point iterations each) backwards by the
+        scene-flow MLP kernels -- one launch of Q points per step -- and every row is projected into the camera of ITS frame by
+        one ops.point_project launch (csrc/point_track.hip).
+          n_steps  default N - 1 - min(frame);  n_back  default max(frame): together the whole video on both sides of every
+                   query; n_back = 0 is the "query first" protocol of the tracking benchmarks
+          depth    [N,1,H,W] refined depth (default: video_depth of the store);  z_tol: a point deeper than the target frame's
+                   depth * (1 + z_tol) is occluded there (evaluate's rule)
+          chunk    queries per pass (default: 8 GB of world points); the result does not depend on it
+        All queries take all steps; the rows that fall off the video are masked by the projection -- at most 2 x wasted MLP work
+        on a tiny workload.  Returns device tensors, row-major (T1 = n_back + 1 + n_steps; row j of query q is frame
+        frame[q] + j - n_back):
+          points [T1,3,Q]  world positions;  uv [T1,Q,2], z, depth_at [T1,Q]  as `track` defines them;  inside uint8 [T1,Q]
+          visible uint8 [T1,Q]  inside and not occluded;  target int32 [T1,Q]  the frame a row looks into, -1 where there is
+          none or the query is not ok (such a row is all zeros; `target` scatters the rows frame-major in one line)
+          ok uint8 [Q]  the query's depth is finite and > 0;  origin  = n_back (a Python int);  resid fp32 [n_back]  per
+          backward step the largest move of a point in the last iteration.
+        An integer query has, bit for bit, what `track` gives that pixel.  Nothing synchronises with the device; --use_cnn
+        raises NotImplementedError."""
+        return point_tracks.track_points(self, store, queries, n_steps=n_steps, n_back=n_back, depth=depth, z_tol=z_tol,
+                                         n_iter=n_iter, chunk=chunk)
+
+    def score_tracks(self, store, queries, gt_uv, gt_state, thresholds=(1, 2, 4, 8, 16), px_scale=(1.0, 1.0), **track_args):
+        """How well do the tracks follow annotated trajectories? (models/point_tracks.py)  The TAP-Vid protocol of the
+        long-range tracking benchmarks: `track_points` of the queries, then ONE fused kernel (ops.point_score) that counts in
+        64-bit integers.
+          gt_uv    [Q,N,2] the annotated position of every query's track in every frame (host array or GPU float32 tensor);
+          gt_state [Q,N]  0 visible, 1 occluded, >= 2 not annotated.  point_tracks.queries_first / queries_strided make the
+                   queries of either protocol from annotations [T,N,2] and return the track of each, so gt_uv[track] repeats
+                   the ground truth per query
+          thresholds  five distances in pixels;  px_scale = (sx, sy) scales the position error before it is compared: a
+                   benchmark that scores in a 256 x 256 raster is evaluated with (256 / W, 256 / H)
+          track_args  n_steps, n_back, depth, z_tol, n_iter, chunk of `track_points`
+        A row counts iff it has a frame, is not the query itself and is annotated.  Returns, float64 on the device and NaN
+        where a denominator is 0:
+          occlusion_accuracy  n_occ_agree / n_eval (predicted `visible` equals annotated visible)
+          pts_within [5]  per threshold the visible points closer than it, / n_gt_visible;  average_pts_within
+          jaccard [5]  n_tp / (n_gt_visible + n_fp): true positives are visible, predicted visible and within; false positives
+                   predicted visible but occluded or not within;  average_jaccard
+          mean_err  mean position error of the visible points, each capped at 1024;  n_eval, n_gt_visible int64
+          by_offset  the same quantities per slab row [T1]: row j is temporal distance j - origin, the accuracy-over-distance
+                   curve a long-range tracker is judged by
+          sums int64 [T1,19], shift  the kernel's exact sums (ops.POINT_SUMS);  tracks  the `track_points` result
+        Bitwise reproducible; nothing synchronises with the device.  --use_cnn raises NotImplementedError."""
+        return point_tracks.score_tracks(self, store, queries, gt_uv, gt_state, thresholds=thresholds, px_scale=px_scale,
+                                         **track_args)
 
     def render(self, store, target, sources, cam_c2w=None, K=None, depth=None, advect=True, chunk=None, valid=None,
                backward=False, n_iter=4, inpaint=False, bg_power=2, **splat_params):

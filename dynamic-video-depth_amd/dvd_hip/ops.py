@@ -489,6 +489,162 @@ def project_backward(g_uv, points, start, tables, planar=True, out=None, accumul
     return out
 
 
+# -- query-point tracks (csrc/point_track.hip) -------------------------------------------------------------------------------
+POINT_SEED_TABLES = ('R_T', 't', 'K_inv_T')
+POINT_CAP = 1024.0           # the position error of the last word is capped here (2^10)
+POINT_THRESHOLDS = (1.0, 2.0, 4.0, 8.0, 16.0)
+POINT_SUMS = (('n_eval', 'n_gt_visible', 'n_occ_agree') + tuple('n_within_%d' % i for i in range(5)) +
+              tuple('n_tp_%d' % i for i in range(5)) + tuple('n_fp_%d' % i for i in range(5)) + ('err',))
+
+
+def _point_queries(what, frame, xy, dev, on, N, host_frame=None):
+    """The query list of the point kernels -> (frame int32 [Q] on dev, xy float32 [Q,2] on dev, Q).  frame: a host sequence /
+    array / CPU tensor (range-checked against the N frames, uploaded here) or a GPU int32 tensor (checked from host_frame where
+    the caller has it, never read back); xy: a GPU float32 tensor."""
+    xy = _dev32(xy, 'xy')
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.shape[0] < 1 or xy.device != dev:
+        raise RuntimeError('%s: xy must be a float32 tensor [Q,2] with Q >= 1 on the device of %s, got %s' % (what, on, tuple(xy.shape)))
+    Q = int(xy.shape[0])
+    if Q >= 1 << 30:
+        raise RuntimeError('%s: at most 2^30 - 1 queries per launch, got %d' % (what, Q))
+    frame, _ = _ids(what, 'frame', frame, (Q,), 0, N, dev, on, host=host_frame)
+    return frame, xy, Q
+
+
+def point_seed(frame, xy, depth_all, tables, time_stamps=True, out=None, host_frame=None):
+    """Queries -> world points (dvd_point_seed, csrc/point_track.hip) -> {'points' [3,Q], 'ok' uint8 [Q][, 't' [Q]]}.
+      frame    Q frame ids: a host sequence / array / CPU tensor (uploaded here) or a GPU int32 tensor (then host_frame, its host
+               copy, is what the range check reads; without it the kernel's own check decides: `ok` is 0 for a frame outside)
+      xy       GPU float32 [Q,2]: the position in the frame, pixel centres at integers
+      depth_all [N,1,H,W];  tables {'R_T': [N,3,3] camera->world, 't': [N,3], 'K_inv_T': [N,3,3], 'ts_vali': [N]} --
+               FrameStore.tables has them under these names;  time_stamps False: no 't' (a time-independent field)
+      out      optional dict of preallocated outputs (points may be a row of a [T1,3,Q] slab)
+    The depth is sampled by direct bilinear taps (weights exactly (1,0,0,0) at an integer position) and un-projected by the
+    per-pixel body of ops.unproject: an integer query has that pixel's bits.  ok = the frame exists, the depth is finite and
+    > 0 and the position is inside [0,W-1] x [0,H-1]; otherwise the point is 0.  Checked on the host; nothing is read back."""
+    what = 'point_seed'
+    depth_all = _dev32(depth_all, 'depth_all')
+    dev = depth_all.device
+    if depth_all.dim() != 4 or depth_all.shape[1] != 1 or depth_all.numel() == 0:
+        raise RuntimeError('%s: depth_all must be [N,1,H,W], got %s' % (what, tuple(depth_all.shape)))
+    N, _, H, W = (int(v) for v in depth_all.shape)
+    if H < 2 or W < 2 or H * W >= 1 << 30:
+        raise RuntimeError('%s: images of %d x %d; the sampling rule needs H, W >= 2 and H * W < 2^30' % (what, H, W))
+    (R_T, t, K_inv_T), _ = _tables(what, tables, POINT_SEED_TABLES, (9, 3, 9), dev, 'the depth', n=N)
+    ts = None
+    if time_stamps:
+        if 'ts_vali' not in tables:
+            raise RuntimeError('%s: tables must hold ts_vali (or pass time_stamps=False)' % what)
+        ts = _dev32(tables['ts_vali'], 'table ts_vali')
+        if ts.device != dev or ts.numel() != N:
+            raise RuntimeError('%s: table ts_vali must hold one value for each of %d rows, got %s' % (what, N, tuple(ts.shape)))
+    frame, xy, Q = _point_queries(what, frame, xy, dev, 'the depth', N, host_frame)
+    shapes = {'points': ((3, Q), torch.float32), 'ok': ((Q,), torch.uint8)}
+    if time_stamps:
+        shapes['t'] = ((Q,), torch.float32)
+    res = _outputs(what, out, shapes, dev, 'the depth')
+    _lib.check(_lib.load().dvd_point_seed(_p(frame), _p(xy), _p(depth_all), _p(R_T), _p(t), _p(K_inv_T), _p(ts), N,
+                                          _p(res['points']), _p(res.get('t')), _p(res['ok']), Q, H, W, _stream()), 'dvd_point_seed')
+    return res
+
+
+def point_project(points, frame, xy, tables, depth_all, k0=0, z_tol=0.05, ok=None, out=None, host_frame=None):
+    """Rows of integrated query points into their own target cameras (dvd_point_project) -> dict of uv [T1,Q,2], z, depth_at
+    [T1,Q], inside, visible uint8 [T1,Q], target int32 [T1,Q].
+      points   [T1,3,Q]: row j of query q is its world point at the time of frame g = frame[q] + j + k0
+      frame, xy, host_frame  as point_seed takes them;  tables {'R', 't', 'K_T'} as track_project takes them
+      ok       None or uint8 [Q] (point_seed's): a query that is not ok gives zeros
+    The projection and the depth sample are track_project's, with the query's position as the source pixel: an integer query
+    has the bits track_project(.., k0) gives that pixel.  visible = inside && !(z > depth_at * (1 + z_tol)) (eval_tracks'
+    occlusion rule); target = g, or -1 where g is no frame or the query is not ok -- such a row is all zeros."""
+    what = 'point_project'
+    points = _dev32(points, 'points')
+    if points.dim() != 3 or points.shape[1] != 3 or points.numel() == 0:
+        raise RuntimeError('%s: points must be [T1,3,Q], got %s' % (what, tuple(points.shape)))
+    dev = points.device
+    T1 = int(points.shape[0])
+    if T1 > 65535:
+        raise RuntimeError('%s: at most 65535 rows per launch, got %d' % (what, T1))
+    k0 = _int_arg(what, 'k0', k0, 1 - (1 << 30), (1 << 30) - 1)
+    z_tol = _real_arg(what, 'z_tol', float(z_tol))
+    (R, t, K_T), N = _tables(what, tables, TRACK_TABLES, (9, 3, 9), dev, 'the points')
+    frame, xy, Q = _point_queries(what, frame, xy, dev, 'the points', N, host_frame)
+    if int(points.shape[2]) != Q:
+        raise RuntimeError('%s: points hold %d queries, xy %d' % (what, int(points.shape[2]), Q))
+    depth_all = _dev32(depth_all, 'depth_all')
+    if depth_all.device != dev or depth_all.dim() != 4 or depth_all.shape[0] != N or depth_all.shape[1] != 1:
+        raise RuntimeError('%s: depth_all must be [%d,1,H,W] on the device of the points, got %s' % (what, N, tuple(depth_all.shape)))
+    H, W = int(depth_all.shape[2]), int(depth_all.shape[3])
+    if H < 2 or W < 2 or H * W >= 1 << 30:
+        raise RuntimeError('%s: images of %d x %d; the sampling rule needs H, W >= 2 and H * W < 2^30' % (what, H, W))
+    ok = _dev_u8(what, 'ok', ok, (Q,), dev)
+    res = _outputs(what, out, {'uv': ((T1, Q, 2), torch.float32), 'z': ((T1, Q), torch.float32),
+                               'depth_at': ((T1, Q), torch.float32), 'inside': ((T1, Q), torch.uint8),
+                               'visible': ((T1, Q), torch.uint8), 'target': ((T1, Q), torch.int32)}, dev, 'the points')
+    _lib.check(_lib.load().dvd_point_project(_p(points), _p(frame), _p(xy), _p(ok), k0, _p(R), _p(t), _p(K_T), _p(depth_all), N,
+                                             z_tol, _p(res['uv']), _p(res['z']), _p(res['depth_at']), _p(res['inside']),
+                                             _p(res['visible']), _p(res['target']), T1, Q, H, W, _stream()), 'dvd_point_project')
+    return res
+
+
+def point_thr2(thresholds):
+    """The five squared thresholds as the kernel receives them: float32(t) * float32(t), rounded to float32."""
+    try:
+        thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        thr = np.zeros(0, np.float32)
+    with np.errstate(over='ignore', invalid='ignore'):
+        thr2 = (thr * thr).astype(np.float32)
+    if thr.size != 5 or not np.all(np.isfinite(thr2)) or not np.all(thr > 0) or not np.all(np.diff(thr2) > 0) or not thr2[0] > 0:
+        raise RuntimeError('point_score: thresholds must be 5 positive, ascending, finite numbers, got %r' % (thresholds,))
+    return thr2
+
+
+def point_score(uv, visible, target, gt_uv, gt_state, origin=-1, thresholds=POINT_THRESHOLDS, px_scale=(1.0, 1.0), sums=None):
+    """Predicted tracks against annotated ones (dvd_point_score): the TAP-Vid counts -> {'sums' int64 [T1,19], 'shift'}.
+      uv [T1,Q,2], visible uint8 [T1,Q], target int32 [T1,Q]   point_project's outputs
+      gt_uv    float32 [Q,N,2], frame-major;  gt_state uint8 [Q,N]: 0 visible, 1 occluded, >= 2 not annotated
+      origin   the slab row of the queries themselves, which is not scored (-1: none)
+      thresholds  five distances in pixels of the raster px_scale = (sx, sy) maps to: du = (u - gu) * sx, dv = (v - gv) * sy
+      sums     None (a cleared tensor is made) or an int64 [T1,19] tensor to ACCUMULATE into; words POINT_SUMS per slab row,
+               the last one in units of 2^-shift, shift = eval_shift(Q)
+    A point counts iff 0 <= target < N, its row is not the origin and gt_state < 2.  Integer atomics only: the same inputs give
+    the same bits for any grid.  Everything is checked on the host before the launch; nothing is read back."""
+    what = 'point_score'
+    uv = _dev32(uv, 'uv')
+    if uv.dim() != 3 or uv.shape[2] != 2 or uv.numel() == 0:
+        raise RuntimeError('%s: uv must be [T1,Q,2], got %s' % (what, tuple(uv.shape)))
+    dev = uv.device
+    T1, Q = int(uv.shape[0]), int(uv.shape[1])
+    if T1 > 65535 or Q >= 1 << 30:
+        raise RuntimeError('%s: at most 65535 rows of fewer than 2^30 queries per launch, got %d of %d' % (what, T1, Q))
+    visible = _dev_u8(what, 'visible', visible, (T1, Q), dev)
+    if visible is None:
+        raise RuntimeError('%s: visible must be a GPU uint8 tensor [%d,%d]' % (what, T1, Q))
+    _out_ok(what, 'target', target, (T1, Q), torch.int32, dev, 'uv')
+    gt_uv = _dev32(gt_uv, 'gt_uv')
+    if gt_uv.device != dev or gt_uv.dim() != 3 or gt_uv.shape[0] != Q or gt_uv.shape[1] < 1 or gt_uv.shape[2] != 2:
+        raise RuntimeError('%s: gt_uv must be [%d,N,2] on the device of uv, got %s' % (what, Q, tuple(gt_uv.shape)))
+    N = int(gt_uv.shape[1])
+    gt_state = _dev_u8(what, 'gt_state', gt_state, (Q, N), dev)
+    if gt_state is None:
+        raise RuntimeError('%s: gt_state must be a GPU uint8 tensor [%d,%d]' % (what, Q, N))
+    origin = _int_arg(what, 'origin', origin, -1, T1 - 1)
+    if not isinstance(px_scale, (tuple, list)) or len(px_scale) != 2:
+        raise RuntimeError('%s: px_scale must be (sx, sy), got %r' % (what, px_scale))
+    sx, sy = (_real_arg(what, n, v, lo_open=True) for n, v in zip(('sx', 'sy'), px_scale))
+    thr2 = point_thr2(thresholds)
+    shift = eval_shift(Q)
+    if sums is None:
+        sums = torch.zeros((T1, len(POINT_SUMS)), device=dev, dtype=torch.int64)
+    else:
+        _out_ok(what, 'sums', sums, (T1, len(POINT_SUMS)), torch.int64, dev, 'uv')
+    c_thr2 = (ctypes.c_float * 5)(*[float(v) for v in thr2])
+    _lib.check(_lib.load().dvd_point_score(_p(uv), _p(visible), _p(target), origin, _p(gt_uv), _p(gt_state), N, sx, sy, c_thr2,
+                                           shift, _p(sums), T1, Q, _stream()), 'dvd_point_score')
+    return {'sums': sums, 'shift': shift}
+
+
 # -- forward splat with a soft z-buffer (csrc/splat.hip) -------------------------------------------------------------------
 SPLAT_MAX_C = 8
 SPLAT_DEFAULTS = dict(z_near=1e-3, z_tol=0.05, w_tap=1.0 / 64, w_min=0.25, value_bound=1.0, fill=0.0)

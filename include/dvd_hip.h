@@ -1005,6 +1005,54 @@ size_t dvd_fill_workspace_bytes(int V, int C, int H, int W);
 int dvd_fill_holes(const float* values, const unsigned char* known, const float* bias, int power, float fill, int V, int C,
                    int H, int W, float* out_values, unsigned char* out_level, void* workspace, dvd_stream_t stream);
 
+/* Query-point tracks (additions within ABI 8; csrc/point_track.hip, models/point_tracks.py): Q chosen, sub-pixel points of any
+ * frames instead of every pixel of whole frames, and their score against annotated trajectories (the TAP-Vid protocol).  A
+ * slab row is [3, Q] -- what dvd_sf_mlp_fwd takes as n_pix = Q points with a time stamp each -- so the queries integrate in
+ * one launch per step, forwards and (dvd_track_invert_update) backwards.
+ *   frame      DEVICE int [Q]: the frame a query lives in;  xy  float [Q, 2]: its position there, pixel centres at integers
+ *   tables     as datasets/frame_store.py keeps them: R_T [N,3,3] camera->world, t [N,3], K_inv_T [N,3,3], ts_vali [N] for the
+ *              seed (dvd_unproject_fwd's R, t, K_inv per frame); R [N,3,3] world->camera, t, K_T [N,3,3] for the projection
+ *   depth_all  [N, 1, H, W]
+ * dvd_point_seed: d = depth_all[frame] at (x, y) by direct bilinear taps -- x clamped to [0, W-1] (a NaN becomes 0), x0 =
+ * floorf(x), weights from x - x0, a tap past the east or south edge reads as 0, the taps combined as dvd_track_project combines
+ * them -- so the weights at an integer position are exactly (1, 0, 0, 0); then P = (d * ((x, y, 1) @ K_inv)) @ R + t by the
+ * device function dvd_unproject_fwd runs per pixel: an integer query has that pixel's bits.
+ *   points     [3, Q] planar;  t_out  [Q] = ts_vali[frame], with ts_vali both or none (a time-independent field);
+ *   ok         uint8 [Q] = frame in 0 .. N-1 && d finite and > 0 && 0 <= x <= W-1 && 0 <= y <= H-1; otherwise the point is 0
+ *              (and t_out 0 where the frame is no frame)
+ * dvd_point_project: row j of query q looks into frame g = frame[q] + j + k0 with the functions of dvd_track_project_from and
+ * the query's own (x, y) as the source pixel: an integer query has the bits that entry gives the pixel.
+ *   points     [T1, 3, Q];  ok  uint8 [Q] or NULL (every query counts)
+ *   uv [T1, Q, 2], z, depth_at [T1, Q], inside uint8 [T1, Q]   as dvd_track_project defines them
+ *   visible    uint8 [T1, Q] = inside && !(z > depth_at * (1 + z_tol)), 1 + z_tol formed once in fp32 (dvd_eval_tracks' rule)
+ *   target     int [T1, Q] = g, or -1
+ * A row whose g is outside 0 .. N-1, whose frame is, or whose query is not ok writes zeros and -1 and reads nothing else.
+ * dvd_point_score: predictions (uv, visible, target of dvd_point_project) against
+ *   gt_uv      float [Q, N, 2], frame-major;  gt_state  uint8 [Q, N]: 0 visible, 1 occluded, >= 2 not annotated
+ * Row j of query q is an evaluation point iff 0 <= target < N, j != origin (-1: no origin row) and gt_state[q][target] < 2.
+ * In fp32, every operation separate: du = (u - gu) * sx, dv = (v - gv) * sy, e2 = du * du + dv * dv, within_i = e2 < thr2[i]
+ * (strict; a NaN is never within), vis_gt = gt_state == 0.
+ *   thr2       HOST array of 5 squared thresholds, finite, positive, ascending
+ *   sums       long long [T1, 19], ACCUMULATED into (the caller clears it), per slab row: n_eval, n_gt_visible, n_occ_agree
+ *              (visible == vis_gt), 5 x n_within (vis_gt && within), 5 x n_tp (vis_gt && within && visible), 5 x n_fp (visible
+ *              && (!vis_gt || !within)), sum over vis_gt points of q(min(sqrt(e2), 1024)), q(x) = llrint((double)x * 2^shift),
+ *              the square root correctly rounded, a NaN taken as the cap.  1 <= shift <= min(32, 62 - 10 - ceil_log2(Q)).
+ * One point per thread, plain stores, one writer per element; the score reduces in 64-bit integers (registers, a shuffle tree,
+ * LDS) and issues at most 19 integer atomicAdd per block: the same bits for any grid.  DVD_EINVAL before any HIP call: a null
+ * pointer (ok, ts_vali / t_out excepted), T1 outside 1..65535, Q outside 1..2^30-1, N < 1, H or W < 2, H * W >= 2^30, |k0| >=
+ * 2^30, z_tol < 0 or not finite, origin outside -1..T1-1, sx or sy not finite and > 0, bad thresholds, a shift outside its
+ * range.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_point_seed(const int* frame, const float* xy, const float* depth_all, const float* R_T, const float* t,
+                   const float* K_inv_T, const float* ts_vali, int N, float* points, float* t_out, unsigned char* ok, int Q,
+                   int H, int W, dvd_stream_t stream);
+int dvd_point_project(const float* points, const int* frame, const float* xy, const unsigned char* ok, int k0, const float* R,
+                      const float* t, const float* K_T, const float* depth_all, int N, float z_tol, float* uv, float* z,
+                      float* depth_at, unsigned char* inside, unsigned char* visible, int* target, int T1, int Q, int H, int W,
+                      dvd_stream_t stream);
+int dvd_point_score(const float* uv, const unsigned char* visible, const int* target, int origin, const float* gt_uv,
+                    const unsigned char* gt_state, int N, float sx, float sy, const float* thr2, int shift, long long* sums,
+                    int T1, int Q, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
