@@ -150,10 +150,10 @@ class scene_flow_projection_slack(nn.Module):
     def forward(self, depth_1, depth_2, flow_1_2, flow_2_1, R_1, R_2, R_1_T, R_2_T, t_1, t_2, K, K_inv, sflow_1_2,
                 sflow_2_1):
         cams = dict(R_1=R_1, R_2=R_2, R_1_T=R_1_T, R_2_T=R_2_T, t_1=t_1, t_2=t_2, K=K, K_inv=K_inv)
-        B, _, H, W = depth_1.shape
         s = _surfaces(depth_1, depth_2, flow_1_2, cams, ('dflow_1_2', 'depth_image_1_2', 'depth_warp_1_2', 'global_p1',
                                                          'staticflow_1_2', 'p1_camera_2', 'warped_p2_camera_2'),
                       sflow_1_2=sflow_1_2)
+        B, _, H, W = depth_1.shape          # (ops.warp_surfaces has checked every shape by now)
         s.update(depth_1=depth_1.view(B, 1, H, W), depth_2=depth_2.view(B, 1, H, W), scenef_1_2=sflow_1_2)
         return s
 

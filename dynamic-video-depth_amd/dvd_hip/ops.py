@@ -162,15 +162,70 @@ def _point_slab(what, p):
     return p
 
 
-def pack_cameras(cams):
-    """dict of the eight camera tensors ([B,1,1,3,3] / [B,1,1,1,3] or flat)
-    -> (ctypes struct, list of tensors kept alive)."""
-    keep, st = [], _lib.Cameras()
+def _shape_is(what, name, t, shapes):
+    """t is a tensor of one of `shapes`; a RuntimeError that names it otherwise.  Host arithmetic only: it holds for a tensor
+    anywhere, so it comes before the device checks and a test needs no GPU for it."""
+    if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
+        raise RuntimeError('%s: %s must be a tensor %s, got %s' % (
+            what, name, ' or '.join(str(list(sh)) for sh in shapes), tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    return t
+
+
+def _images(what, specs, dev=None):
+    """'These tensors are all [B,...,H,W] of this call': specs of (name, tensor or None, shapes) -> the tensors as contiguous
+    float32 GPU tensors, all on one device (`dev`, or that of the first).  Every shape is checked before any device or dtype,
+    and all of it before anything is launched; a None stays None."""
+    for name, t, shapes in specs:
+        if t is not None:
+            _shape_is(what, name, t, shapes)
+    res = []
+    for name, t, _ in specs:
+        if t is not None:
+            t = _dev32(t, '%s: %s' % (what, name))
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise RuntimeError('%s: %s is on %s, the other tensors are on %s' % (what, name, t.device, dev))
+        res.append(t)
+    return res
+
+
+def _image_size(what, name, t):
+    """(B, H, W) of the [B,1,H,W] tensor that fixes them for a call."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 1 or t.numel() == 0:
+        raise RuntimeError('%s: %s must be a tensor [B,1,H,W], got %s' % (
+            what, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    return int(t.shape[0]), int(t.shape[2]), int(t.shape[3])
+
+
+def _camera_shapes(B, per):
+    return ((B, 1, 1, 3, 3), (B, 3, 3), (B, 9)) if per == 9 else ((B, 1, 1, 1, 3), (B, 3))
+
+
+def _camera_specs(what, cams, B):
+    """The eight camera tensors as specs for _images: each [B,1,1,3,3] / [B,1,1,1,3] or flat, for exactly B images."""
     for k in CAM_KEYS:
-        t = _dev32(cams[k], k)
-        keep.append(t)
+        if k not in cams:
+            raise RuntimeError('%s: cams must hold %s' % (what, ', '.join(CAM_KEYS)))
+    return [(k, cams[k], _camera_shapes(B, 3 if k.startswith('t_') else 9)) for k in CAM_KEYS]
+
+
+def _camera_struct(tensors):
+    st = _lib.Cameras()
+    for k, t in zip(CAM_KEYS, tensors):
         setattr(st, k, t.data_ptr())
-    return st, keep
+    return st
+
+
+def pack_cameras(cams, B=None, what='pack_cameras', dev=None):
+    """dict of the eight camera tensors ([B,1,1,3,3] / [B,1,1,1,3] or flat: [B,3,3], [B,9] / [B,3])
+    -> (ctypes struct, list of tensors kept alive).  With B, each must be one of these shapes for exactly B images, on `dev`
+    where that is given."""
+    if B is not None:
+        keep = _images(what, _camera_specs(what, cams, B), dev)
+    else:
+        keep = [_dev32(cams[k], k) for k in CAM_KEYS]
+    return _camera_struct(keep), keep
 
 
 def warp_cfg(B, H, W, midas_mask=True, crit_l2=False, disp_mode=1, loss_on_sf=False, flow_mul=1.0, disp_mul=1.0):
@@ -180,9 +235,9 @@ def warp_cfg(B, H, W, midas_mask=True, crit_l2=False, disp_mode=1, loss_on_sf=Fa
 
 def unproject(depth, R, t, K_inv, planar=True, out=None):
     """depth [B,1,H,W] -> world points, [B,3,H,W] (planar) or [B,H,W,1,3]; out: optional destination of that shape."""
-    depth = _dev32(depth, 'depth')
-    R, t, K_inv = _dev32(R, 'R'), _dev32(t, 't'), _dev32(K_inv, 'K_inv')
-    B, _, H, W = depth.shape
+    B, H, W = _image_size('unproject', 'depth', depth)
+    depth, R, t, K_inv = _images('unproject', [('depth', depth, ((B, 1, H, W),)), ('R', R, _camera_shapes(B, 9)),
+                                               ('t', t, _camera_shapes(B, 3)), ('K_inv', K_inv, _camera_shapes(B, 9))])
     shape = (B, 3, H, W) if planar else (B, H, W, 1, 3)
     if out is None:
         out = torch.empty(shape, device=depth.device, dtype=torch.float32)
@@ -196,17 +251,23 @@ def unproject(depth, R, t, K_inv, planar=True, out=None):
 
 def unproject_backward(g_points, planar, R, K_inv, scale=None, out=None, accumulate=False):
     """g_depth (+)= scale * ((g_points @ R^T) . ray);  scale: 1-element GPU tensor or None."""
-    g_points = _dev32(g_points, 'g_points')
-    R, K_inv = _dev32(R, 'R'), _dev32(K_inv, 'K_inv')
+    what = 'unproject_backward'
+    if not torch.is_tensor(g_points) or g_points.dim() < 4 or g_points.numel() == 0:
+        raise RuntimeError('%s: g_points must be a tensor [B,3,H,W] (planar) or [B,H,W,3] / [B,H,W,1,3], got %s' % (
+            what, tuple(g_points.shape) if torch.is_tensor(g_points) else type(g_points).__name__))
     if planar:
-        B, _, H, W = g_points.shape
+        B, H, W = int(g_points.shape[0]), int(g_points.shape[2]), int(g_points.shape[3])
     else:
-        B, H, W = g_points.shape[:3]
+        B, H, W = (int(v) for v in g_points.shape[:3])
+    g_points, R, K_inv, scale = _images(what, [
+        ('g_points', g_points, ((B, 3, H, W),) if planar else ((B, H, W, 3), (B, H, W, 1, 3))),
+        ('R', R, _camera_shapes(B, 9)), ('K_inv', K_inv, _camera_shapes(B, 9)), ('scale', scale, ((1,), ()))])
     if out is None:
         if accumulate:
             raise RuntimeError('accumulate=True needs an output tensor')
         out = torch.empty((B, 1, H, W), device=g_points.device, dtype=torch.float32)
-    out = _dev32(out, 'g_depth')
+    else:       # written in place: it is exactly this already, or refused (a copy would take the result with it)
+        _out_ok(what, 'out', out, (B, 1, H, W), torch.float32, g_points.device, 'g_points')
     lib = _lib.load()
     _lib.check(lib.dvd_unproject_bwd(_p(g_points), int(planar), _p(R), _p(K_inv), _p(scale), _p(out),
                                      int(bool(accumulate)), B, H, W, _stream()), 'dvd_unproject_bwd')
@@ -1591,21 +1652,34 @@ _SURFACE_SHAPES = {'global_p1': 3, 'warped_global_p2': 3, 'sf_by_depth': 3, 'p1_
                    'staticflow_1_2': 2, 'dflow_1_2': 2, 'depth_image_1_2': 1, 'depth_warp_1_2': 1}
 
 
+def _surface_shape(k, B, H, W):
+    c = _SURFACE_SHAPES[k]
+    return (B, H, W, 1, 3) if c == 3 else ((B, H, W, 2) if c == 2 else (B, 1, H, W))
+
+
+def _surface_inputs(what, depth_1, depth_2, flow_1_2, sflow_1_2, cams, more=()):
+    """The inputs the surface kernel and its backward share, checked against the B, H, W of depth_1 -> (B, H, W, the tensors,
+    the camera struct, what to keep alive); `more`: further (name, tensor, shapes(B, H, W)) of the same call."""
+    B, H, W = _image_size(what, 'depth_1', depth_1)
+    ts = _images(what, [('depth_1', depth_1, ((B, 1, H, W),)), ('depth_2', depth_2, ((B, 1, H, W),)),
+                        ('flow_1_2', flow_1_2, ((B, H, W, 2),)), ('sflow_1_2', sflow_1_2, ((B, H, W, 1, 3),))] +
+                 [(name, t, shapes(B, H, W)) for name, t, shapes in more] + _camera_specs(what, cams, B))
+    keep = ts[-len(CAM_KEYS):]
+    return B, H, W, ts[:-len(CAM_KEYS)], _camera_struct(keep), keep
+
+
 def warp_surfaces(depth_1, depth_2, flow_1_2, cams, sflow_1_2=None, want=_lib.SURFACE_KEYS):
     """The per-pixel surfaces of flow_by_depth / scene_flow_projection_slack (forward values).
     Returns a dict name -> tensor: 3-vectors [B,H,W,1,3], flows [B,H,W,2], depths [B,1,H,W]."""
-    depth_1, depth_2, flow_1_2 = _dev32(depth_1, 'depth_1'), _dev32(depth_2, 'depth_2'), _dev32(flow_1_2, 'flow_1_2')
-    B, _, H, W = depth_1.shape
-    if sflow_1_2 is not None:
-        sflow_1_2 = _dev32(sflow_1_2, 'sflow_1_2')
-        if sflow_1_2.numel() != 3 * B * H * W:
-            raise RuntimeError('sflow_1_2 must be [B,H,W,1,3]')
-    cst, keep = pack_cameras(cams)
+    want = tuple(want)
+    for k in want:
+        if k not in _SURFACE_SHAPES:
+            raise RuntimeError('warp_surfaces: want holds %r, the surfaces are %s' % (k, ', '.join(_lib.SURFACE_KEYS)))
+    B, H, W, (depth_1, depth_2, flow_1_2, sflow_1_2), cst, keep = _surface_inputs('warp_surfaces', depth_1, depth_2, flow_1_2,
+                                                                                  sflow_1_2, cams)
     out, st = {}, _lib.Surfaces()
     for k in want:
-        c = _SURFACE_SHAPES[k]
-        shape = (B, H, W, 1, 3) if c == 3 else ((B, H, W, 2) if c == 2 else (B, 1, H, W))
-        out[k] = torch.empty(shape, device=depth_1.device, dtype=torch.float32)
+        out[k] = torch.empty(_surface_shape(k, B, H, W), device=depth_1.device, dtype=torch.float32)
         setattr(st, k, out[k].data_ptr())
     lib = _lib.load()
     _lib.check(lib.dvd_warp_surfaces(_p(depth_1), _p(depth_2), _p(flow_1_2), _p(sflow_1_2), ctypes.byref(cst),
@@ -1617,20 +1691,18 @@ def warp_surfaces(depth_1, depth_2, flow_1_2, cams, sflow_1_2=None, want=_lib.SU
 def warp_surfaces_backward(depth_1, depth_2, flow_1_2, cams, grads, sflow_1_2=None, want_sflow_grad=False):
     """VJP of warp_surfaces: `grads` maps surface name -> upstream gradient (same layout as the surface; missing / None =
     no gradient).  Returns (g_depth_1, g_depth_2, g_sflow_1_2 | None)."""
-    depth_1, depth_2, flow_1_2 = _dev32(depth_1, 'depth_1'), _dev32(depth_2, 'depth_2'), _dev32(flow_1_2, 'flow_1_2')
-    B, _, H, W = depth_1.shape
-    if sflow_1_2 is not None:
-        sflow_1_2 = _dev32(sflow_1_2, 'sflow_1_2')
-    cst, keep = pack_cameras(cams)
+    what = 'warp_surfaces_backward'
+    for k in grads:
+        if k not in _SURFACE_SHAPES:
+            raise RuntimeError('%s: grads holds %r, the surfaces are %s' % (what, k, ', '.join(_lib.SURFACE_KEYS)))
+    names = [k for k in _lib.SURFACE_KEYS if grads.get(k) is not None]
+    B, H, W, ts, cst, keep = _surface_inputs(what, depth_1, depth_2, flow_1_2, sflow_1_2, cams, [
+        ('the gradient of ' + k, grads[k], lambda B, H, W, k=k: (_surface_shape(k, B, H, W),)) for k in names])
+    depth_1, depth_2, flow_1_2, sflow_1_2 = ts[:4]
     st = _lib.Surfaces()
-    for k in _lib.SURFACE_KEYS:
-        g = grads.get(k)
-        if g is not None:
-            g = _dev32(g, 'grad of ' + k)
-            if g.numel() != _SURFACE_SHAPES[k] * B * H * W:
-                raise RuntimeError('gradient of %s has the wrong size' % k)
-            keep.append(g)
-            setattr(st, k, g.data_ptr())
+    for k, g in zip(names, ts[4:]):
+        keep.append(g)
+        setattr(st, k, g.data_ptr())
     g1, g2 = torch.empty_like(depth_1), torch.empty_like(depth_2)
     gs = torch.empty(B, H, W, 1, 3, device=depth_1.device, dtype=torch.float32) if want_sflow_grad else None
     _lib.check(_lib.load().dvd_warp_surfaces_bwd(_p(depth_1), _p(depth_2), _p(flow_1_2), _p(sflow_1_2), ctypes.byref(cst),
@@ -1640,9 +1712,17 @@ def warp_surfaces_backward(depth_1, depth_2, flow_1_2, cams, grads, sflow_1_2=No
     return g1, g2, gs
 
 
+def _warp_args(what, name, buffer, flow_1_2):
+    if not torch.is_tensor(buffer) or buffer.dim() != 4 or buffer.numel() == 0:
+        raise RuntimeError('%s: %s must be a tensor [B,C,H,W], got %s' % (
+            what, name, tuple(buffer.shape) if torch.is_tensor(buffer) else type(buffer).__name__))
+    B, C, H, W = (int(v) for v in buffer.shape)
+    buffer, flow_1_2 = _images(what, [(name, buffer, ((B, C, H, W),)), ('flow_1_2', flow_1_2, ((B, H, W, 2),))])
+    return buffer, flow_1_2, B, C, H, W
+
+
 def flow_warp(buffer, flow_1_2):
-    buffer, flow_1_2 = _dev32(buffer, 'buffer'), _dev32(flow_1_2, 'flow_1_2')
-    B, C, H, W = buffer.shape
+    buffer, flow_1_2, B, C, H, W = _warp_args('flow_warp', 'buffer', buffer, flow_1_2)
     out = torch.empty_like(buffer)
     lib = _lib.load()
     _lib.check(lib.dvd_flow_warp_fwd(_p(buffer), _p(flow_1_2), _p(out), B, C, H, W, _stream()), 'dvd_flow_warp_fwd')
@@ -1650,8 +1730,7 @@ def flow_warp(buffer, flow_1_2):
 
 
 def flow_warp_backward(g_out, flow_1_2):
-    g_out, flow_1_2 = _dev32(g_out, 'g_out'), _dev32(flow_1_2, 'flow_1_2')
-    B, C, H, W = g_out.shape
+    g_out, flow_1_2, B, C, H, W = _warp_args('flow_warp_backward', 'g_out', g_out, flow_1_2)
     g = torch.empty_like(g_out)
     lib = _lib.load()
     _lib.check(lib.dvd_flow_warp_bwd(_p(g_out), _p(flow_1_2), _p(g), B, C, H, W, _stream()), 'dvd_flow_warp_bwd')

@@ -23,10 +23,11 @@ BEHIND_CAMERA_Z = 1e-3   # losses/scene_flow_projection.py:144,253,257,261
 DIV_EPS = 1e-8           # :142,250-252
 
 
-def pixel_grid(H, W, device=None):
-    """[1,H,W,1,3] homogeneous pixel coordinates (x, y, 1)."""
-    ys, xs = torch.meshgrid(torch.arange(H).float(), torch.arange(W).float(), indexing='ij')
-    g = torch.ones([1, H, W, 1, 3])
+def pixel_grid(H, W, device=None, dtype=torch.float32):
+    """[1,H,W,1,3] homogeneous pixel coordinates (x, y, 1); dtype=torch.float64 makes every function below that builds its
+    grid from depth_1 a float64 specification (the integers are exact in either)."""
+    ys, xs = torch.meshgrid(torch.arange(H).to(dtype), torch.arange(W).to(dtype), indexing='ij')
+    g = torch.ones([1, H, W, 1, 3], dtype=dtype)
     g[0, :, :, 0, 0] = xs
     g[0, :, :, 0, 1] = ys
     return g if device is None else g.to(device)
@@ -56,7 +57,7 @@ def camera_points(depth, grid, K_inv):
 
 def unproject(depth_1, R_1, t_1, K_inv, grid=None):
     B, _, H, W = depth_1.shape
-    grid = pixel_grid(H, W, depth_1.device) if grid is None else grid
+    grid = pixel_grid(H, W, depth_1.device, depth_1.dtype) if grid is None else grid
     return torch.matmul(camera_points(depth_1, grid, K_inv), R_1) + t_1
 
 
@@ -78,7 +79,7 @@ def _project_with_fallback(p_cam, K, own_xy):
 def static_reprojection(depth_1, depth_2, flow_1_2, R_1, R_2, R_1_T, R_2_T, t_1, t_2, K, K_inv):
     """flow_by_depth.forward: rigid-scene flow + scene flow implied by depth."""
     B, _, H, W = depth_1.shape
-    grid = pixel_grid(H, W, depth_1.device)
+    grid = pixel_grid(H, W, depth_1.device, depth_1.dtype)
     own = grid.expand([B, H, W, 1, 3])
     pc1 = camera_points(depth_1, grid, K_inv)
     pc2 = camera_points(depth_2, grid, K_inv)
@@ -98,7 +99,7 @@ def dynamic_reprojection(depth_1, depth_2, flow_1_2, flow_2_1, R_1, R_2, R_1_T, 
                          t_1, t_2, K, K_inv, sflow_1_2, sflow_2_1):
     """scene_flow_projection_slack.forward (all ten returned surfaces)."""
     B, _, H, W = depth_1.shape
-    grid = pixel_grid(H, W, depth_1.device)
+    grid = pixel_grid(H, W, depth_1.device, depth_1.dtype)
     own = grid.expand([B, H, W, 1, 3])
     own_xy = own[..., :-1]
     pc1 = camera_points(depth_1, grid, K_inv)
