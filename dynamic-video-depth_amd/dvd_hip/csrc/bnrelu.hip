@@ -142,7 +142,13 @@ __global__ __launch_bounds__(256) void bnrelu_bwd_kernel(const T* __restrict__ g
       gmax = amax_acc(gmax, g);
       if (x) sgx = __builtin_fmaf(g, ldf(x + base + i) - mu, sgx);
       if (gres) stf(gres + base + i, g);
-      if (gx) stf(gx + base + i, g * s);
+      if (gx) {
+        // the product rounded to fp32 and THEN stored, as the 16-byte loop and the fp32 storage have it: left to the
+        // compiler, product and fp16 store become one v_fma_mixlo_f16, which rounds once (one fp16 ulp apart on ties)
+        float gs = g * s;
+        asm volatile("" : "+v"(gs));
+        stf(gx + base + i, gs);
+      }
     }
   }
   }

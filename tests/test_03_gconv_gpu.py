@@ -1,7 +1,8 @@
 """Grouped 3x3 convolution kernels (8 channels per group) against torch's fp32 CPU
 convolution: forward, backward-data, backward-weight.  Tolerance: rtol 1e-5 of max|.|
 forward / backward-data (72-term fp32 dot products in a different order), 2e-5 for the weight
-gradient (sums over N*H*W pixels)."""
+gradient (sums over N*H*W pixels).  A smoke-level comparison at six shapes in a max-norm: the plain kernels are held to float64
+element by element, per tile and staging path and with fp16 storage, by tests/test_68_layer_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

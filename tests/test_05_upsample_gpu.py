@@ -1,6 +1,8 @@
 """Bilinear x2 up-sampling kernels (both align_corners flavours of the MiDaS decoder) against
 torch's fp32 CPU F.interpolate: forward and the gradient w.r.t. the input.  Tolerance 2e-6 of
-max|.| (same source-index and weight formulas; ATen may contract the blend into FMAs)."""
+max|.| (same source-index and weight formulas; ATen may contract the blend into FMAs).  Every even-width case has H >= 16
+and W >= 4, and only x2 is reached: maps of one to three rows, the forward's gathers, the 8-candidate backward and the refusal
+of factors above 3 are in tests/test_68_layer_kernels_gpu.py, against float64."""
 import numpy as np
 import pytest
 import torch
