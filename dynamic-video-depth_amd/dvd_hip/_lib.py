@@ -255,6 +255,8 @@ SIGNATURES = {
                           [c_void_p]),
     'dvd_point_score': (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_void_p,
                                 c_int, c_int, c_void_p]),
+    # stored flows chained into the gaps nobody computed (csrc/flow_chain.hip; an addition within ABI 8)
+    'dvd_flow_chain': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p] + [c_int] * 4 + [c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

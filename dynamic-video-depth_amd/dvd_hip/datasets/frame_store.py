@@ -68,18 +68,19 @@ class Catalogue(object):
     def n_frames(self):
         return len(self.frame_files)
 
-    def order(self, epoch):
-        """The epoch's permutation of the pair list: `Dataset.pair_order` of the same (--manual_seed, epoch)."""
-        return epoch_pair_order(len(self.pairs), self.manual_seed, epoch)
+    def order(self, epoch, n_pairs=None):
+        """The epoch's permutation of the pair list: `Dataset.pair_order` of the same (--manual_seed, epoch).  n_pairs: of its
+        first n_pairs entries only (a loader made before FrameStore.add_pairs; None: all)."""
+        return epoch_pair_order(len(self.pairs) if n_pairs is None else int(n_pairs), self.manual_seed, epoch)
 
-    def n_steps(self, pairs_per_step):
-        return -(-len(self.pairs) // int(pairs_per_step))
+    def n_steps(self, pairs_per_step, n_pairs=None):
+        return -(-(len(self.pairs) if n_pairs is None else int(n_pairs)) // int(pairs_per_step))
 
-    def steps(self, pairs_per_step, epoch, rank=0, world=1, group_gaps=False):
+    def steps(self, pairs_per_step, epoch, rank=0, world=1, group_gaps=False, n_pairs=None):
         """Per optimisation step of `epoch`, the list of (f_1, f_2, pair) index triples of `rank`: step i holds the pairs
         order[i * N : (i + 1) * N] (the last step may be short), a rank takes parallel.shard_range of them, and
-        group_gaps=True sorts what the rank holds by frame gap, stable (the order the model works in)."""
-        N, order = int(pairs_per_step), self.order(epoch)
+        group_gaps=True sorts what the rank holds by frame gap, stable (the order the model works in).  n_pairs as in `order`."""
+        N, order = int(pairs_per_step), self.order(epoch, n_pairs)
         if N <= 0:
             raise ValueError('pairs_per_step must be positive')
         out = []
@@ -209,7 +210,7 @@ class FrameStore(object):
         if self.device.type != 'cuda':
             raise RuntimeError('FrameStore lives on a GPU (dvd_hip has no CPU path), got %s' % self.device)
         N, P = cat.n_frames, len(cat.pairs)
-        self.H, self.W, self.has_seg = int(H), int(W), bool(has_seg)
+        self.H, self.W, self.has_seg, self.budget_gb = int(H), int(W), bool(has_seg), budget_gb
         per_frame = (5 + (1 if self.has_seg else 0)) * H * W * 4 + (4 * 9 + 3 + 16 + 2) * 4
         per_pair = 4 * H * W * 4 + 2 * H * W
         self.nbytes = N * per_frame + P * per_pair
@@ -241,6 +242,44 @@ class FrameStore(object):
 
     def loader(self, pairs_per_step, group_gaps=False, rank=0, world=1, repeat=1):
         return StoreLoader(self, pairs_per_step, group_gaps, rank, world, repeat)
+
+    def add_pairs(self, chained):
+        """Appends flow pairs computed on the device -- preprocess.chain_flows' result: 'pairs' [(f_1, f_2)] and flow_1_2,
+        flow_2_1 [P',H,W,2] fp32, mask_1, mask_2 [P',H,W] uint8 on the store's device -- to the store's four pair tensors and to
+        cat.pairs; cat.pair_files gains a None per pair (no file holds them) and cat.gaps the new gaps.  nbytes grows and the
+        budget check is repeated; a pair the store holds already is refused.  Training, preprocess.triangulate_depth and
+        Model.evaluate then see the new pairs through cat.pairs like stored ones.  Call it BEFORE store.loader(...): a loader
+        made earlier keeps drawing from the pairs it saw when it was made."""
+        cat, H, W, dev = self.cat, self.H, self.W, self.flow_1_2.device          # (with its index, which 'cuda' alone lacks)
+        try:
+            pairs = [(int(a), int(b)) for a, b in chained['pairs']]
+            tensors = [chained[k] for k in ('flow_1_2', 'flow_2_1', 'mask_1', 'mask_2')]
+        except (KeyError, TypeError, ValueError):
+            raise RuntimeError('add_pairs: expected a dict of pairs [(f_1, f_2)], flow_1_2, flow_2_1, mask_1 and mask_2')
+        n = len(pairs)
+        if n == 0:
+            raise RuntimeError('add_pairs: no pair to add')
+        have = set(cat.pairs)
+        for a, b in pairs:
+            if not 0 <= a < b < cat.n_frames:
+                raise RuntimeError('add_pairs: the pair (%d, %d) is no forward pair of a video of %d frames' % (a, b, cat.n_frames))
+            if (a, b) in have:
+                raise RuntimeError('add_pairs: the store holds the pair (%d, %d) already' % (a, b))
+            have.add((a, b))
+        for k, t in zip(('flow_1_2', 'flow_2_1', 'mask_1', 'mask_2'), tensors):
+            shape, dtype = ((n, H, W, 2), torch.float32) if k.startswith('flow') else ((n, H, W), torch.uint8)
+            if not (torch.is_tensor(t) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+                raise RuntimeError('add_pairs: %s must be a %s tensor %s on %s' % (k, dtype, list(shape), dev))
+        nbytes = self.nbytes + n * (4 * H * W * 4 + 2 * H * W)
+        if self.budget_gb is not None and nbytes > float(self.budget_gb) * 2 ** 30:
+            raise RuntimeError('frame store: with %d more pairs of %d x %d it needs %.2f GB, more than --store_gb %.2f' % (
+                n, H, W, nbytes / 2 ** 30, float(self.budget_gb)))
+        self.flow_1_2, self.flow_2_1, self.mask_1, self.mask_2 = (
+            torch.cat([getattr(self, k), t], 0) for k, t in zip(('flow_1_2', 'flow_2_1', 'mask_1', 'mask_2'), tensors))
+        self.nbytes = nbytes
+        cat.pairs += pairs
+        cat.pair_files += [None] * n
+        cat.gaps += sorted(set(b - a for a, b in pairs) - set(cat.gaps))
 
     def frames(self, batch_size):
         """The validation / test view: what DataLoader(Dataset(mode='vali'), batch_size=b) yields, on the device.  Images,
@@ -282,6 +321,7 @@ class StoreLoader(object):
         self.rank, self.world, self.repeat = int(rank), int(world), max(1, int(repeat))
         if self.pairs_per_step <= 0:
             raise ValueError('pairs_per_step must be positive')
+        self.n_pairs = len(store.cat.pairs)        # the pairs it draws from: those the store held when it was made
         self.epoch = 0
         self._uploaded = None         # (epoch, steps, host index [3, total], device index, device frame ids [2, total])
         self._out = {}                # pairs in a step -> output tensors
@@ -293,12 +333,12 @@ class StoreLoader(object):
         self.epoch += 1
 
     def __len__(self):
-        return self.store.cat.n_steps(self.pairs_per_step) * self.repeat
+        return self.store.cat.n_steps(self.pairs_per_step, self.n_pairs) * self.repeat
 
     def _epoch_tables(self):
         if self._uploaded is None or self._uploaded[0] != self.epoch:
-            steps = self.store.cat.steps(self.pairs_per_step, self.epoch, self.rank, self.world, self.group_gaps)
-            whole = self.store.cat.steps(self.pairs_per_step, self.epoch)
+            steps = self.store.cat.steps(self.pairs_per_step, self.epoch, self.rank, self.world, self.group_gaps, self.n_pairs)
+            whole = self.store.cat.steps(self.pairs_per_step, self.epoch, n_pairs=self.n_pairs)
             empty = [i for i, s in enumerate(steps) if len(s) == 0]
             if empty:
                 raise RuntimeError('frame store: rank %d of %d holds no pair in step %d of epoch %d, a step of %d pair(s); every '

@@ -472,6 +472,68 @@ def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='m
     return res
 
 
+CHAIN_MAX_LINKS = 32        # kChainMaxLinks of csrc/flow_chain.hip
+
+
+def flow_chain(flow_1_2, flow_2_1, mask_1, mask_2, links, out=None):
+    """Stored flows followed one after another (dvd_flow_chain, csrc/flow_chain.hip) -> {'flow': [L,B,H,W,2] fp32, 'broken':
+    [L,B,H,W] uint8}: row k of chain b holds, per pixel x0, the position after links 0 .. k minus x0, and 0 while the chain is
+    whole there, else 1 + the index of the link that broke (a position outside the image, a masked tap, a step that is not
+    finite); the flow then stays at its last value.  Rows past a chain's end are 0 and 255.
+      flow_1_2, flow_2_1   [P,H,W,2] fp32;  mask_1, mask_2  [P,H,W] uint8, 0 = valid  (a FrameStore's tensors)
+      links    [B,L,2] integral rows (pair, dir), L <= 32, pair = -1 ends a chain: a host array / sequence / CPU tensor
+               (preprocess.chain_plan builds it; uploaded here).  dir 0 follows flow_1_2 with mask_2, dir 1 flow_2_1 with mask_1
+      out      optional dict of preallocated outputs; out['flow'] may have a row stride above B * H * W * 2 (a slice of a larger
+               tensor along dimension 1), everything within a row contiguous
+    include/dvd_hip.h has the sampling rule.  Everything is checked on the host before the launch, the table goes up in one
+    pinned upload, and nothing synchronises with the device."""
+    what = 'flow_chain'
+    # the host data first: a bad table is refused before a tensor is looked at
+    ln = _host_ids(what, 'links (rows of pair, dir)', links, (None, None, 2), floats=False)
+    B, L = int(ln.shape[0]), int(ln.shape[1])
+    if not 1 <= L <= CHAIN_MAX_LINKS:
+        raise RuntimeError('%s: links holds L=%d links per chain, 1 .. %d are possible' % (what, L, CHAIN_MAX_LINKS))
+    if not 1 <= B <= 65535:
+        raise RuntimeError('%s: links must hold 1 .. 65535 chains per launch, got %d' % (what, B))
+    ended = ln[..., 0] == -1
+    n_live = np.where(ended.any(1), ended.argmax(1), L)                 # links before the row's first -1
+    live = np.arange(L)[None, :] < n_live[:, None]
+    f12 = _dev32(flow_1_2, 'flow_1_2')
+    dev = f12.device
+    if f12 is not flow_1_2 or f12.dim() != 4 or f12.shape[3] != 2 or f12.shape[0] < 1:
+        raise RuntimeError('%s: flow_1_2 must be contiguous [P,H,W,2], got %s' % (what, tuple(f12.shape)))
+    P, H, W = (int(v) for v in f12.shape[:3])
+    if H < 2 or W < 2 or H * W >= 1 << 30:
+        raise RuntimeError('%s: images of %d x %d; the sampling rule needs H, W >= 2, and H * W must stay below 2^30' % (what, H, W))
+    _out_ok(what, 'flow_2_1', flow_2_1, f12.shape, torch.float32, dev, 'flow_1_2')
+    if mask_1 is None or mask_2 is None:
+        raise RuntimeError('%s: mask_1 and mask_2 are required, got None for %s' % (what, 'mask_1' if mask_1 is None else 'mask_2'))
+    mask_1 = _dev_u8(what, 'mask_1', mask_1, (P, H, W), dev, copy=False)
+    mask_2 = _dev_u8(what, 'mask_2', mask_2, (P, H, W), dev, copy=False)
+    if live.any() and (int(ln[..., 0][live].min()) < 0 or int(ln[..., 0][live].max()) >= P):
+        raise RuntimeError('%s: links names pairs in [%d, %d], outside -1 (the end) .. %d' % (
+            what, int(ln[..., 0][live].min()), int(ln[..., 0][live].max()), P - 1))
+    if live.any() and not np.isin(ln[..., 1][live], (0, 1)).all():
+        raise RuntimeError('%s: the dir column of links must be 0 (flow_1_2) or 1 (flow_2_1)' % what)
+    row = B * H * W * 2
+    flow = out.get('flow') if out is not None else None
+    if flow is None:
+        flow = torch.empty((L, B, H, W, 2), device=dev, dtype=torch.float32)
+    elif not (torch.is_tensor(flow) and flow.device == dev and flow.dtype == torch.float32 and tuple(flow.shape) == (L, B, H, W, 2)
+              and flow[0].is_contiguous() and (L == 1 or (flow.stride(0) >= row and flow.stride(0) % 2 == 0))
+              and flow.data_ptr() % 8 == 0):
+        raise RuntimeError("%s: out['flow'] must be a float32 tensor %s on the device of the flows, contiguous within a row, the "
+                           "rows an even stride of at least %d apart" % (what, [L, B, H, W, 2], row))
+    res = {'flow': flow}
+    res.update(_outputs(what, out, {'broken': ((L, B, H, W), torch.uint8)}, dev, 'the flows'))
+    stride = int(flow.stride(0)) if L > 1 else row
+    # ONE upload from pinned memory, enqueued on the current stream: a copy from pageable memory would make the host wait
+    table = torch.from_numpy(np.ascontiguousarray(ln.astype(np.int32))).pin_memory().to(dev, non_blocking=True)
+    _lib.check(_lib.load().dvd_flow_chain(_p(f12), _p(flow_2_1), _p(mask_1), _p(mask_2), P, _p(table), int(n_live.sum()),
+                                          _p(flow), stride, _p(res['broken']), L, B, H, W, _stream()), 'dvd_flow_chain')
+    return res
+
+
 def invert_update(p, sf, y_old, out=None, resid=None):
     """One fixed-point update of the inverse Euler step (dvd_track_invert_update, csrc/invert.hip): out = p - sf, and resid[b]
     = max(resid[b], max |out - y_old| of image b) -- the caller zeroes resid; a NaN difference counts as +Inf.
@@ -1304,7 +1366,7 @@ BYTE_CLASS_KERNELS = {
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
                                                    'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
                                                    'depth_score_kernel', 'track_filter_kernel', 'triangulate_kernel', 'fill_pull_kernel',
-                                                   'fill_mid_kernel', 'fill_push_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'fill_mid_kernel', 'fill_push_kernel', 'flow_chain_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

@@ -133,6 +133,115 @@ def triangulate_depth(store, frames=None, gaps=None, mode='median', epi_tol=1.0,
     return res
 
 
+def chain_plan(pairs, n_frames, gaps, base=None):
+    """The chain tables of ops.flow_chain that reach the frame gaps `gaps` from the stored `pairs` (host only)
+    -> (new_pairs, links_fwd, links_bwd).  For every requested gap g, and every a with a + g < n_frames whose pair (a, a + g) is
+    not stored already, two chains:
+      forward   a -> a + g, greedy: at frame f the largest stored gap s <= the frames that remain for which (f, f + s) is
+                stored, as the row (its pair index, 0)
+      backward  a + g -> a: the same pairs from the far end, as rows (pair index, 1)
+    new_pairs lists the (a, a + g), gaps ascending, a ascending; links_fwd and links_bwd are int32 [P', L, 2], L the longest
+    chain, padded with -1.  base: the stored gaps a chain may use (base=[1] chains gap-1 flows only; None: all of them).  A
+    ValueError names the first pair that the greedy walk cannot reach (it does not back up: gap 7 from base=[2, 3] is stuck after
+    3 + 3 although 3 + 2 + 2 exists), or that would need more than ops.CHAIN_MAX_LINKS links."""
+    import numpy as np
+    from . import ops
+    n_frames = int(n_frames)
+    try:
+        want = sorted(set(int(g) for g in gaps))
+        ok = all(int(g) == g and not isinstance(g, bool) for g in gaps)
+    except (TypeError, ValueError):
+        want, ok = [], False
+    if not ok or not want or want[0] < 1:
+        raise ValueError('chain_plan: gaps must be positive frame distances, got %r' % (gaps,))
+    allow = None if base is None else set(int(g) for g in base)
+    if allow is not None and (not allow or min(allow) < 1):
+        raise ValueError('chain_plan: base must be positive frame distances, got %r' % (base,))
+    at, stored = {}, set()
+    for j, (a, b) in enumerate(pairs):
+        a, b = int(a), int(b)
+        if not 0 <= a < b < n_frames:
+            raise ValueError('chain_plan: pair %d is (%d, %d); stored pairs run forwards in a video of %d frames' % (j, a, b, n_frames))
+        at.setdefault((a, b), j)
+        if allow is None or b - a in allow:
+            stored.add(b - a)
+    steps = sorted(stored, reverse=True)
+    new_pairs, chains = [], []
+    for g in want:
+        for a in range(n_frames - g):
+            if (a, a + g) in at:
+                continue
+            f, chain = a, []
+            while f < a + g:
+                s = next((s for s in steps if s <= a + g - f and (f, f + s) in at), None)
+                if s is None:
+                    raise ValueError('chain_plan: the pair (%d, %d) cannot be reached by the greedy walk (the largest stored gap%s that fits, '
+                                     'at every frame): it is stuck at frame %d, %d frame(s) short, with no stored flow that fits' % (
+                                         a, a + g, '' if allow is None else ' among %s' % sorted(allow), f, a + g - f))
+                chain.append(at[(f, f + s)])
+                f += s
+                if len(chain) > ops.CHAIN_MAX_LINKS:
+                    raise ValueError('chain_plan: the pair (%d, %d) needs more than %d links' % (a, a + g, ops.CHAIN_MAX_LINKS))
+            new_pairs.append((a, a + g))
+            chains.append(chain)
+    L = max([len(c) for c in chains] + [1])
+    fwd = np.full((len(chains), L, 2), -1, dtype=np.int32)
+    bwd = np.full((len(chains), L, 2), -1, dtype=np.int32)
+    for i, c in enumerate(chains):
+        fwd[i, :len(c), 0], fwd[i, :len(c), 1] = c, 0
+        bwd[i, :len(c), 0], bwd[i, :len(c), 1] = c[::-1], 1
+    return new_pairs, fwd, bwd
+
+
+CHAIN_SCRATCH_BYTES = 1 << 28       # chain_flows' default chunk keeps the rows of a launch below this
+
+
+def chain_flows(store, gaps, base=None, chunk=None):
+    """The flow pairs of the frame gaps `gaps` that a FrameStore lacks, chained on the device from the pairs it holds
+    (chain_plan over store.cat.pairs, ops.flow_chain) -> dict on the device, ready for FrameStore.add_pairs:
+      pairs                the new (f_1, f_2), gaps ascending, f_1 ascending (a host list)
+      flow_1_2, flow_2_1   [P',H,W,2]: the forward chain f_1 -> f_2 and the backward chain f_2 -> f_1 after their last link
+      broken_1, broken_2   uint8 [P',H,W]: 0, or 1 + the link at which the backward / the forward chain broke (the sides are the
+                           masks': mask_2 belongs to flow_1_2, mask_1 to flow_2_1)
+      mask_1, mask_2       uint8 [P',H,W], 1 = not to be used: the reference's forward / backward consistency rule on the composed
+                           pair (flow_consistency_masks), or the chain broke
+      n_links              int32 [P']: links per chain
+    base: the stored gaps to chain from (None: all; [1]: gap-1 flows only).  chunk: chains per launch (None: as many as keep a
+    launch's rows within CHAIN_SCRATCH_BYTES); it does not change a bit."""
+    import numpy as np
+    from . import ops
+    if chunk is not None and (isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1):
+        raise ValueError('chain_flows: chunk must be a positive number of chains, got %r' % (chunk,))
+    pairs, fwd, bwd = chain_plan(store.cat.pairs, store.cat.n_frames, gaps, base)
+    if not pairs:
+        raise ValueError('chain_flows: the store holds every pair of the gaps %r already' % (gaps,))
+    n, L = fwd.shape[:2]
+    H, W, dev = store.H, store.W, store.device
+    if chunk is None:
+        chunk = max(1, CHAIN_SCRATCH_BYTES // (L * H * W * 9))
+    chunk = min(int(chunk), n, 65535)
+    n_links = (fwd[..., 0] >= 0).sum(1).astype(np.int64)
+    # the row of each chain's last link, and the chain's place in its launch: one pinned upload for all launches
+    pick = torch.from_numpy(np.stack([n_links - 1, np.arange(n) % chunk])).pin_memory().to(dev, non_blocking=True)
+    res = {'pairs': pairs, 'n_links': pick[0].to(torch.int32) + 1}
+    scratch = {'flow': torch.empty(L, chunk, H, W, 2, device=dev), 'broken': torch.empty(L, chunk, H, W, device=dev, dtype=torch.uint8)}
+    for links, flow_key, broken_key in ((fwd, 'flow_1_2', 'broken_2'), (bwd, 'flow_2_1', 'broken_1')):
+        res[flow_key] = torch.empty(n, H, W, 2, device=dev)
+        res[broken_key] = torch.empty(n, H, W, device=dev, dtype=torch.uint8)
+        for b0 in range(0, n, chunk):
+            b1 = min(b0 + chunk, n)
+            b = b1 - b0       # (a short last launch: the flow rows keep the scratch's stride, `broken` is the front of its memory)
+            out = ops.flow_chain(store.flow_1_2, store.flow_2_1, store.mask_1, store.mask_2, links[b0:b1],
+                                 out={'flow': scratch['flow'][:, :b], 'broken': scratch['broken'].view(-1)[:L * b * H * W].view(L, b, H, W)})
+            last, col = pick[0, b0:b1], pick[1, b0:b1]
+            res[flow_key][b0:b1] = out['flow'][last, col]
+            res[broken_key][b0:b1] = out['broken'][last, col]
+    m1, m2 = flow_consistency_masks(res['flow_1_2'], res['flow_2_1'])
+    res['mask_1'] = m1 | (res['broken_1'] != 0).to(torch.uint8)
+    res['mask_2'] = m2 | (res['broken_2'] != 0).to(torch.uint8)
+    return res
+
+
 def scale_poses(w2c, s):
     """World-to-camera matrices [N,4,4] -> camera-to-world fp32 [N,4,4] at the calibrated scale, the reference's three
     statements per frame (generate_frame_midas.py:180-183): `T[:3, 3] *= s`, `np.linalg.inv(T)`, `.astype(np.float32)`.  Host

@@ -1053,6 +1053,35 @@ int dvd_point_score(const float* uv, const unsigned char* visible, const int* ta
                     const unsigned char* gt_state, int N, float sx, float sy, const float* thr2, int shift, long long* sums,
                     int T1, int Q, dvd_stream_t stream);
 
+/* Stored optical flows chained into frame gaps nobody computed (an addition within ABI 8; csrc/flow_chain.hip, ops.flow_chain,
+ * preprocess.chain_flows): a gap-g flow is g gap-1 flows -- or fewer, longer stored ones -- followed one after another.
+ *   flow_1_2, flow_2_1   float [P, H, W, 2];  mask_1, mask_2  uint8 [P, H, W], 0 = valid  (a FrameStore's tensors)
+ *   links      DEVICE int [B, L, 2], rows (pair, dir), 1 <= L <= 32.  dir 0 follows flow_1_2[pair], whose validity is
+ *              mask_2[pair]; dir 1 follows flow_2_1[pair] with mask_1[pair] (dvd_triangulate's convention).  pair = -1 ends a
+ *              chain: every later link of that row is ignored.
+ *   live_links the number of links before the rows' ends.  The table is on the device, so the entry cannot count them: the value
+ *              only feeds dvd_byte_counters, the kernel never reads it, and the caller answers for it (ops.flow_chain counts
+ *              them on the host copy it uploads).
+ * One thread per pixel x0 = (u, v) of chain b walks the links in order from x_0 = x0.  Link k (0-based) at x_k = (px, py), every
+ * multiply and add a separate fp32 operation:
+ *   it breaks unless 0 <= px <= W-1 && 0 <= py <= H-1 (a NaN fails); a pair outside -1 .. P-1 breaks it and reads nothing
+ *   ix = floorf(px), iy = floorf(py), wx = px - ix, wy = py - iy; the taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) have
+ *   the weights (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy.  A tap whose weight is exactly 0 is neither read nor tested, which
+ *   holds a position on the last row or column inside the image.
+ *   it breaks if the link's mask is non-zero at any tap that is read
+ *   f = ((t00 * w00 + t10 * w10) + t01 * w01) + t11 * w11 per component; an unread tap contributes 0 * w, which is +0
+ *   x_{k+1} = x_k + f; it breaks if a component of x_{k+1} is a NaN or an Inf, so that no output ever is one
+ *   flow_out   float [L, B, H, W, 2], row k = x_{k+1} - x0; after a break the last value before it, (0, 0) if link 0 broke.
+ *              Rows are flow_stride floats apart (>= B * H * W * 2, even).
+ *   broken     uint8 [L, B, H, W]: 0 while the chain is whole, then 1 + the index of the link that broke, in all later rows
+ *   Rows past a chain's end are 0 in flow_out and 255 in broken.
+ * No atomics, one writer per element, plain vector stores: the same inputs give the same bits.  Grid (ceil(H W / 256), B).
+ * DVD_EINVAL before any HIP call: a null pointer, L outside 1..32, B outside 1..65535, H or W < 2, H * W >= 2^30, P < 1, a stride
+ * below B * H * W * 2 or odd, live_links outside 0 .. B * L, a misaligned pointer.  Bytes are counted under DVD_BYTES_GEOMETRY. */
+int dvd_flow_chain(const float* flow_1_2, const float* flow_2_1, const unsigned char* mask_1, const unsigned char* mask_2, int P,
+                   const int* links, long long live_links, float* flow_out, long long flow_stride, unsigned char* broken, int L,
+                   int B, int H, int W, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
