@@ -143,6 +143,7 @@ SIGNATURES = {
     'dvd_chansum': (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'dvd_xconv_fwd': (c_int, [c_void_p] * 6 + [ctypes.POINTER(BnParams), c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
     'dvd_xconv_select': (c_int, [c_int]),
+    'dvd_xconv_describe': (c_int, [c_int] * 10 + [c_void_p]),
     'dvd_xconv_pack_scaled': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                       c_void_p]),
     'dvd_convbn_finalize': (c_int, [c_void_p] * 6 + [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

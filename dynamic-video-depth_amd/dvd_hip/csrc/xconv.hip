@@ -1113,7 +1113,7 @@ __global__ __launch_bounds__(64 * WM * WN, B1 ? 3 : 2) void xconv_kernel(const X
 static int g_xcfg = 0;    // test / A-B hook (dvd_xconv_select), see pick_cfg
 
 template <int TM, int TN, int WM, int WN, bool FAST, bool B1 = false, bool IN16 = false, bool OUT16 = false>
-static int launch_fi(const XArgs& a, int FI, dim3 grid, size_t lds, hipStream_t s) {
+static int launch_fi(const XArgs& a, int fit, dim3 grid, size_t lds, hipStream_t s) {      // fit: XDecision::fit
   auto go = [&](auto kern) -> int {
     DVD_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, a);
@@ -1123,13 +1123,16 @@ static int launch_fi(const XArgs& a, int FI, dim3 grid, size_t lds, hipStream_t 
   // (a.Cin / a.Cout: per group; ZI: three of four staged cells are structural zeros -- the NEEDED work is counted)
   const double flops = 2.0 * a.N * (double)a.G * a.Cout * a.Cin * a.T * (double)a.H * a.W * (a.ZI ? 0.25 : 1.0);
   if constexpr (TM >= 4 && !B1 && FAST && DVD_XCONV_ROLL != 0) {
-    if (a.T == 1 && FI == 1 && g_xcfg != 6) {
+    if (fit == kXFitOne) {
       flops_add(DVD_FLOP_XCONV_1X1_WIDE, flops);
       return go(xconv_kernel<TM, TN, WM, WN, kXFitOne, FAST, B1, IN16, OUT16>);
     }
   }
+  // (xconv_decide names the one-loop kernel only for the instantiations that have it: anything else here is a bug of the
+  //  decision, never a reason to run another staging family behind dvd_xconv_describe's back)
+  DVD_REQUIRE(fit >= 0 && fit <= kXMaxFI, "xconv: no kernel <%d,%d,%d,%d> with staging family %d", TM, TN, WM, WN, fit);
   flops_add(TM >= 4 ? DVD_FLOP_XCONV_WIDE : (WM == 2 ? DVD_FLOP_XCONV_128 : DVD_FLOP_XCONV_SMALL), flops);
-  switch (FI) {
+  switch (fit) {
     case 1: return go(xconv_kernel<TM, TN, WM, WN, 1, FAST, B1, IN16, OUT16>);
     case 2: return go(xconv_kernel<TM, TN, WM, WN, 2, FAST, B1, IN16, OUT16>);
     case 3: return go(xconv_kernel<TM, TN, WM, WN, 3, FAST, B1, IN16, OUT16>);
@@ -1143,6 +1146,18 @@ static int xconv_mtiles(int M) {
   const int bm = M <= 32 ? 32 : (M <= 64 ? 64 : (M >= 256 ? 256 : 128));
   return (M + bm - 1) / bm * (bm / 32);
 }
+
+// What a call of dvd_xconv_fwd[_h] launches, decided from the shape alone (xconv_decide): the plan of csrc/xconv_tile.h, the
+// instantiation key of xconv_kernel and the launch's LDS size.  dvd_xconv_describe reports it, xconv_launch switches on it.
+struct XDecision {
+  XPlan plan;
+  int s2, zi;             // flags bit 3 / bit 4
+  int in16, out16;
+  int fit;                // FIT of the instantiation: 1 .. kXMaxFI register-prefetched items, 0 direct staging, kXFitOne
+  int vec_out;            // XArgs::vec_out (it sizes the LDS of every 1x1 launch; only the kOne kernels read it)
+  size_t lds;
+  bool wide() const { return vec_out && fit == kXFitOne; }
+};
 
 }  // namespace dvd
 
@@ -1261,11 +1276,10 @@ int dvd_xconv_select(int cfg) {
   return DVD_OK;
 }
 
-static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed, const float* bias, const void* residual,
-                          const void* mask_src, const dvd_bn_params* bn, void* y, float* y_amax, int N, int Cin_total,
-                          int Cout_total, int H, int W, int KS, int groups, int flags, int in16, int out16, dvd_stream_t stream) {
-  DVD_REQUIRE(x && packed && y, "xconv: null pointer");
-  DVD_REQUIRE(in16 || x_amax, "xconv: the input's max|x| scalar is missing (dvd_amax, or the producer's y_amax)");
+// "Decide": every shape check of a launch and its XDecision; pure host code, no HIP call.  aligned16: y, residual and mask_src
+// sit at 16-byte aligned addresses (null counts as aligned).
+static int xconv_decide(int N, int Cin_total, int Cout_total, int H, int W, int KS, int groups, int flags, int in16, int out16,
+                        bool aligned16, dvd::XDecision& d) {
   DVD_REQUIRE(N > 0 && Cin_total > 0 && Cout_total > 0 && H > 0 && W > 0, "xconv: bad shape N=%d Cin=%d Cout=%d H=%d W=%d", N,
               Cin_total, Cout_total, H, W);
   DVD_REQUIRE(groups > 0 && Cin_total % groups == 0 && Cout_total % groups == 0, "xconv: %d groups do not divide the channels",
@@ -1280,17 +1294,70 @@ static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed
   const int s2 = (flags >> 3) & 1, zi = (flags >> 4) & 1;
   DVD_REQUIRE(!(s2 && zi), "xconv: stride-2 forward and stride-2 backward-data are different launches");
   DVD_REQUIRE(!(s2 || zi) || KS == 3, "xconv: the strided forms exist for 3x3 kernels (got %d)", KS);
-  const int Hq = (H + 1) / 2, Wq = (W + 1) / 2;
   const int Cin = Cin_total / groups, Cout = Cout_total / groups;
   // block shape, tile and position mapping of this launch (csrc/xconv_tile.h)
-  dvd::XPlan plan;
+  dvd::XPlan& plan = d.plan;
   const bool planned = dvd::xconv_plan(Cin, Cout, H, W, KS, s2 != 0, in16 != 0, dvd::g_xcfg, plan);
   const bool fast = plan.fast;
   DVD_REQUIRE(fast || !in16, "xconv: fp16 activations need input channels in multiples of 16 (got %d per group)", Cin);
   DVD_REQUIRE(!(s2 || zi) || fast, "xconv: the strided forms need input channels in multiples of 16 (got %d per group)", Cin);
   DVD_REQUIRE(planned, "xconv: no %stile of a %dx%d image with a %dx%d kernel fits the LDS", s2 ? "stride-2 " : "", H, W, KS, KS);
+  DVD_REQUIRE((long long)plan.mblocks * groups <= 65535, "xconv: too many channel blocks");
   const dvd::XCfg& c = plan.c;
   const dvd::XTile& t = plan.t;
+  d.s2 = s2; d.zi = zi; d.in16 = in16 ? 1 : 0; d.out16 = out16 ? 1 : 0;
+  // the 1x1 kernels of the wide wave tiles run the two-chunk loop (kOne), unless the A/B hook 6 turns it off
+  const bool one = c.TM >= 4 && !c.b1 && fast && DVD_XCONV_ROLL != 0 && KS == 1 && t.FI == 1 && dvd::g_xcfg != 6;
+  d.fit = one ? dvd::kXFitOne : (t.FI <= dvd::kXMaxFI ? t.FI : 0);
+  // wide epilogue of the 1x1 kernels: whole 16-byte runs of pixels behind 16-byte aligned pointers
+  d.vec_out = (KS == 1 && ((long long)H * W) % 8 == 0 && t.TC % 8 == 0 && aligned16 && dvd::g_xcfg != 7) ? 1 : 0;
+  d.lds = t.lds;
+  if (d.vec_out && d.lds < (size_t)c.NT() / 64 * 32 * 68 * 4) d.lds = (size_t)c.NT() / 64 * 32 * 68 * 4;   // one tile row per wave
+  return DVD_OK;
+}
+
+// "Launch": the instantiation the decision names
+static int xconv_launch(const dvd::XDecision& d, const dvd::XArgs& a, dim3 grid, hipStream_t s) {
+  const dvd::XCfg& c = d.plan.c;
+  const int fit = d.fit;
+  const size_t lds = d.lds;
+#define DVD_XGO(TM_, TN_, WM_, WN_)                                                                                    \
+  do {                                                                                                                 \
+    if (d.in16 && d.out16) return dvd::launch_fi<TM_, TN_, WM_, WN_, true, false, true, true>(a, fit, grid, lds, s);    \
+    if (d.in16) return dvd::launch_fi<TM_, TN_, WM_, WN_, true, false, true, false>(a, fit, grid, lds, s);              \
+    return dvd::launch_fi<TM_, TN_, WM_, WN_, true>(a, fit, grid, lds, s);                                              \
+  } while (0)
+  if (d.plan.fast) {
+    if (c.TM == 4 && c.WN == 4) DVD_XGO(4, 2, 2, 4);
+    if (c.TM == 4) DVD_XGO(4, 2, 2, 2);
+    if (c.WM == 2 && c.b1) return dvd::launch_fi<2, 2, 2, 2, true, true>(a, fit, grid, lds, s);
+    if (c.TM == 2 && c.WM == 1 && c.b1) return dvd::launch_fi<2, 2, 1, 4, true, true>(a, fit, grid, lds, s);     // (stride 2 only)
+    if (c.TM == 1 && c.b1) return dvd::launch_fi<1, 2, 1, 4, true, true>(a, fit, grid, lds, s);
+    if (c.WM == 2) DVD_XGO(2, 2, 2, 2);
+    if (c.TM == 2) DVD_XGO(2, 2, 1, 4);
+    DVD_XGO(1, 2, 1, 4);
+  }
+#undef DVD_XGO
+  if (c.WM == 2) return dvd::launch_fi<2, 2, 2, 2, false>(a, fit, grid, lds, s);
+  if (c.TM == 2) return dvd::launch_fi<2, 2, 1, 4, false>(a, fit, grid, lds, s);
+  return dvd::launch_fi<1, 2, 1, 4, false>(a, fit, grid, lds, s);
+}
+
+static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed, const float* bias, const void* residual,
+                          const void* mask_src, const dvd_bn_params* bn, void* y, float* y_amax, int N, int Cin_total,
+                          int Cout_total, int H, int W, int KS, int groups, int flags, int in16, int out16, dvd_stream_t stream) {
+  DVD_REQUIRE(x && packed && y, "xconv: null pointer");
+  DVD_REQUIRE(in16 || x_amax, "xconv: the input's max|x| scalar is missing (dvd_amax, or the producer's y_amax)");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  dvd::XDecision d;
+  if (const int st = xconv_decide(N, Cin_total, Cout_total, H, W, KS, groups, flags, in16, out16,
+                                  al16(y) && al16(residual) && al16(mask_src), d))
+    return st;
+  const dvd::XPlan& plan = d.plan;
+  const dvd::XTile& t = plan.t;
+  const int s2 = d.s2, zi = d.zi;
+  const int Hq = (H + 1) / 2, Wq = (W + 1) / 2;
+  const int Cin = Cin_total / groups, Cout = Cout_total / groups;
   const int Hh = plan.Hh, Ww = plan.Ww, S2 = plan.S2;
   dvd::XArgs a;
   a.x = x;
@@ -1314,37 +1381,26 @@ static int xconv_fwd_impl(const void* x, const float* x_amax, const void* packed
   a.nkc = (Cin + 15) / 16; a.npos = t.npos; a.nfi = t.FI;
   a.Hi = s2 ? H : (zi ? Hq : Hh); a.Wi = s2 ? W : (zi ? Wq : Ww); a.S2 = S2; a.ZI = zi;
   a.relu_in = flags & 1; a.relu_out = (flags >> 1) & 1; a.res_relu = (flags >> 2) & 1;
-  const int mblocks = plan.mblocks;
-  a.mbpg = mblocks;
-  DVD_REQUIRE((long long)mblocks * groups <= 65535, "xconv: too many channel blocks");
-  const dim3 grid(t.ntr * t.ntc, mblocks * groups, N);
-  // wide epilogue of the 1x1 kernels: whole 16-byte runs of pixels behind 16-byte aligned pointers
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  a.vec_out = (KS == 1 && ((long long)H * W) % 8 == 0 && t.TC % 8 == 0 && al16(y) && al16(residual) && al16(mask_src) &&
-               dvd::g_xcfg != 7) ? 1 : 0;
-  size_t lds = t.lds;
-  if (a.vec_out && lds < (size_t)c.NT() / 64 * 32 * 68 * 4) lds = (size_t)c.NT() / 64 * 32 * 68 * 4;   // one tile row per wave
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define DVD_XGO(TM_, TN_, WM_, WN_)                                                                                      \
-  do {                                                                                                                   \
-    if (in16 && out16) return dvd::launch_fi<TM_, TN_, WM_, WN_, true, false, true, true>(a, t.FI, grid, lds, s);         \
-    if (in16) return dvd::launch_fi<TM_, TN_, WM_, WN_, true, false, true, false>(a, t.FI, grid, lds, s);                 \
-    return dvd::launch_fi<TM_, TN_, WM_, WN_, true>(a, t.FI, grid, lds, s);                                               \
-  } while (0)
-  if (fast) {
-    if (c.TM == 4 && c.WN == 4) DVD_XGO(4, 2, 2, 4);
-    if (c.TM == 4) DVD_XGO(4, 2, 2, 2);
-    if (c.WM == 2 && c.b1) return dvd::launch_fi<2, 2, 2, 2, true, true>(a, t.FI, grid, lds, s);
-    if (c.TM == 2 && c.WM == 1 && c.b1) return dvd::launch_fi<2, 2, 1, 4, true, true>(a, t.FI, grid, lds, s);     // (stride 2 only)
-    if (c.TM == 1 && c.b1) return dvd::launch_fi<1, 2, 1, 4, true, true>(a, t.FI, grid, lds, s);
-    if (c.WM == 2) DVD_XGO(2, 2, 2, 2);
-    if (c.TM == 2) DVD_XGO(2, 2, 1, 4);
-    DVD_XGO(1, 2, 1, 4);
-  }
-#undef DVD_XGO
-  if (c.WM == 2) return dvd::launch_fi<2, 2, 2, 2, false>(a, t.FI, grid, lds, s);
-  if (c.TM == 2) return dvd::launch_fi<2, 2, 1, 4, false>(a, t.FI, grid, lds, s);
-  return dvd::launch_fi<1, 2, 1, 4, false>(a, t.FI, grid, lds, s);
+  a.mbpg = plan.mblocks;
+  a.vec_out = d.vec_out;
+  const dim3 grid(t.ntr * t.ntc, plan.mblocks * groups, N);
+  return xconv_launch(d, a, grid, static_cast<hipStream_t>(stream));
+}
+
+int dvd_xconv_describe(int Cin_total, int Cout_total, int H, int W, int KS, int groups, int flags, int in_f16, int out_f16,
+                       int operands_aligned16, int* out) {
+  DVD_REQUIRE(out, "xconv_describe: null pointer");
+  dvd::XDecision d;
+  if (const int st = xconv_decide(1, Cin_total, Cout_total, H, W, KS, groups, flags, in_f16 ? 1 : 0, out_f16 ? 1 : 0,
+                                  operands_aligned16 != 0, d))
+    return st;
+  const dvd::XCfg& c = d.plan.c;
+  const dvd::XTile& t = d.plan.t;
+  const int v[DVD_XDESC_INTS] = {c.TM, c.TN, c.WM, c.WN, c.b1 ? 1 : 0, d.plan.fast ? 1 : 0, d.fit, d.in16, d.out16,
+                                 d.wide() ? 1 : 0, d.s2, d.zi, t.TR, t.TC, t.P, t.PQ, t.ntr, t.ntc, d.plan.mblocks,
+                                 (int)d.lds, c.NT(), t.FI, 0, 0};
+  for (int i = 0; i < DVD_XDESC_INTS; ++i) out[i] = v[i];
+  return DVD_OK;
 }
 
 int dvd_xconv_fwd(const float* x, const float* x_amax, const void* packed, const float* bias, const float* residual,

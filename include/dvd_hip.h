@@ -461,6 +461,33 @@ int dvd_xconv_fwd(const float* x, const float* x_amax, const void* packed, const
  * stays on haloed positions in every setting).
  * Results are identical in every setting (same products, same K order). */
 int dvd_xconv_select(int cfg);
+/* What dvd_xconv_fwd (in_f16 = out_f16 = 0) / dvd_xconv_fwd_h (in_f16 = 1) would launch for these arguments, under the current
+ * dvd_xconv_select value: pure host code, no HIP call, usable without a GPU.  Returns what the launch would return for the
+ * shape (DVD_EINVAL with the same message for what it refuses; pointers and N are not its business).  operands_aligned16:
+ * whether y, residual and mask_src all sit at 16-byte aligned addresses (null counts as aligned).  out receives
+ * DVD_XDESC_INTS ints, indexed by the constants below.  The launch code switches on the same decision (csrc/xconv.hip,
+ * XDecision): this is the dispatch, not a copy of it.  tests/xconv_spec.py lists the classes the suite must reach. */
+enum {
+  DVD_XDESC_TM = 0, DVD_XDESC_TN, DVD_XDESC_WM, DVD_XDESC_WN, /* wave tile and waves per block of xconv_kernel                 */
+  DVD_XDESC_B1,        /* one activation stage in LDS                                                                        */
+  DVD_XDESC_FAST,      /* buffer-addressed main loop (0: the generic loop, Cin / groups % 16 != 0)                           */
+  DVD_XDESC_FIT,       /* staging family, DVD_XFIT_*                                                                         */
+  DVD_XDESC_IN16, DVD_XDESC_OUT16,
+  DVD_XDESC_WIDE,      /* the LDS-transposed 16-byte epilogue runs (a DVD_XFIT_ONE kernel with whole aligned runs)           */
+  DVD_XDESC_S2, DVD_XDESC_ZI,
+  DVD_XDESC_TR, DVD_XDESC_TC, DVD_XDESC_P, DVD_XDESC_PQ, DVD_XDESC_NTR, DVD_XDESC_NTC, /* tile, csrc/xconv_tile.h             */
+  DVD_XDESC_MBLOCKS,   /* channel blocks per group                                                                           */
+  DVD_XDESC_LDS_BYTES, DVD_XDESC_THREADS,
+  DVD_XDESC_ITEMS,     /* staging items per thread and chunk                                                                 */
+  DVD_XDESC_INTS = 24
+};
+enum {
+  DVD_XFIT_DIRECT = 0, /* item by item, nothing kept in registers across the matrix instructions (wide halos, stride 2)       */
+  DVD_XFIT_1 = 1, DVD_XFIT_2 = 2, DVD_XFIT_3 = 3, /* register-prefetched staging, items per thread                            */
+  DVD_XFIT_ONE = 11    /* the two-chunk loop of the 1x1 kernels with >= 256 output channels per group                         */
+};
+int dvd_xconv_describe(int Cin_total, int Cout_total, int H, int W, int KS, int groups, int flags, int in_f16, int out_f16,
+                       int operands_aligned16, int* out);
 /* Transposed / forward packing with every weight of output channel co scaled by gamma[co] / sqrt(var[co] + eps): the
  * backward-data pass through a fused BatchNorm is dvd_xconv_fwd on the masked, UNSCALED output gradient. */
 int dvd_xconv_pack_scaled(const float* w, void* packed, int Cout, int Cin, int KS, int groups, int transposed,
