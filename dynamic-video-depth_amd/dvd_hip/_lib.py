@@ -150,6 +150,7 @@ SIGNATURES = {
     'dvd_xwgrad3_workspace_bytes': (c_size_t, [c_int] * 6),
     'dvd_xwgrad1s_workspace_bytes': (c_size_t, [c_int] * 5),
     'dvd_xwgrad_select': (c_int, [c_int]),
+    'dvd_xwgrad_describe': (c_int, [c_int] * 9 + [c_void_p]),          # host only (an addition within ABI 8)
     'dvd_sf_mlp_select': (c_int, [c_int]),
     'dvd_xwgradk_workspace_bytes': (c_size_t, [c_int] * 6),
     'dvd_xwgradk': (c_int, [c_void_p] * 6 + [c_size_t] + [c_int] * 7 + [c_void_p]),

@@ -1320,26 +1320,65 @@ static int wg_with_nk(int nk, F&& f) {
 
 typedef void (*WgKernel)(const Wg3Args);
 
-// The instantiation that runs a launch of nk live K steps of a route (rsum: the RSUM form).  11x11 runs two, kernel columns
-// 0 .. 5 and 6 .. 10: disjoint taps of the same partials.
-static void wg_kernels(const WgRoute& r, bool h16, bool rsum, int nk, WgKernel (&k)[2]) {
-  k[1] = nullptr;
+// The instantiation key of a launch: what wg_kernels() switches on and dvd_xwgrad_describe reports.  nk: the NK template
+// argument, 0 where the instantiation has none to choose (the guarded row step of xwgrad3_kernel keeps four K steps, the dead
+// ones over zeros; the 1x1 kernels).  fw / rsum: the FW / RSUM template arguments (false where the family has no such form).
+struct WgKey {
+  WgFamily fam;
+  int KS;
+  bool h16, fw, rsum;
+  int nk;
+};
+// rsum: the caller wants the row sums AND the route has an RSUM form (gy_rowsum && r.rsum)
+static WgKey wg_key(const WgRoute& r, bool h16, bool rsum, int nk) {
+  WgKey k{r.fam, r.KS, h16, false, false, 0};
+  nk = nk >= 1 && nk <= 3 ? nk : 4;
   switch (r.fam) {
     case kWg3:
+      k.fw = r.fw;
+      k.nk = r.fw ? nk : 0;
+      break;
     case kWg3g:
-      wg_with_nk(nk, [&](auto nkc) -> int {
+      k.rsum = rsum && !h16;
+      k.nk = nk;
+      break;
+    case kWgK:
+      k.nk = nk;
+      break;
+    case kWg1b:
+      k.fw = r.fw;
+      k.rsum = rsum && r.fw && !h16;
+      break;
+    case kWg1s:
+      break;
+  }
+  return k;
+}
+
+// The instantiation of a key.  11x11 runs two, kernel columns 0 .. 5 and 6 .. 10: disjoint taps of the same partials.
+static void wg_kernels(const WgKey& key, WgKernel (&k)[2]) {
+  k[0] = k[1] = nullptr;
+  const bool h16 = key.h16;
+  switch (key.fam) {
+    case kWg3:
+      if (!key.fw) {
+        if (h16) k[0] = xwgrad3_kernel<true, false>;
+        else k[0] = xwgrad3_kernel<false, false>;
+        break;
+      }
+      wg_with_nk(key.nk, [&](auto nkc) -> int {
         constexpr int NK = decltype(nkc)::value;
-        if (r.fam == kWg3g) {
-          if (h16) k[0] = xwgrad3g_kernel<true, false, NK>;
-          else if (rsum) k[0] = xwgrad3g_kernel<false, true, NK>;
-          else k[0] = xwgrad3g_kernel<false, false, NK>;
-        } else if (h16) {        // (the guarded row step -- fp16 rows of odd width -- keeps four K steps, the dead ones over zeros)
-          if (r.fw) k[0] = xwgrad3_kernel<true, true, NK>;
-          else k[0] = xwgrad3_kernel<true, false>;
-        } else {
-          if (r.fw) k[0] = xwgrad3_kernel<false, true, NK>;
-          else k[0] = xwgrad3_kernel<false, false>;
-        }
+        if (h16) k[0] = xwgrad3_kernel<true, true, NK>;
+        else k[0] = xwgrad3_kernel<false, true, NK>;
+        return 0;
+      });
+      break;
+    case kWg3g:
+      wg_with_nk(key.nk, [&](auto nkc) -> int {
+        constexpr int NK = decltype(nkc)::value;
+        if (h16) k[0] = xwgrad3g_kernel<true, false, NK>;
+        else if (key.rsum) k[0] = xwgrad3g_kernel<false, true, NK>;
+        else k[0] = xwgrad3g_kernel<false, false, NK>;
         return 0;
       });
       break;
@@ -1347,19 +1386,19 @@ static void wg_kernels(const WgRoute& r, bool h16, bool rsum, int nk, WgKernel (
       auto pick = [&](auto h, auto nkc) -> int {
         constexpr bool H16 = decltype(h)::value;
         constexpr int NK = decltype(nkc)::value;
-        if (r.KS == 5) k[0] = xwgradk_kernel<H16, 5, 0, 5, NK>;
-        else if (r.KS == 7) k[0] = xwgradk_kernel<H16, 7, 0, 7, NK>;
+        if (key.KS == 5) k[0] = xwgradk_kernel<H16, 5, 0, 5, NK>;
+        else if (key.KS == 7) k[0] = xwgradk_kernel<H16, 7, 0, 7, NK>;
         else k[0] = xwgradk_kernel<H16, 11, 0, 6, NK>, k[1] = xwgradk_kernel<H16, 11, 6, 5, NK>;
         return 0;
       };
-      wg_with_nk(nk, [&](auto nkc) -> int { return h16 ? pick(std::true_type{}, nkc) : pick(std::false_type{}, nkc); });
+      wg_with_nk(key.nk, [&](auto nkc) -> int { return h16 ? pick(std::true_type{}, nkc) : pick(std::false_type{}, nkc); });
       break;
     }
     case kWg1b:
-      if (h16 && r.fw) k[0] = xwgrad1b_kernel<true, true>;
+      if (h16 && key.fw) k[0] = xwgrad1b_kernel<true, true>;
       else if (h16) k[0] = xwgrad1b_kernel<true, false>;
-      else if (rsum) k[0] = xwgrad1b_kernel<false, true, true>;
-      else if (r.fw) k[0] = xwgrad1b_kernel<false, true>;
+      else if (key.rsum) k[0] = xwgrad1b_kernel<false, true, true>;
+      else if (key.fw) k[0] = xwgrad1b_kernel<false, true>;
       else k[0] = xwgrad1b_kernel<false, false>;
       break;
     case kWg1s:
@@ -1367,6 +1406,30 @@ static void wg_kernels(const WgRoute& r, bool h16, bool rsum, int nk, WgKernel (
       else k[0] = xwgrad1s_kernel<false>;
       break;
   }
+}
+
+// What an entry point does for a shape, storage and row-sum request under the current hook: the route, whether the kernel sums
+// the gy rows itself, and the workspace the launches need.  xwgrad_impl launches from it, dvd_xwgrad_describe reports it.
+struct WgCall {
+  WgRoute r;
+  bool rsum;               // the kernel sums the rows it stages (the RSUM form)
+  bool chansum;            // row sums wanted on a route without one: the chansum_kernel pass
+  size_t per, npart, need; // floats of one partial slice, of all slices; workspace bytes
+};
+static bool wg_call(int KS, int N, int Cin_total, int Cout_total, int H, int W, int groups, bool h16, bool want_rowsum, WgCall& c) {
+  if (!wg_route(KS, N, Cin_total, Cout_total, H, W, groups, h16, c.r)) return false;
+  c.rsum = want_rowsum && c.r.rsum;
+  c.chansum = want_rowsum && !c.rsum;
+  c.per = (size_t)KS * KS * Cout_total * c.r.Cin;
+  c.npart = (size_t)c.r.S * c.per;
+  c.need = (c.npart + (c.rsum ? (size_t)c.r.S * Cout_total : 0)) * sizeof(float);
+  return true;
+}
+// bytes an operand's base address must be a multiple of: the kernels read rows (1x1: planes) in the widest items their length
+// allows -- 16 bytes where a row is whole 16-byte items, 8 / 4 where it is whole 8- / 4-byte ones, single elements otherwise
+static size_t wg_operand_align(int KS, int H, int W, bool h16) {
+  const long long row = (KS == 1 ? (long long)H * W : (long long)W) * (h16 ? 2 : 4);
+  return row % 16 == 0 ? 16 : row % 8 == 0 ? 8 : row % 4 == 0 ? 4 : 2;
 }
 
 static int wg_launch(WgKernel kern, const WgRoute& r, const Wg3Args& a, hipStream_t s) {
@@ -1390,12 +1453,17 @@ static int xwgrad_impl(int KS, bool kxk, const void* x, const float* x_amax, con
   DVD_REQUIRE((long long)H * W * (long long)(Cin_total > Cout_total ? Cin_total : Cout_total) < (1ll << 31),
               "%s: image too large for 32-bit offsets", name);
   DVD_REQUIRE(!(h16 && gy_rowsum), "%s: the channel sums exist for fp32 gradients", name);
-  WgRoute r;
-  DVD_REQUIRE((!kxk || KS > 3) && wg_route(KS, N, Cin_total, Cout_total, H, W, groups, h16, r),
+  WgCall c;
+  DVD_REQUIRE((!kxk || KS > 3) && wg_call(KS, N, Cin_total, Cout_total, H, W, groups, h16, gy_rowsum != nullptr, c),
               "%s: kernel size %d (5, 7 and 11 are covered)", name, KS);
-  const bool rsum = gy_rowsum && r.rsum;                             // the kernel sums the rows it stages
-  const size_t per = (size_t)KS * KS * Cout_total * r.Cin, npart = (size_t)r.S * per;
-  const size_t need = (npart + (rsum ? (size_t)r.S * Cout_total : 0)) * sizeof(float);
+  const WgRoute& r = c.r;
+  const bool rsum = c.rsum;                                          // the kernel sums the rows it stages
+  const size_t per = c.per, npart = c.npart, need = c.need;
+  const size_t al = wg_operand_align(KS, H, W, h16);
+  DVD_REQUIRE((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(gy)) % al == 0,
+              "%s: x and gy must be %zu-byte aligned for rows of %d elements", name, al, KS == 1 ? H * W : W);
+  DVD_REQUIRE((reinterpret_cast<size_t>(gw) | reinterpret_cast<size_t>(workspace) | reinterpret_cast<size_t>(gy_rowsum)) % sizeof(float) == 0,
+              "%s: gw, the row sums and the workspace must be 4-byte aligned", name);
   if (workspace_bytes < need) {
     set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
     return DVD_ENOSPC;
@@ -1417,7 +1485,7 @@ static int xwgrad_impl(int KS, bool kxk, const void* x, const float* x_amax, con
   for (int l = 0; l < r.nl; ++l) {
     wg_args_class(a, r.p, r.L[l]);
     WgKernel k[2];
-    wg_kernels(r, h16, rsum, r.L[l].nk, k);
+    wg_kernels(wg_key(r, h16, rsum, r.L[l].nk), k);
     for (int j = 0; j < 2 && k[j]; ++j)
       if (int e = wg_launch(k[j], r, a, s)) return e;
   }
@@ -1425,7 +1493,7 @@ static int xwgrad_impl(int KS, bool kxk, const void* x, const float* x_amax, con
   hipLaunchKernelGGL(xwgrad3_reduce_kernel, dim3(nmain + nrs), dim3(256), 0, s, a.partial, gw, r.S, KS * KS, Cout_total, r.Cin, nmain,
                      a.rowsum_partial, gy_rowsum, Cout_total);
   DVD_LAUNCH_OK();
-  if (gy_rowsum && !rsum) {                      // no RSUM kernel on this route: one fixed-order pass over gy
+  if (c.chansum) {                               // no RSUM kernel on this route: one fixed-order pass over gy
     hipLaunchKernelGGL(chansum_kernel, dim3(Cout_total), dim3(256), 0, s, static_cast<const float*>(gy), N, Cout_total, H * W, gy_rowsum);
     DVD_LAUNCH_OK();
   }
@@ -1448,6 +1516,49 @@ size_t dvd_xwgradk_workspace_bytes(int N, int Cin, int Cout, int H, int W, int K
 int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, int groups) {
   dvd::WgRoute r;
   return (KS == 1 || KS == 3) && dvd::wg_route(KS, N, Cin, Cout, H, W, groups, false, r) && r.rsum ? 1 : 0;
+}
+
+int dvd_xwgrad_describe(int KS, int N, int Cin_total, int Cout_total, int H, int W, int groups, int in_f16, int with_rowsum,
+                        int* out) {
+  DVD_REQUIRE(out, "xwgrad_describe: null pointer");
+  // the row sums exist for the fp32 1x1 and 3x3 entry points; groups other than 1 only for 3x3 (wg_route refuses them too)
+  DVD_REQUIRE(!(with_rowsum && (in_f16 || KS > 3)), "xwgrad_describe: no row sums for fp16 gradients or %dx%d kernels", KS, KS);
+  dvd::WgCall c;
+  DVD_REQUIRE(dvd::wg_call(KS, N, Cin_total, Cout_total, H, W, groups, in_f16 != 0, with_rowsum != 0, c),
+              "xwgrad_describe: no weight-gradient kernel for this shape");
+  for (int i = 0; i < DVD_WDESC_INTS; ++i) out[i] = 0;
+  const dvd::WgRoute& r = c.r;
+  dvd::WgKey key{};
+  for (int l = 0; l < r.nl; ++l) {
+    key = dvd::wg_key(r, in_f16 != 0, c.rsum, r.L[l].nk);
+    int* o = out + DVD_WDESC_L0 + l * DVD_WDESC_L_INTS;
+    o[DVD_WDESC_L_NK] = r.L[l].nk;
+    o[DVD_WDESC_L_KEY_NK] = key.nk;
+    o[DVD_WDESC_L_S] = r.L[l].S;
+    o[DVD_WDESC_L_SLICE0] = r.L[l].slice0;
+    o[DVD_WDESC_L_STRIP0] = r.L[l].strip0;
+    o[DVD_WDESC_L_NCOLS] = r.L[l].ncols;
+  }
+  dvd::WgKernel k[2];
+  dvd::wg_kernels(key, k);
+  out[DVD_WDESC_FAMILY] = (int)key.fam;
+  out[DVD_WDESC_KS] = key.KS;
+  out[DVD_WDESC_H16] = key.h16 ? 1 : 0;
+  out[DVD_WDESC_FW] = key.fw ? 1 : 0;
+  out[DVD_WDESC_RSUM] = key.rsum ? 1 : 0;
+  out[DVD_WDESC_LAUNCHES] = r.nl;
+  out[DVD_WDESC_SECOND] = k[1] ? 1 : 0;
+  out[DVD_WDESC_NCO] = r.p.nco;
+  out[DVD_WDESC_NCI] = r.p.nci;
+  out[DVD_WDESC_LDS_BYTES] = (int)r.p.lds;
+  out[DVD_WDESC_THREADS] = r.nthreads;
+  out[DVD_WDESC_SLICES] = r.S;
+  out[DVD_WDESC_WS_BYTES_LO] = (int)(c.need & 0x7fffffffu);
+  out[DVD_WDESC_WS_BYTES_HI] = (int)(c.need >> 31);
+  out[DVD_WDESC_CHANSUM] = c.chansum ? 1 : 0;
+  out[DVD_WDESC_DEAL] = dvd::g_w3_deal && KS != 1 ? 1 : 0;
+  out[DVD_WDESC_ALIGN] = (int)dvd::wg_operand_align(KS, H, W, in_f16 != 0);
+  return DVD_OK;
 }
 
 int dvd_xwgrad_select(int variant) {

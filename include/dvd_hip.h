@@ -556,7 +556,49 @@ int dvd_xwgrad_rowsum_in_kernel(int N, int Cin, int Cout, int H, int W, int KS, 
  * cut into equal row counts, csrc/wg3_plan.h).  Same products and the same per-element summation order
  * within a slice; the number of slices (partial sums added at the end) differs, so results agree to fp32 rounding, not bitwise. */
 int dvd_xwgrad_select(int variant);
-/* The same for dense 5x5 / 7x7 / 11x11 stride-1 "same" convolutions (round 4: third_party/hourglass.py:21-57, the inception
+/* Alignment of the operands of every dvd_xwgrad3* / dvd_xwgrad1s* / dvd_xwgradk* entry point (checked: DVD_EINVAL before any
+ * launch).  The kernels read a row of x and gy (W elements; for the 1x1 entry points a whole plane, H * W elements) in the widest
+ * items its length allows, so x and gy must sit at a multiple of
+ *     16 bytes where a row is a whole number of 16-byte items (fp32: W % 4 == 0, fp16: W % 8 == 0),
+ *      8 bytes where it is a whole number of 8-byte items,
+ *      4 bytes where it is a whole number of dwords (every fp32 row; fp16 rows of even length: the buffer loads of the
+ *              branch-free row step take dword-aligned 16-byte runs),
+ *      2 bytes otherwise (fp16 rows of odd length: element loads).
+ * Every row of a contiguous tensor then starts on that boundary too.  gw, gy_rowsum and the workspace: 4 bytes.
+ *
+ * What the entry points above would launch for a shape, under the current dvd_xwgrad_select value: pure host code, no HIP call,
+ * usable without a GPU.  KS = 1: dvd_xwgrad1s[_rowsum / _h], 3: dvd_xwgrad3[_rowsum / _h], 5 / 7 / 11: dvd_xwgradk[_h]; in_f16:
+ * the _h entry point; with_rowsum: a gy_rowsum pointer is passed (fp32, KS 1 or 3).  DVD_EINVAL for every shape the size queries
+ * answer 0 for, and for row sums where no entry point takes them.  out receives DVD_WDESC_INTS ints.  The launch path switches
+ * on the same key (csrc/xwgrad3.hip, WgKey / WgCall): this is the dispatch, not a copy of it.  tests/wgrad_spec.py lists the
+ * instantiations the suite must reach. */
+enum {
+  DVD_WDESC_FAMILY = 0,  /* DVD_WFAM_*                                                                                       */
+  DVD_WDESC_KS, DVD_WDESC_H16,
+  DVD_WDESC_FW, DVD_WDESC_RSUM, /* the FW / RSUM template arguments of the instantiation (0 where the family has no such form) */
+  DVD_WDESC_LAUNCHES,    /* 1 or 2 (one per strip class, csrc/wg3_plan.h); an 11x11 launch is two kernels (DVD_WDESC_SECOND)   */
+  DVD_WDESC_L0,          /* first launch: DVD_WDESC_L_INTS ints, the second launch right behind it                           */
+  DVD_WDESC_SECOND = DVD_WDESC_L0 + 12, /* every launch runs a second kernel (11x11: kernel columns 6 .. 10)                  */
+  DVD_WDESC_NCO, DVD_WDESC_NCI,         /* channel blocks per group: grid z / groups, grid y                                 */
+  DVD_WDESC_LDS_BYTES, DVD_WDESC_THREADS,
+  DVD_WDESC_SLICES,      /* partial slices the launches write in all                                                          */
+  DVD_WDESC_WS_BYTES_LO, DVD_WDESC_WS_BYTES_HI, /* workspace bytes the call needs, exactly: LO + HI * 2^31                    */
+  DVD_WDESC_CHANSUM,     /* the row sums come from the extra fixed-order pass over gy                                         */
+  DVD_WDESC_DEAL,        /* whole work items dealt round robin (dvd_xwgrad_select(3))                                         */
+  DVD_WDESC_ALIGN,       /* bytes x and gy must be aligned to                                                                 */
+  DVD_WDESC_INTS = 32
+};
+enum {                   /* per launch                                                                                        */
+  DVD_WDESC_L_NK = 0,    /* live K steps per row step of the strips it walks (1 .. 4)                                         */
+  DVD_WDESC_L_KEY_NK,    /* the NK template argument; 0: the instantiation has none (guarded 3x3 row step, 1x1 kernels)       */
+  DVD_WDESC_L_S, DVD_WDESC_L_SLICE0,      /* slices of the launch (grid x), the first partial slice it writes                  */
+  DVD_WDESC_L_STRIP0, DVD_WDESC_L_NCOLS,  /* the column strips [strip0, strip0 + ncols) of every image (0, 0 for 1x1)          */
+  DVD_WDESC_L_INTS = 6
+};
+enum { DVD_WFAM_XWGRAD3 = 0, DVD_WFAM_XWGRAD3G, DVD_WFAM_XWGRADK, DVD_WFAM_XWGRAD1S, DVD_WFAM_XWGRAD1B };
+int dvd_xwgrad_describe(int KS, int N, int Cin_total, int Cout_total, int H, int W, int groups, int in_f16, int with_rowsum,
+                        int* out);
+/* The weight gradient (as dvd_xwgrad3) of dense 5x5 / 7x7 / 11x11 stride-1 "same" convolutions (round 4: third_party/hourglass.py:21-57, the inception
  * branches; round 3 left their weight gradient to MIOpen): split-operand MFMA, 32 x 32 channels per block, one wave per kernel
  * row, deterministic.  gw [Cout][Cin][KS][KS]. */
 size_t dvd_xwgradk_workspace_bytes(int N, int Cin, int Cout, int H, int W, int KS);

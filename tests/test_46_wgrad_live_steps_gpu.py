@@ -170,7 +170,7 @@ def test_grouped_3x3_and_row_sums(N, C, G, H, W, relu_in):
     assert bool(torch.isfinite(sums).all()) and err <= L * U, '%s: row sums %.3g of sum|g| > %d * 2^-24' % (tag, err, L)
 
 
-@pytest.mark.parametrize('N,C,G,H,W,relu_in', [c for c in GROUPED if c[4] % 2 == 0 and c[4] not in (64, 168)])
+@pytest.mark.parametrize('N,C,G,H,W,relu_in', [c for c in GROUPED if c[4] % 2 == 0])
 def test_grouped_3x3_fp16(N, C, G, H, W, relu_in):
     x, gy = _data(N, C, C, H, W, 346 + W, half=True)
     _check('3x3 grouped fp16 %dx%d g%d %dx%d' % (N, C, G, H, W), x, gy, 3, G, relu_in, half=True)
