@@ -259,6 +259,10 @@ SIGNATURES = {
                                 c_int, c_int, c_void_p]),
     # stored flows chained into the gaps nobody computed (csrc/flow_chain.hip; an addition within ABI 8)
     'dvd_flow_chain': (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p] + [c_int] * 4 + [c_void_p]),
+    # normal equations of the camera refinement from stored flow and depth (csrc/pose.hip; additions within ABI 8)
+    'dvd_pose_workspace_bytes': (c_size_t, [c_int] * 3),
+    'dvd_pose_normal_eq': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_float, c_float, c_float, c_void_p,
+                                                                               c_size_t] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
 }
 RATIO_MEDIAN_WORKSPACE_PER_SEGMENT = 8224      # DVD_RATIO_MEDIAN_WORKSPACE_PER_SEGMENT of include/dvd_hip.h
 

@@ -54,6 +54,7 @@ SOURCES = [
     ('fill.hip', ['-ffp-contract=off']),
     ('point_track.hip', ['-ffp-contract=off']),
     ('flow_chain.hip', ['-ffp-contract=off']),
+    ('pose.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
           '-I' + INCLUDE, '-I' + CSRC]

@@ -123,6 +123,27 @@ def _set_camera_row(tab, i, pose, K):
     tab['cam_c2w'][i] = torch.from_numpy(pose).float()
 
 
+def camera_tables(host_tables, poses, intrinsics=None):
+    """A copy of the per-frame tables `host_tables` (CPU tensors) whose camera rows are rebuilt from `poses`, camera to world
+    [N,4,4] (an array or a tensor; cast to fp32), through _set_camera_row.  intrinsics [N,3,3]: new ones; None keeps every row
+    of K_T and K_inv_T bit for bit.  The time-stamp tables are carried over."""
+    N = int(host_tables['R'].shape[0])
+    poses = np.ascontiguousarray((poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)), dtype=np.float32)
+    if poses.shape != (N, 4, 4) or not np.all(np.isfinite(poses)):
+        raise ValueError('poses must be finite camera-to-world matrices [%d,4,4], got %s' % (N, poses.shape))
+    if intrinsics is not None:
+        intrinsics = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics)
+        if intrinsics.shape != (N, 3, 3) or intrinsics.dtype.kind != 'f' or not np.all(np.isfinite(intrinsics)):
+            raise ValueError('intrinsics must be finite floating-point matrices [%d,3,3], got %s %s' % (N, intrinsics.dtype, intrinsics.shape))
+    tab = {k: v.clone() for k, v in host_tables.items()}
+    for i in range(N):
+        K = host_tables['K_T'][i].numpy().T if intrinsics is None else intrinsics[i]
+        _set_camera_row(tab, i, poses[i], K)
+    if intrinsics is None:
+        tab['K_T'], tab['K_inv_T'] = host_tables['K_T'].clone(), host_tables['K_inv_T'].clone()
+    return tab
+
+
 def frame_tables(frame_files):
     """The small per-frame tables of a list of frame files, computed on the host (CPU tensors; the kernel only copies them).
     `FrameStore` fills the same tables in its one pass over the files; this is the host-only way to them."""
@@ -280,6 +301,18 @@ class FrameStore(object):
         cat.pairs += pairs
         cat.pair_files += [None] * n
         cat.gaps += sorted(set(b - a for a, b in pairs) - set(cat.gaps))
+
+    def set_cameras(self, poses, intrinsics=None):
+        """Installs other cameras -- preprocess.refine_cameras' 'poses', camera to world [N,4,4] -- so that training and every
+        post-processing call use them: the camera rows of host_tables and tables are rebuilt through _set_camera_row
+        (camera_tables).  intrinsics [N,3,3]: new ones too; None keeps K_T and K_inv_T as they are.  Nothing else is touched:
+        the time-stamp tables, the frames, the flows and the depths stay (a depth scale found with the poses is the caller's
+        to apply: store.depth_pred.mul_(scales.view(-1, 1, 1, 1))).  Call it BEFORE store.loader(...): a loader made earlier
+        must be remade."""
+        tab = camera_tables(self.host_tables, poses, intrinsics)
+        self.host_tables = tab
+        self.tables = {k: v.to(self.device) for k, v in tab.items()}
+        torch.cuda.synchronize(self.device)
 
     def frames(self, batch_size):
         """The validation / test view: what DataLoader(Dataset(mode='vali'), batch_size=b) yields, on the device.  Images,

@@ -472,6 +472,97 @@ def triangulate(flow_1_2, flow_2_1, mask_1, mask_2, obs, frames, tables, mode='m
     return res
 
 
+POSE_SUMS = 106             # kPoseSums of csrc/pose.hip: 91 of J^T w J + 13 of J^T w r + the cost + sum w |r|^2
+POSE_MAX_ROWS = 65535
+
+
+def pose_penalty(H, W, huber):
+    """What an observation that a step pushed behind its camera costs per unit weight: Huber's rho of a residual as long as the
+    image's diagonal, huber * (hypot(W, H) - huber / 2) (the square's half should huber exceed the diagonal), as float32."""
+    h, far = float(np.float32(huber)), float(np.hypot(float(W), float(H)))
+    return float(np.float32(h * (far - h / 2) if far > h else far * far / 2))
+
+
+def pose_normal_eq(flow_1_2, flow_2_1, mask_1, mask_2, depth, weight, rows, tables, log_scale, huber, z_near, maps=False, out=None):
+    """The normal equations of the camera refinement, reduced per observation row (dvd_pose_normal_eq, csrc/pose.hip) -> dict of
+    sums float64 [R,106], wsum float64 [R], counts int64 [R,2] and, with `maps`, resid fp32 [R,H,W,2] and gate uint8 [R,H,W].
+      flow_1_2, flow_2_1   [P,H,W,2] fp32;  mask_1, mask_2  [P,H,W] uint8, 0 = valid  (a FrameStore's tensors)
+      depth      [N,1,H,W] (or [N,H,W]) fp32 planar depth per frame;  weight  [N,H,W] fp32 or None (all ones)
+      rows       [R,4] integral rows (pair, a, b, dir), 1 <= R <= 65535: a host array / sequence / CPU tensor
+                 (preprocess.refine_plan builds it; uploaded here).  dir 0 reads flow_1_2 with mask_2, dir 1 flow_2_1 with mask_1.
+                 A row whose pair is outside 0 .. P-1 or whose frames are outside 0 .. N-1 is skipped: zeros
+      tables     {'R': [N,3,3] camera to world, 't': [N,3], 'K_T': [N,3,3], 'K_inv_T': [N,3,3]} -- FrameStore.tables has them
+      log_scale  N finite log depth scales on the host, or None (zeros); the kernel receives float32(exp(.))
+      huber      px, > 0;  z_near > 0: an observation with q.z below it counts in counts[:, 1] and costs pose_penalty()
+      out        optional dict of preallocated outputs
+    sums[:, :91] is the upper triangle of J^T w J over the unknowns [tau_a, omega_a, sigma_a, tau_b, omega_b], sums[:, 91:104]
+    J^T w r, sums[:, 104] the cost, sums[:, 105] sum w |r|^2; include/dvd_hip.h has the formulae and the gates.  Everything is
+    checked on the host before the launch, and nothing synchronises with the device."""
+    what = 'pose_normal_eq'
+    huber = _real_arg(what, 'huber', huber, lo_open=True)
+    z_near = _real_arg(what, 'z_near', z_near, lo_open=True)
+    # the host data first: a bad table is refused before a tensor is looked at
+    try:
+        r = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows)
+    except (TypeError, ValueError):
+        raise RuntimeError('%s: rows must be a host array of integers' % what)
+    r = _host_ids(what, 'rows (pair, a, b, dir)', r, (None, 4), floats=False)
+    R = int(r.shape[0])
+    if not 1 <= R <= POSE_MAX_ROWS:
+        raise RuntimeError('%s: rows must hold 1 .. %d rows per launch, got %d' % (what, POSE_MAX_ROWS, R))
+    if not np.isin(r[:, 3], (0, 1)).all():
+        raise RuntimeError('%s: the dir column of rows must be 0 (flow_1_2) or 1 (flow_2_1)' % what)
+    if np.abs(r).max() >= 1 << 31:
+        raise RuntimeError('%s: rows holds an index beyond int32' % what)
+    n_tab = int(tables['R'].shape[0]) if isinstance(tables, dict) and torch.is_tensor(tables.get('R')) and tables['R'].dim() else None
+    if log_scale is not None:
+        try:
+            ls = np.asarray(log_scale.cpu() if torch.is_tensor(log_scale) else log_scale, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise RuntimeError('%s: log_scale must be a host sequence of numbers, got %r' % (what, log_scale))
+        with np.errstate(over='ignore'):
+            sc = np.exp(ls).astype(np.float32)
+        if ls.ndim != 1 or (n_tab is not None and ls.size != n_tab) or not np.all(np.isfinite(sc)) or not np.all(sc > 0):
+            raise RuntimeError('%s: log_scale must hold one finite value per frame whose exp is a positive float32, got %r' % (what, log_scale))
+    f12 = _dev32(flow_1_2, 'flow_1_2')
+    dev = f12.device
+    if f12 is not flow_1_2 or f12.dim() != 4 or f12.shape[3] != 2 or f12.shape[0] < 1 or f12.shape[1] < 1 or f12.shape[2] < 1:
+        raise RuntimeError('%s: flow_1_2 must be contiguous [P,H,W,2], got %s' % (what, tuple(f12.shape)))
+    P, H, W = (int(v) for v in f12.shape[:3])
+    if H * W >= 1 << 30:
+        raise RuntimeError('%s: images of %d x %d: H * W must stay below 2^30' % (what, H, W))
+    _out_ok(what, 'flow_2_1', flow_2_1, f12.shape, torch.float32, dev, 'flow_1_2')
+    if mask_1 is None or mask_2 is None:
+        raise RuntimeError('%s: mask_1 and mask_2 are required, got None for %s' % (what, 'mask_1' if mask_1 is None else 'mask_2'))
+    mask_1 = _dev_u8(what, 'mask_1', mask_1, (P, H, W), dev, copy=False)
+    mask_2 = _dev_u8(what, 'mask_2', mask_2, (P, H, W), dev, copy=False)
+    tabs, N = _tables(what, tables, TRI_TABLES, (9, 3, 9, 9), dev, 'the flows')
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.device == dev and depth.dtype == torch.float32 and depth.is_contiguous()
+            and tuple(depth.shape) in ((N, 1, H, W), (N, H, W))):
+        raise RuntimeError('%s: depth must be a contiguous float32 GPU tensor [%d,1,%d,%d] on the device of the flows' % (what, N, H, W))
+    if weight is not None:
+        _out_ok(what, 'weight', weight, (N, H, W), torch.float32, dev, 'the flows')
+    if log_scale is None:
+        sc = np.ones(N, np.float32)
+    elif sc.size != N:
+        raise RuntimeError('%s: log_scale holds %d values for %d frames' % (what, sc.size, N))
+    shapes = {'sums': ((R, POSE_SUMS), torch.float64), 'wsum': ((R,), torch.float64), 'counts': ((R, 2), torch.int64)}
+    if maps:
+        shapes.update(resid=((R, H, W, 2), torch.float32), gate=((R, H, W), torch.uint8))
+    res = _outputs(what, out, shapes, dev, 'the flows')
+    lib = _lib.load()
+    ws_bytes = int(lib.dvd_pose_workspace_bytes(R, H, W))
+    ws = torch.empty(ws_bytes // 8, device=dev, dtype=torch.float64)
+    # the rows and the scales in ONE upload from pinned memory, enqueued on the current stream
+    host = torch.from_numpy(np.concatenate([r.astype(np.int32).ravel(), sc.view(np.int32)])).pin_memory()
+    both = host.to(dev, non_blocking=True)
+    _lib.check(lib.dvd_pose_normal_eq(
+        _p(f12), _p(flow_2_1), _p(mask_1), _p(mask_2), P, _p(depth), _p(weight), _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
+        _p(both[4 * R:]), N, _p(both[:4 * R]), huber, z_near, pose_penalty(H, W, huber), _p(ws), ws_bytes, _p(res['sums']),
+        _p(res['wsum']), _p(res['counts']), _p(res.get('resid')), _p(res.get('gate')), R, H, W, _stream()), 'dvd_pose_normal_eq')
+    return res
+
+
 CHAIN_MAX_LINKS = 32        # kChainMaxLinks of csrc/flow_chain.hip
 
 
@@ -1366,7 +1457,8 @@ BYTE_CLASS_KERNELS = {
     'adam': ('adam_kernel', 'sgd_kernel'), 'geometry': ('unproject_', 'track_project_kernel', 'project_bwd_kernel', 'splat_zmin_kernel', 'splat_accumulate_kernel',
                                                    'splat_resolve_kernel', 'eval_tracks_kernel', 'ratio_hist_kernel', 'ratio_pick_kernel',
                                                    'depth_score_kernel', 'track_filter_kernel', 'triangulate_kernel', 'fill_pull_kernel',
-                                                   'fill_mid_kernel', 'fill_push_kernel', 'flow_chain_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
+                                                   'fill_mid_kernel', 'fill_push_kernel', 'flow_chain_kernel', 'pose_normal_eq_kernel',
+                                                   'pose_sum_partials_kernel'), 'gather': ('gather_pairs_kernel', 'store_gather_kernel', 'union_'),
 }
 ALL_CLASSES = FLOP_CLASSES + BYTE_CLASSES
 

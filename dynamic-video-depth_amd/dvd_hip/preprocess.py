@@ -242,6 +242,202 @@ def chain_flows(store, gaps, base=None, chunk=None):
     return res
 
 
+def refine_plan(pairs, n_frames, gaps=None):
+    """The observation rows of ops.pose_normal_eq from `Catalogue.pairs` (host only) -> int32 [R,4], rows (pair, a, b, dir):
+    every stored pair (f_1, f_2) -- restricted to |f_2 - f_1| in `gaps` if given -- in stored order, as (pair, f_1, f_2, 0)
+    (flow_1_2 leaves f_1) and then (pair, f_2, f_1, 1) (flow_2_1 leaves f_2).  A ValueError if that selects no row."""
+    import numpy as np
+    if isinstance(n_frames, bool) or int(n_frames) != n_frames or n_frames < 1:
+        raise ValueError('refine_plan: n_frames must be a positive number of frames, got %r' % (n_frames,))
+    n_frames = int(n_frames)
+    keep = None
+    if gaps is not None:
+        try:
+            keep = set(abs(int(g)) for g in gaps)
+            ok = all(int(g) == g and not isinstance(g, bool) for g in gaps)
+        except (TypeError, ValueError):
+            keep, ok = set(), False
+        if not ok or not keep or min(keep) < 1:
+            raise ValueError('refine_plan: gaps must be non-zero frame distances, got %r' % (gaps,))
+    rows = []
+    for j, (a, b) in enumerate(pairs):
+        a, b = int(a), int(b)
+        if a == b or not (0 <= a < n_frames and 0 <= b < n_frames):
+            raise ValueError('refine_plan: pair %d is (%d, %d) in a video of %d frames' % (j, a, b, n_frames))
+        if keep is None or abs(b - a) in keep:
+            rows += [(j, a, b, 0), (j, b, a, 1)]
+    if not rows:
+        raise ValueError('refine_plan: no row: none of the %d stored pairs has a gap in %r' % (len(pairs), gaps))
+    return np.array(rows, dtype=np.int32)
+
+
+def _exp_so3(w):
+    """Rodrigues' formula in float64."""
+    import numpy as np
+    th = float(np.sqrt(w @ w))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], np.float64)
+    if th < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (np.sin(th) / th) * K + ((1 - np.cos(th)) / (th * th)) * (K @ K)
+
+
+POSE_STALL = 5      # refine_cameras: rejected steps in a row, after an accepted one, that end the loop as converged
+POSE_TRI = [(i, j) for i in range(13) for j in range(i, 13)]        # the order of the 91 entries of J^T w J in a row's sums
+
+
+def _pose_system(sums, rows, N):
+    """The rows' 13 x 13 blocks over [tau_a, omega_a, sigma_a, tau_b, omega_b] -> (H [7N,7N], g [7N], cost) in float64."""
+    import numpy as np
+    Hm, g = np.zeros((7 * N, 7 * N)), np.zeros(7 * N)
+    ti, tj = (np.array(v) for v in zip(*POSE_TRI))
+    for s, (_, a, b, _) in zip(sums, rows.tolist()):
+        idx = np.r_[7 * a:7 * a + 7, 7 * b:7 * b + 6]
+        blk = np.zeros((13, 13))
+        blk[ti, tj] = s[:91]
+        blk[tj, ti] = s[:91]
+        Hm[np.ix_(idx, idx)] += blk
+        g[idx] += s[91:104]
+    return Hm, g, float(np.sum(sums[:, 104]))
+
+
+def refine_cameras(store, depth=None, weight=None, gaps=None, anchor=0, scales=False, huber=1.0, z_near=1e-3, max_iter=30,
+                   rel_tol=1e-9, tables=None):
+    """Camera poses -- and with scales=True one depth scale per frame -- refined against a FrameStore's flows, by
+    Levenberg-Marquardt on the robust reprojection error of every stored flow vector (ops.pose_normal_eq, csrc/pose.hip, over
+    the rows of refine_plan; include/dvd_hip.h has the residual, its gates and the Jacobian).  The depth itself is held fixed.
+      depth    [N,1,H,W] fp32 planar depth on the device; None: store.depth_pred
+      weight   [N,H,W] fp32 on the device, > 0 where the scene is static (triangulate_depth's 'static' as float, or a motion
+               segmentation); None: all ones -- Huber's loss alone does not keep a large moving object from pulling the poses
+      gaps     the frame distances whose pairs are used (None: all)
+      anchor   the frame that stays as it is (it fixes the gauge; with `scales` its scale stays 1)
+      huber    px;  z_near: an observation whose point comes closer to the target camera's plane is not used, and costs as much
+               as a residual as long as the image's diagonal
+      max_iter, rel_tol   it stops after max_iter evaluations of a step, or when an accepted step lowers the cost by less than
+               rel_tol of it, or -- the cost at its rounding floor -- when 5 steps in a row after an accepted one did not lower it
+      tables   the cameras to start from (the store's layout); None: store.tables
+    The loop runs on the host in float64: the 7N x 7N system of the unknowns (tau, omega, sigma) per frame -- c += R tau,
+    R <- R Exp(omega), s = exp(sigma) -- without the anchor's columns, without sigma unless `scales`, without a frame no row
+    touches; (H + lambda diag H) dx = -g with lambda from 1e-3, divided by 10 after a step that lowered the cost, multiplied by
+    10 after one that did not (the state is kept).  Poses stay float64 between the steps and are rounded to fp32 for the
+    kernel's tables.  One launch and one device-to-host copy of its sums per evaluation.
+    -> dict:
+      poses    fp32 [N,4,4] camera to world (a host tensor; FrameStore.set_cameras installs them)
+      tables   the store's tables with these cameras, on the device (triangulate_depth(tables=...) takes them)
+      scales   fp32 [N] on the device, ones without `scales`: store.depth_pred.mul_(scales.view(-1, 1, 1, 1)) applies them
+      cost     the cost after every iteration, the start first (a float64 list)
+      rms_before, rms_after   float64 [R]: sqrt(sum w |r|^2 / sum w) per row, in pixels (0 for a row without an observation)
+      counts   int64 [R,2] at the end: the observations used, and those whose point lies behind z_near
+      rows     int32 [R,4]: refine_plan's rows
+      iterations, accepted, converged"""
+    import numpy as np
+    from . import ops
+    from .datasets.frame_store import camera_tables
+    what = 'refine_cameras'
+    N, H, W = int(store.cat.n_frames), int(store.H), int(store.W)
+    depth = store.depth_pred if depth is None else depth
+    if not (torch.is_tensor(depth) and depth.dtype == torch.float32 and tuple(depth.shape) == (N, 1, H, W)):
+        raise ValueError('%s: depth must be a float32 tensor [%d,1,%d,%d]' % (what, N, H, W))
+    if weight is not None and not (torch.is_tensor(weight) and weight.dtype == torch.float32 and tuple(weight.shape) == (N, H, W)):
+        raise ValueError('%s: weight must be a float32 tensor [%d,%d,%d] (e.g. tri["static"].float()) or None' % (what, N, H, W))
+    rows = refine_plan(store.cat.pairs, N, gaps)
+    if isinstance(anchor, (bool, np.bool_)) or not isinstance(anchor, (int, np.integer)) or not 0 <= anchor < N:
+        raise ValueError('%s: anchor must be one of the frames 0 .. %d, got %r' % (what, N - 1, anchor))
+    if not isinstance(scales, (bool, np.bool_)):
+        raise ValueError('%s: scales must be True or False, got %r' % (what, scales))
+    for name, v, lo_open in (('huber', huber, True), ('z_near', z_near, True), ('rel_tol', rel_tol, False)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (
+                (v > 0 if lo_open else v >= 0) and v <= 3.4028234663852886e+38):
+            raise ValueError('%s: %s must be a finite number %s 0, got %r' % (what, name, '>' if lo_open else '>=', v))
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError('%s: max_iter must be a positive integer, got %r' % (what, max_iter))
+    start = store.tables if tables is None else tables
+    keys = ('R', 't', 'K_T', 'K_inv_T')
+    if not (isinstance(start, dict) and all(torch.is_tensor(start.get(k)) and start[k].dtype == torch.float32 and
+                                            tuple(start[k].shape) == ((N, 3) if k == 't' else (N, 3, 3)) for k in keys)):
+        raise ValueError('%s: tables must hold float32 R [%d,3,3], t [%d,3], K_T and K_inv_T [%d,3,3]' % (what, N, N, N))
+    anchor, R = int(anchor), len(rows)
+    _dev32(store.flow_1_2, 'flow_1_2')                       # (the wrapper checks the rest; this one before anything is pinned)
+    # ---- the state: float64 poses and log-scales on the host
+    host = store.host_tables if tables is None else {k: start[k].cpu() for k in ('R', 't')}
+    poses = np.tile(np.eye(4), (N, 1, 1))
+    poses[:, :3, :3], poses[:, :3, 3] = host['R'].numpy().astype(np.float64), host['t'].numpy().astype(np.float64)
+    first32 = poses.astype(np.float32)
+    sigma = np.zeros(N)
+    seen = set(rows[:, 1:3].ravel().tolist())
+    free = [i for i in range(7 * N) if i // 7 != anchor and i // 7 in seen and (scales or i % 7 != 6)]
+    dev = store.flow_1_2.device if torch.is_tensor(store.flow_1_2) else store.device
+    state = {}
+
+    def evaluate(p64, sg):
+        """One launch per chunk of rows -> (sums [R,106], wsum [R], counts [R,2]) on the host: one copy, the only wait."""
+        p32 = p64.astype(np.float32)
+        cam = torch.from_numpy(np.concatenate([p32[:, :3, :3].reshape(N, 9), p32[:, :3, 3]], 1)).pin_memory().to(dev, non_blocking=True)
+        tab = {'R': cam[:, :9].contiguous().view(N, 3, 3), 't': cam[:, 9:].contiguous(), 'K_T': start['K_T'], 'K_inv_T': start['K_inv_T']}
+        if 'buf' not in state:
+            state['buf'] = torch.empty(R * (ops.POSE_SUMS + 3), device=dev, dtype=torch.int64)
+        buf = state['buf']
+        n_s = R * ops.POSE_SUMS
+        sums, wsum = buf[:n_s].view(torch.float64).view(R, ops.POSE_SUMS), buf[n_s:n_s + R].view(torch.float64)
+        counts = buf[n_s + R:].view(R, 2)
+        for r0 in range(0, R, ops.POSE_MAX_ROWS):
+            r1 = min(r0 + ops.POSE_MAX_ROWS, R)
+            ops.pose_normal_eq(store.flow_1_2, store.flow_2_1, store.mask_1, store.mask_2, depth, weight, rows[r0:r1], tab,
+                               sg if scales else None, huber, z_near,
+                               out={'sums': sums[r0:r1], 'wsum': wsum[r0:r1], 'counts': counts[r0:r1]})
+        h = buf.cpu().numpy()
+        return h[:n_s].view(np.float64).reshape(R, ops.POSE_SUMS), h[n_s:n_s + R].view(np.float64), h[n_s + R:].reshape(R, 2)
+
+    def rms(sums, wsum):
+        return np.sqrt(np.divide(sums[:, 105], wsum, out=np.zeros(R), where=wsum > 0))
+
+    sums, wsum, counts = evaluate(poses, sigma)
+    Hm, g, cost = _pose_system(sums, rows, N)
+    rms_before = rms(sums, wsum)
+    hist, lam, accepted, rejected, converged, it = [cost], 1e-3, 0, 0, False, 0
+    STALL = POSE_STALL
+    for it in range(1, int(max_iter) + 1):
+        Hf, gf = Hm[np.ix_(free, free)], g[free]
+        A = Hf + lam * np.diag(np.diag(Hf))
+        try:
+            step = np.linalg.solve(A, -gf)
+        except np.linalg.LinAlgError:
+            step = np.linalg.lstsq(A, -gf, rcond=None)[0]
+        dx = np.zeros(7 * N)
+        dx[free] = step
+        p2, s2 = poses.copy(), sigma.copy()
+        for f in range(N):
+            d = dx[7 * f:7 * f + 7]
+            if d.any():
+                p2[f, :3, 3] = poses[f, :3, 3] + poses[f, :3, :3] @ d[0:3]
+                p2[f, :3, :3] = poses[f, :3, :3] @ _exp_so3(d[3:6])
+                s2[f] = sigma[f] + d[6]
+        sums2, wsum2, counts2 = evaluate(p2, s2)
+        H2, g2, c2 = _pose_system(sums2, rows, N)
+        if c2 < cost:
+            small = cost - c2 < rel_tol * cost
+            poses, sigma, Hm, g, cost, sums, wsum, counts = p2, s2, H2, g2, c2, sums2, wsum2, counts2
+            lam, accepted, rejected = lam / 10, accepted + 1, 0
+            hist.append(cost)
+            if small:
+                converged = True
+                break
+        else:
+            lam, rejected = lam * 10, rejected + 1
+            hist.append(cost)
+            if accepted and rejected >= STALL:          # no step lowers the cost any more: it is at its rounding floor
+                converged = True
+                break
+    out32 = poses.astype(np.float32)
+    out32[anchor] = first32[anchor]
+    new = camera_tables(store.host_tables, out32)
+    if tables is not None:                                   # (the intrinsics of the start, which may differ from the store's)
+        new['K_T'], new['K_inv_T'] = start['K_T'].cpu().clone(), start['K_inv_T'].cpu().clone()
+    return {'poses': torch.from_numpy(out32), 'tables': {k: v.to(dev) for k, v in new.items()},
+            'scales': torch.from_numpy(np.exp(sigma).astype(np.float32)).to(dev), 'cost': hist, 'rms_before': rms_before,
+            'rms_after': rms(sums, wsum), 'counts': counts.copy(), 'rows': rows, 'iterations': it, 'accepted': accepted,
+            'converged': converged}
+
+
 def scale_poses(w2c, s):
     """World-to-camera matrices [N,4,4] -> camera-to-world fp32 [N,4,4] at the calibrated scale, the reference's three
     statements per frame (generate_frame_midas.py:180-183): `T[:3, 3] *= s`, `np.linalg.inv(T)`, `.astype(np.float32)`.  Host

@@ -1151,6 +1151,46 @@ int dvd_flow_chain(const float* flow_1_2, const float* flow_2_1, const unsigned 
                    const int* links, long long live_links, float* flow_out, long long flow_stride, unsigned char* broken, int L,
                    int B, int H, int W, dvd_stream_t stream);
 
+/* Normal equations of the camera refinement from stored flow and depth (additions within ABI 8; csrc/pose.hip,
+ * ops.pose_normal_eq, preprocess.refine_cameras): one launch reduces, per observation row, the Gauss-Newton system of the
+ * robust reprojection error of a stored flow in the poses of its two frames and the depth scale of the first.
+ *   rows     DEVICE int32 [R, 4], rows (pair, a, b, dir): dir 0 reads flow_1_2[pair] with mask_2[pair], dir != 0 flow_2_1[pair]
+ *            with mask_1[pair] (dvd_triangulate's pairing); a is the frame the flow leaves, b the one it reaches
+ *   flows    fp32 [P, H, W, 2];  masks uint8 [P, H, W], 0 = valid;  depth fp32 [N, H, W] (planar depth per frame);
+ *   weight   fp32 [N, H, W] or null (all ones): what is static;  scale fp32 [N]: s = exp(sigma), the per-frame depth scale
+ *   R, t, K_T, K_inv_T   the per-frame tables of dvd_triangulate (R camera to world, c = t)
+ * Per pixel x = (u, v, 1) of frame a, every multiply and add a separate fp32 operation, every three-term sum as (p0 + p1) + p2,
+ * the divisions IEEE:
+ *   ray = K_a^-1 x;  Ds = D_a(x) * s_a;  P = Ds * ray;  X = R_a P;  Z = X + (c_a - c_b);  Y = R_b^T Z;  q = K_b Y
+ *   proj = q.xy / q.z;  x' = x.xy + flow;  r = proj - x'
+ *   considered  mask byte == 0 && D > 0 && D <= FLT_MAX && weight > 0 && 0 <= x'0 <= W-1 && 0 <= x'1 <= H-1
+ *   live        considered && q.z >= z_near            (a NaN fails every comparison)
+ * A live observation enters with Huber's loss on |r|, threshold huber in pixels: rho = |r|^2 / 2 and IRLS weight 1 inside,
+ * huber (|r| - huber / 2) and huber / |r| outside, both times weight_a(x) (w below is that product), and with the 2 x 13 Jacobian
+ * of r in the local unknowns [tau_a, omega_a, sigma_a, tau_b, omega_b] (c += R tau, R <- R Exp(omega), s = exp(sigma)):
+ *   J = Pi K_b [ M | -M [P]x | M P | -I | [Y]x ],  M = R_b^T R_a,  Pi = (1 / q.z) [[1, 0, -proj_0], [0, 1, -proj_1]]
+ * Outputs, per row:
+ *   sums    float64 [R, 106]: the upper triangle of J^T w J row-major (91), J^T w r (13), the cost = sum of weight * rho over
+ *           the live + penalty * (sum of weight over the considered that are not live), and sum of w |r|^2 over the live
+ *   wsum    float64 [R]: sum of w over the live;   counts  int64 [R, 2]: the live, and the considered that are not live
+ *   resid   fp32 [R, H, W, 2] and gate uint8 [R, H, W], both or neither (null): r where live, (0, 0) elsewhere; 0 not
+ *           considered, 1 live, 2 considered but q.z < z_near
+ * penalty is the cost, per unit weight, of an observation a step has pushed behind its camera (preprocess passes Huber's rho of
+ * a residual as long as the image's diagonal), so that no step lowers the cost that way.  A thread sums at most 16 pixels in fp32,
+ * the wave's 64 lanes are added in fp32, everything after in float64: one partial per (row, block of 4096 pixels) in the
+ * workspace (dvd_pose_workspace_bytes(R, H, W) bytes, 8-byte aligned), summed by a second kernel in ascending block order.  No
+ * atomics, one writer per element: the same inputs give the same bits.  A row whose pair is outside 0 .. P-1 or whose frames are
+ * outside 0 .. N-1 is skipped: zero sums and counts (and zero maps).  Grid (ceil(H W / 4096), R).  DVD_EINVAL before any HIP
+ * call: a null pointer, one of resid / gate without the other, R outside 1 .. 65535, H * W >= 2^30, P < 1, N < 1, huber or z_near
+ * not positive and finite, penalty negative or not finite, a workspace that is too small or misaligned.  Bytes are counted
+ * under DVD_BYTES_GEOMETRY: R H W (8 flow + 1 mask + 4 depth + 4 weight if given + 9 with the maps). */
+size_t dvd_pose_workspace_bytes(int R, int H, int W);
+int dvd_pose_normal_eq(const float* flow_1_2, const float* flow_2_1, const unsigned char* mask_1, const unsigned char* mask_2, int P,
+                       const float* depth, const float* weight, const float* R, const float* t, const float* K_T,
+                       const float* K_inv_T, const float* scale, int N, const int* rows, float huber, float z_near, float penalty,
+                       void* workspace, size_t workspace_bytes, double* sums, double* wsum, long long* counts, float* resid,
+                       unsigned char* gate, int n_rows, int H, int W, dvd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
